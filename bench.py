@@ -2,7 +2,7 @@
 """bench.py -- headline benchmark: M tet-solves/s on the 1 M-tet Kuhn lattice, polar-decomposition Jacobi,
 20 substeps per frame, on N MI355X (BASELINE.json metric; SURVEY.md §8(d) config 3, config 5 shape for N>1).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]          # N > 1 without a launcher: spawns its own N rank processes
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]   # N > 1 without a launcher: spawns its own N rank processes
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -12,17 +12,25 @@ before the timed region; nothing is read back inside it.  N > 1: weak scaling --
 55 x 55 x 55N cells, slab-partitioned along z (one slab, ~1 M tets, per GPU), ghost-vertex positions cross
 xGMI once per substep through RCCL send/recv issued by libtetsim_hip itself.
 
-The JSON line carries two extra objects:
-  roofline      the dominant kernel (pj_tet_kernel, P3+P4 of the reference) against HBM peak.  `achieved` =
-                algorithmic bytes per launch / mean launch duration measured here with HIP events on the
-                handle's own stream.  Bytes per tet are SURVEY.md §8(d)'s tet row (148 B) -- see DESIGN.md.
+A plain run does only what the headline needs: it builds the body, steps the W warm-up and the K timed frames, writes the
+last frame's outputs when --dump-outputs DIR is given (DIR/pos.npy, vel.npy and, polar, quats.npy in the caller's tet order;
+float32, at most 64 MB in all: past that a fixed seeded sample of rows), and prints the line.  Besides the headline fields it
+carries `library` (what was loaded: ABI, source / kernel hashes, "ablation": false for the product build, debug env knobs set)
+and a `roofline` object computed from the timed frames alone (the whole substep's algorithmic bytes at `value` against HBM peak).
+
+--full adds everything else, outside the timed region:
+  roofline      (N = 1) the dominant kernel against HBM peak, from runs of its own: `achieved` = algorithmic bytes per
+                launch / mean launch duration measured here with HIP events on the handle's own stream (replays of the
+                timed frames, the reference's rotation threshold, the lean tet record, the chip's measured copy peak).
+                Bytes per tet are SURVEY.md §8(d)'s tet row (148 B) -- see DESIGN.md.
   cpu_baseline  the CPU restatement (oracle/, "port") of the same algorithm on this host's cores, bounded sample.
-and, outside the timed region:
-  library        what was loaded: ABI, source / kernel hashes, "ablation": false for the product build, debug env knobs set
   other_configs  (N = 1) BASELINE configs 1, 2 and 4 on the same box, bounded to a few seconds
-  multi_gpu      (N > 1) ranks RCCL itself reports, per-rank step time min/max, halo bytes, host enqueue time per substep;
-                 the run FAILS if RCCL's rank count differs from --gpus
-  config5_strong (N = 8, or --config5 on) BASELINE config 5 literally: the 110^3-cell lattice cut into N slabs
+  config5_strong (N = 8, or --config5 on without --full) BASELINE config 5 literally: the 110^3-cell lattice cut into N slabs
+  multi_gpu.halo_exchange_us  (N > 1) both transports' exchange latency on the real wire
+and at N > 1 in every run:
+  multi_gpu      ranks RCCL itself reports, per-rank step time min/max, halo bytes, host enqueue time per substep;
+                 the run FAILS if RCCL's rank count differs from --gpus (the validation run of the other halo transport,
+                 which decides which transport's figures are the headline, belongs to the headline too)
 
 This file is the entry point (arguments, launch modes); the parts live in benchlib/: launcher.py (self-launch, one-line stdout, the
 headline guard), ranks.py (torch.distributed / thread-rank adapters), body.py + headline.py (the body, the timed region, the retry
@@ -51,8 +59,16 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)   # 200 frames = 4000 substeps = 0.17 s timed: past the clock ramp of a short run
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline (after the timed region): the dominant kernel's roofline from runs of "
+                         "its own, the reference threshold and lean-state legs, the measured copy peak, the 8 M-tet body, BASELINE configs 1, 2, 4, "
+                         "the CPU baseline; N > 1: the halo exchange probe and config 5 (auto).  Off: set-up, warm-up, timed steps, outputs, line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32: pos, vel and, polar, "
+                         "quats in the caller's tet order; N > 1: <name>_rank<r>.npy as each rank received them); at most 64 MB in all, a fixed seeded "
+                         "sample of rows beyond that")
     ap.add_argument("--precision", default="fast", choices=["fast", "precise"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--solver", default="polar", choices=["polar", "neohookean"],
                     help="polar (default: the headline, BASELINE configs 3/5) or neohookean (config 4: coloured Gauss-Seidel on the same "
                          "lattice; single GPU only -- it does not partition)")
@@ -61,11 +77,11 @@ def parse_args():
                     help="opt-in TETSIM_FLAG_CONSTANT_REST_SHAPE formulation (NOT the headline: 100 instead of 148 algorithmic B/tet)")
     ap.add_argument("--lean-state", action="store_true",
                     help="the HEADLINE body with TETSIM_FLAG_LEAN_STATE (92 instead of 148 algorithmic B/tet: three carried corners, no quaternion in the substep) -- "
-                         "counter passes and profiles of the lean kernel; the default line already carries value_lean / roofline_lean beside the reference formulation")
-    ap.add_argument("--no-lean", action="store_true", help="N = 1: skip the lean-state leg (value_lean, roofline_lean)")
+                         "counter passes and profiles of the lean kernel; the --full line already carries value_lean / roofline_lean beside the reference formulation")
+    ap.add_argument("--no-lean", action="store_true", help="N = 1, --full: skip the lean-state leg (value_lean, roofline_lean)")
     ap.add_argument("--reference-rotation-exit", action="store_true",
                     help="the HEADLINE body with TETSIM_FLAG_REF_ROTATION_EXIT (|omega| < 1e-9: nine rotation iterations in every tet, the reference's "
-                         "work) -- counter passes of the equal-work kernel; the default line already carries value_reference_threshold beside value")
+                         "work) -- counter passes of the equal-work kernel; the --full line already carries value_reference_threshold beside value")
     ap.add_argument("--cells", type=int, default=CELLS, help="lattice cells per side (default 55 = the 1 M-tet headline; 110 = 8 M tets)")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak (default, what the driver measures): cells^2 x (cells*N) lattice, one slab per GPU; strong: the cells^3 "
@@ -75,11 +91,11 @@ def parse_args():
                          "its interior tet kernel in `roofline` (default at N > 1: whole-substep figures only)")
     ap.add_argument("--config5", default="auto", choices=["auto", "on", "off"],
                     help="N > 1: append BASELINE config 5 literally (the --config5-cells^3 lattice cut into N slabs, strong scaling) as "
-                         "`config5_strong` of the same JSON line; auto = when N == 8")
+                         "`config5_strong` of the same JSON line; auto = when N == 8 and --full")
     ap.add_argument("--config5-cells", type=int, default=110, help="cells per side of the config-5 body (110 = 7,986,000 tets)")
-    ap.add_argument("--no-replay", action="store_true", help="N = 1: time the dominant kernel in the 180 substeps AFTER the timed region only (rounds 1-3), not over a replay of the timed frames")
-    ap.add_argument("--no-beyond-mall", action="store_true", help="N = 1: skip `roofline.beyond_mall` (the 8 M-tet body on this GPU)")
-    ap.add_argument("--no-other-configs", action="store_true", help="N = 1: skip the `other_configs` object (BASELINE configs 1, 2, 4)")
+    ap.add_argument("--no-replay", action="store_true", help="N = 1, --full: time the dominant kernel in the 180 substeps AFTER the timed region only (rounds 1-3), not over a replay of the timed frames")
+    ap.add_argument("--no-beyond-mall", action="store_true", help="N = 1, --full: skip `roofline.beyond_mall` (the 8 M-tet body on this GPU)")
+    ap.add_argument("--no-other-configs", action="store_true", help="N = 1, --full: skip the `other_configs` object (BASELINE configs 1, 2, 4)")
     ap.add_argument("--halo", default="p2p", choices=["p2p", "rccl", "deep"],
                     help="N > 1: transport of the per-substep ghost exchange the HEADLINE run starts with -- p2p (default: the boundary-particle kernel stores "
                          "straight into the neighbours' ghost ranges, mapped through HIP IPC; an RCCL run of the same frames afterwards validates it bit for "

@@ -1,4 +1,6 @@
-"""This rank's body of the benchmark lattice (+ its communicator and, on request, the peer-to-peer halo), and the timed frames."""
+"""This rank's body of the benchmark lattice (+ its communicator and, on request, the peer-to-peer halo), the timed frames, and what
+--dump-outputs writes of their last one."""
+import os
 import time
 
 import numpy as np
@@ -95,3 +97,34 @@ def timed_frames(body, pp, steps, warmup, ranks):
         host += time.perf_counter() - h0
     barrier()
     return time.perf_counter() - t0, host
+
+
+DUMP_BYTES = 64 << 20      # --dump-outputs: at most this much in all (every rank's files together)
+
+
+def read_outputs(body, solver, world):
+    """What a caller of the timed path receives after its last step: positions and velocities of the owned particles and, polar, the
+    per-tet rotation quaternions -- on one GPU in the caller's tet order (tetsim_get_local_tets), on a partition as the rank reads them."""
+    out = {"pos": body.pos.reshape(-1, 3), "vel": body.vel.reshape(-1, 3)}
+    if solver == "polar":
+        q = body.quats
+        if world == 1:
+            full = np.zeros((body.numElems, 4), dtype=np.float32)
+            full[body.localTets] = q
+            q = full
+        out["quats"] = q
+    return out
+
+
+def dump_outputs(outdir, arrays, rank=0, world=1, budget=DUMP_BYTES):
+    """outdir/<name>.npy (N > 1: <name>_rank<r>.npy), float32.  Past budget / world bytes per rank every array keeps the same fraction
+    of its rows: a fixed seeded sample in ascending row order, so that two builds of the project write the same rows."""
+    os.makedirs(outdir, exist_ok=True)
+    share = budget // world - 4096 * len(arrays)          # (room for the .npy headers)
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if total > share and len(a):
+            keep = max(1, len(a) * share // total)
+            a = a[np.sort(np.random.RandomState(12345).choice(len(a), keep, replace=False))]
+        np.save(os.path.join(outdir, name + ("" if world == 1 else "_rank%d" % rank) + ".npy"), a)

@@ -9,7 +9,7 @@ import numpy as np
 
 from .common import CELLS, DT, HBM_PEAK_GBS, PP, ROOT, SUBSTEPS, TET_KERNEL_BYTES, TET_KERNEL_BYTES_LEAN, VERTEX_BYTES
 from .cpu import cpu_baseline
-from .body import make_body, timed_frames
+from .body import dump_outputs, make_body, read_outputs, timed_frames
 from .launcher import GUARD
 from .legs import beyond_mall, demote_p2p, halo_probe_report, multi_gpu_report, other_configs, p2p_check, promote_p2p, run_neohookean, transport_check
 
@@ -170,6 +170,8 @@ def run(args, rank, world, local_rank, ranks):
         elapsed_local, host_local = timed_frames(body, pp, args.steps, args.warmup, ranks)
         if not np.isfinite(body.pos).all():
             raise SystemExit("non-finite positions after the timed region")
+    if args.dump_outputs:   # the last timed frame's results, before anything below steps the body further
+        dump_outputs(args.dump_outputs, read_outputs(body, args.solver, world), rank, world)
     nt_global = len(tets)
     # tetsim_step_n of this body is ONE launch per call (pj_blocked.hip: pjb_call_kernel, TetSimInfo.fused_particle_pass 5): the dominant
     # kernel is then the whole call -- tiles and particles of its 20 substeps -- and is timed as such (events around each launch)
@@ -194,7 +196,7 @@ def run(args, rank, world, local_rank, ranks):
                        "solver": "polar_jacobi", "arithmetic": args.precision,
                        "formulation": "constant rest shape (opt-in)" if args.constant_rest_shape else "lean state (opt-in: three carried corners, no quaternion, 92 B/tet)" if args.lean_state else "reference (rest shape carried from substep to substep, 148 B/tet)", "substeps_per_step": SUBSTEPS,
                        "rotation_exit": "|omega| < 1e-9 throughout (--reference-rotation-exit: the reference's, SoftbodyGPU.js:131)" if getattr(args, "reference_rotation_exit", False) else ("iteration 1: |omega| < 1e-9 (the reference's, SoftbodyGPU.js:131); correction iterations 2..9: |omega| < 1e-6 rad "
-                                         "(FAST default; value_reference_threshold at the top level has the same frames with 1e-9 throughout, and roofline.frac is quoted on THAT kernel)") if args.precision == "fast"
+                                         "(FAST default; with --full, value_reference_threshold at the top level has the same frames with 1e-9 throughout, and roofline.frac is quoted on THAT kernel)") if args.precision == "fast"
                                         else "|omega| < 1e-9 (the reference's, SoftbodyGPU.js:131)",
                        "tets": nt_global, "particles": nv_global,
                        "parallelism": "single GPU" if world == 1 else "z-slab domain decomposition x%d, RCCL ghost halo per substep" % world},
@@ -213,7 +215,7 @@ def run(args, rank, world, local_rank, ranks):
     # beside it on the halo stream.
     pr = None
     replay = None
-    if world == 1 and args.solver == "polar" and not args.no_replay:
+    if world == 1 and args.full and args.solver == "polar" and not args.no_replay:
         # The contract's window for the dominant kernel is the TIMED REGION.  Its launches there are graph nodes (no events of their own),
         # so the same W + K frames are stepped once more on a second body with the library's per-launch events (tetsim_profile: begin /
         # end events around every kernel, on the handle's stream, same kernels in the same order).  The trajectory is deterministic:
@@ -239,7 +241,7 @@ def run(args, rank, world, local_rank, ranks):
     # threshold (TETSIM_FLAG_REF_ROTATION_EXIT: |omega| < 1e-9, all nine iterations in f32, SoftbodyGPU.js:131): wall clock (median of
     # three bodies from rest) -> value_reference_threshold, and per-launch events on a fourth -> the kernel the roofline fraction leads with.
     equal = None
-    if world == 1 and args.solver == "polar" and args.precision == "fast" and not args.no_replay and rank == 0:
+    if world == 1 and args.full and args.solver == "polar" and args.precision == "fast" and not args.no_replay and rank == 0:
         try:
             from tetsim_amd import SoftBodyHIP
             kw = dict(constant_rest_shape=True) if args.constant_rest_shape else dict(lean_state=True) if args.lean_state else {}
@@ -278,7 +280,7 @@ def run(args, rank, world, local_rank, ranks):
         b.close()
         return {"timed_ms": sum(timed) / len(timed), "floor_ms": floor[4], "launches": len(timed), "finite": fin}
     callk = None
-    if one_launch and args.precision == "fast" and not args.no_replay and rank == 0:
+    if one_launch and args.full and args.precision == "fast" and not args.no_replay and rank == 0:
         try:
             kwf = dict(constant_rest_shape=True) if args.constant_rest_shape else dict(lean_state=True) if args.lean_state else {}
             callk = {"ref": call_windows(ref_rotation_exit=True, **kwf), "fast": call_windows(**kwf)}
@@ -288,7 +290,7 @@ def run(args, rank, world, local_rank, ranks):
     # tet (three carried corners, no quaternion) -- wall clock with the FAST exit (value_lean) and with the reference's threshold
     # (value_lean_reference_threshold), medians of three bodies from rest each, and the kernel on the floor by per-launch events + in graphs.
     lean = None
-    if world == 1 and args.solver == "polar" and args.precision == "fast" and not args.no_replay and not args.no_lean and rank == 0 and not args.constant_rest_shape and not args.lean_state:
+    if world == 1 and args.full and args.solver == "polar" and args.precision == "fast" and not args.no_replay and not args.no_lean and rank == 0 and not args.constant_rest_shape and not args.lean_state:
         try:
             from tetsim_amd import SoftBodyHIP
 
@@ -327,7 +329,7 @@ def run(args, rank, world, local_rank, ranks):
                     "floor_substep_us": floor_sub, "finite": finite, "call": lean_call}
         except Exception as e:  # noqa: BLE001
             print("[bench] the lean-state leg failed: %r" % (e,), file=sys.stderr)
-    if world == 1 or (args.profile_ranks and args.precision == "fast"):
+    if (world == 1 and args.full) or (args.profile_ranks and args.precision == "fast"):
         # three batches of 60 substeps, the median batch is reported (a single batch right after the timed region is
         # occasionally 5-8% slow on a box that agrees with rocprofv3 otherwise)
         batches = sorted((body.profile(SUBSTEPS * 3, DT, pp) for _ in range(3)), key=lambda p: p["tet_ms"] / p["tet_launches"])
@@ -556,9 +558,9 @@ def run(args, rank, world, local_rank, ranks):
                        "fast_exit_on_floor": cw(lc["fast"]["floor_ms"], "nine launches ~45 frames in, FAST exit, median" + how, alg_lc)})
 
     def whole_job_roofline():
-        # N > 1 without --profile-ranks: the whole-job figure only (no extra GPU work after the timed region)
+        # a plain run, and N > 1 without --profile-ranks: the whole-job figure only (no extra GPU work after the timed region)
         agg = b_alg * out["value"] * 1e6 / 1e9
-        return {"bound": "hbm", "kernel": "whole substep, all ranks (tet + particle kernels)", "achieved": round(agg, 1),
+        return {"bound": "hbm", "kernel": "whole substep%s (tet + particle kernels)" % (", all ranks" if world > 1 else ""), "achieved": round(agg, 1),
                 "peak": HBM_PEAK_GBS * world, "unit": "GB/s", "frac": round(agg / (HBM_PEAK_GBS * world), 4), "traffic": None,
                 "substep_alg_bytes_per_tet": round(b_alg, 1)}
     if rank == 0 and pr is None:
@@ -566,9 +568,10 @@ def run(args, rank, world, local_rank, ranks):
     # ---- optional legs of an N-rank run: nothing below may cost the headline (HeadlineGuard) ------------------------------------
     if use_dist and world > 1:
         GUARD.arm(out, int(os.environ.get("TETSIM_BENCH_OPTIONAL_S", "240")), "the legs after the headline (peer-to-peer halo check / config 5)")
-        hp = halo_probe_report(body, ranks)   # (the body is between steps: the timed region ended with a sync + barrier)
-        if rank == 0 and out is not None and "multi_gpu" in out:
-            out["multi_gpu"]["halo_exchange_us"] = hp
+        if args.full:
+            hp = halo_probe_report(body, ranks)   # (the body is between steps: the timed region ended with a sync + barrier)
+            if rank == 0 and out is not None and "multi_gpu" in out:
+                out["multi_gpu"]["halo_exchange_us"] = hp
     check = args.p2p_check == "on" or (args.p2p_check == "auto" and not args.fake_ranks)
     if use_dist and world > 1 and used_halo in ("p2p", "deep") and check:
         # The headline ran on the peer-to-peer halo.  RCCL is the VALIDATOR: the same frames from the same rest state on a fresh body whose
@@ -605,7 +608,7 @@ def run(args, rank, world, local_rank, ranks):
                     out["roofline"]["substep_achieved"] = round(b_alg * out["value"] * 1e6 / 1e9, 1)
                     out["roofline"]["substep_frac"] = round(b_alg * out["value"] * 1e6 / 1e9 / (HBM_PEAK_GBS * world), 4)
     # ---- BASELINE config 5, literally: the 110^3-cell lattice (7,986,000 tets) cut into N slabs -- strong scaling -----------
-    if use_dist and (args.config5 == "on" or (args.config5 == "auto" and world == 8)) and not (args.scaling == "strong" and cells == args.config5_cells):
+    if use_dist and (args.config5 == "on" or (args.config5 == "auto" and world == 8 and args.full)) and not (args.scaling == "strong" and cells == args.config5_cells):
         # (the headline body stays alive: if this second body cannot be built on some rank, the line above is still reported)
         body5, v5, t5, pp5, _, err5 = make_body(args, args.config5_cells, "strong", rank, world, local_rank, ranks, vote=True, halo=used_halo)   # (the transport the headline ended up with)
         if body5 is None:
@@ -637,10 +640,10 @@ def run(args, rank, world, local_rank, ranks):
             except Exception as e:  # noqa: BLE001
                 print("[bench] side leg failed: %r" % (e,), file=sys.stderr)
                 return {"error": repr(e)[:300]}
-        if not args.no_beyond_mall and args.precision == "fast" and cells == CELLS and args.solver == "polar" and "roofline" in out:
+        if args.full and not args.no_beyond_mall and args.precision == "fast" and cells == CELLS and args.solver == "polar" and "roofline" in out:
             out["roofline"]["beyond_mall"] = side_leg(lambda: beyond_mall(args, local_rank, out["roofline"].get("measured_copy_peak", {})))
-        if not args.no_other_configs and args.precision == "fast" and cells == CELLS:
+        if args.full and not args.no_other_configs and args.precision == "fast" and cells == CELLS:
             out["other_configs"] = side_leg(lambda: other_configs(args.steps, args.warmup))
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = side_leg(lambda: cpu_baseline(verts, tets))
     return out, body

@@ -8,7 +8,7 @@ import time
 
 import numpy as np
 
-from .body import make_body
+from .body import dump_outputs, make_body, read_outputs
 from .common import CELLS, DT, GOLD, HBM_PEAK_GBS, PP, ROOT, SUBSTEPS, TET_KERNEL_BYTES, VERTEX_BYTES
 
 def other_configs(steps=20, warmup=5):
@@ -117,10 +117,11 @@ def run_neohookean(args, verts, tets, device):
     elapsed = time.perf_counter() - t0
     if not np.isfinite(body.pos).all():
         raise SystemExit("non-finite positions after the timed region")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, read_outputs(body, "neohookean", 1))
     value = len(tets) * SUBSTEPS * args.steps / elapsed / 1e6
     b_alg = 56.0 + 124.0 * len(verts) / len(tets)   # idx 16 + invRestPose 36 + invRestVolume 4; 124 B per particle
     agg = b_alg * value * 1e6 / 1e9
-    pr = body.profile(SUBSTEPS * 3, DT, PP)
     out = {
         "metric": "tet_solves_per_sec", "value": round(value, 1), "unit": "M tet-solves/s", "n_gpus": 1, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
@@ -134,11 +135,13 @@ def run_neohookean(args, verts, tets, device):
         # the HBM figure is reported because the contract asks for one
         "roofline": {"bound": "hbm", "kernel": "whole substep (Gauss-Seidel sweep + particle pass)", "achieved": round(agg, 1),
                      "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(agg / HBM_PEAK_GBS, 4), "traffic": None,
-                     "sweep_us_per_substep": round(pr["tet_ms"] / pr["substeps"] * 1e3, 2),
-                     "particle_us_per_substep": round(pr["vertex_ms"] / pr["substeps"] * 1e3, 2),
                      "substep_alg_bytes_per_tet": round(b_alg, 1)},
     }
-    if not args.no_cpu_baseline:
+    if args.full:   # the sweep and the particle pass by their own events, 60 more substeps
+        pr = body.profile(SUBSTEPS * 3, DT, PP)
+        out["roofline"]["sweep_us_per_substep"] = round(pr["tet_ms"] / pr["substeps"] * 1e3, 2)
+        out["roofline"]["particle_us_per_substep"] = round(pr["vertex_ms"] / pr["substeps"] * 1e3, 2)
+    if args.full and not args.no_cpu_baseline:
         body.close()
         from oracle import OracleNH
         nh = OracleNH(verts, tets, PP)

@@ -24,7 +24,7 @@ def _run(args, env=None):
 
 
 def test_single_gpu_line():
-    d = _run(["--cells", "14", "--steps", "3", "--warmup", "1"])
+    d = _run(["--cells", "14", "--steps", "3", "--warmup", "1", "--full"])
     assert REQUIRED | {"cpu_baseline"} <= set(d)
     assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0 and d["higher_is_better"] is True
     assert d["metric"] == "tet_solves_per_sec" and d["unit"] == "M tet-solves/s" and d["vs_baseline"] is None and d["dtype"] == "f32"
@@ -53,10 +53,41 @@ def test_single_gpu_line():
     assert rl["kernel"] == "pjb_tet_kernel_lean" and rl["finite"] is True and abs(rl["frac"] - rl["achieved"] / 8000.0) < 1e-3 and rl["on_floor"]["kernel_us"] > 0
 
 
+def test_plain_line_is_the_headline_alone_and_dumps_the_last_timed_frame(tmp_path):
+    """A plain run (no --full): the headline fields, `library` and a roofline object from the timed frames alone -- none of the legs
+    --full adds.  --dump-outputs writes what the timed path computed in its last step: bit-equal to the same W + K frames stepped here,
+    and identical from run to run."""
+    a, b = tmp_path / "a", tmp_path / "b"
+    d = _run(["--cells", "14", "--steps", "3", "--warmup", "1", "--dump-outputs", str(a)])
+    assert REQUIRED <= set(d) and d["steps"] == 3 and d["warmup"] == 1 and d["metric"] == "tet_solves_per_sec" and d["dtype"] == "f32"
+    assert abs(d["value"] - d["config"]["tets"] * 20 / (d["ms_per_step"] * 1e-3) / 1e6) / d["value"] < 1e-3
+    moved = {"cpu_baseline", "other_configs", "value_reference_threshold", "value_lean", "roofline_lean"}
+    assert not moved & set(d) and "on_floor" not in d["roofline"] and "measured_copy_peak" not in d["roofline"]
+    rf = d["roofline"]
+    assert rf["bound"] == "hbm" and rf["peak"] == 8000.0 and abs(rf["frac"] - rf["achieved"] / rf["peak"]) < 1e-3
+    _run(["--cells", "14", "--steps", "3", "--warmup", "1", "--dump-outputs", str(b)])
+    import numpy as np
+    from tetsim_amd import SoftBodyHIP, make_lattice
+    from benchlib.common import DT, PP, SUBSTEPS
+    v, t = make_lattice(14)
+    body = SoftBodyHIP(v, t, None, dict(PP), solver="polar", precision="fast")
+    for _ in range(4):
+        body.simulateSubsteps(SUBSTEPS, DT, PP)
+    q = np.zeros((len(t), 4), dtype=np.float32)
+    q[body.localTets] = body.quats
+    want = {"pos": body.pos.reshape(-1, 3), "vel": body.vel.reshape(-1, 3), "quats": q}
+    body.close()
+    assert sorted(os.listdir(a)) == ["pos.npy", "quats.npy", "vel.npy"]
+    for name, w in want.items():
+        x, y = np.load(a / (name + ".npy")), np.load(b / (name + ".npy"))
+        assert x.dtype == np.float32 and x.shape == w.shape and np.isfinite(x).all()
+        assert np.array_equal(x.view(np.uint32), w.view(np.uint32)) and np.array_equal(x.view(np.uint32), y.view(np.uint32)), name
+
+
 def test_headline_line_carries_every_baseline_config():
     """The default workload (1 M-tet lattice): `other_configs` reports BASELINE configs 1, 2 and 4 next to the headline
     (config 3), and roofline.traffic is either null or keyed to this very kernel build."""
-    d = _run(["--steps", "3", "--warmup", "1", "--no-cpu-baseline"])
+    d = _run(["--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--full"])
     assert d["config"]["tets"] == 998250
     rf = d["roofline"]
     # round 6: tetsim_step_n of this body is ONE launch per call (pjb_call_kernel: tiles + particles of the 20 substeps) -- THAT is the dominant
@@ -101,7 +132,7 @@ def test_headline_line_carries_every_baseline_config():
 
 def test_neohookean_line_on_request():
     """`--solver neohookean` (BASELINE config 4): same metric and JSON shape, never the default."""
-    d = _run(["--solver", "neohookean", "--order", "clustered", "--cells", "10", "--steps", "3", "--warmup", "1", "--precision", "precise", "--no-cpu-baseline"])
+    d = _run(["--solver", "neohookean", "--order", "clustered", "--cells", "10", "--steps", "3", "--warmup", "1", "--precision", "precise", "--no-cpu-baseline", "--full"])
     assert REQUIRED <= set(d) and d["config"]["solver"] == "neohookean_gs" and d["dtype"] == "f64" and d["value"] > 0
     assert d["roofline"]["bound"] == "hbm" and d["roofline"]["substep_alg_bytes_per_tet"] > 56
 
@@ -120,7 +151,7 @@ def test_a_failed_n_rank_run_is_repeated_with_more_conservative_halo_settings():
     """bench.py's retry ladder (headline_with_retries): a failure on ANY rank is voted on, every rank closes its body, and all of them
     rebuild -- new communicator, new body -- with the halo path enqueued eagerly; the line carries the attempts.  The failure is
     injected on rank 1 after the first rung's timed region (TETSIM_BENCH_TEST_FAIL_FIRST_RUNG)."""
-    d = _run(["--fake-ranks", "3", "--cells", "12", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"],
+    d = _run(["--fake-ranks", "3", "--cells", "12", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--full"],
              env={"TETSIM_RCCL_LIB": _mock_rccl(), "TETSIM_BENCH_TEST_FAIL_FIRST_RUNG": "1"})
     assert REQUIRED <= set(d) and d["n_gpus"] == 3 and d["value"] > 0
     att = d["multi_gpu"]["halo_attempts"]
@@ -129,7 +160,7 @@ def test_a_failed_n_rank_run_is_repeated_with_more_conservative_halo_settings():
     assert len(att) == 3 and "peer-to-peer" in att[0]["halo"] and "skipped" in att[0] and att[1]["ok"] is False and "default" in att[1]["halo"] and att[2]["ok"] is True and "eagerly" in att[2]["halo"]
     assert d["multi_gpu"]["rccl_ranks"] == 3 and d["multi_gpu"]["halo"].startswith("rccl")
     # --halo rccl: RCCL first, no peer-to-peer rung at all
-    d = _run(["--fake-ranks", "3", "--cells", "12", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--halo", "rccl"], env={"TETSIM_RCCL_LIB": _mock_rccl()})
+    d = _run(["--fake-ranks", "3", "--cells", "12", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--halo", "rccl", "--full"], env={"TETSIM_RCCL_LIB": _mock_rccl()})
     assert "halo_attempts" not in d["multi_gpu"] and "RCCL ghost halo" in d["config"]["parallelism"]
 
 
@@ -142,7 +173,7 @@ def test_multi_rank_code_path_with_thread_ranks(extra):
                            capture_output=True, text=True)
         assert r.returncode == 0, r.stderr[-2000:]
     cells = 24 if "--profile-ranks" in extra else 12      # per-kernel profiling needs interior tiles on every rank
-    d = _run(["--fake-ranks", "3", "--cells", str(cells), "--steps", "3", "--warmup", "1", "--no-cpu-baseline"] + extra, env={"TETSIM_RCCL_LIB": lib})
+    d = _run(["--fake-ranks", "3", "--cells", str(cells), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--full"] + extra, env={"TETSIM_RCCL_LIB": lib})
     assert REQUIRED <= set(d) and d["n_gpus"] == 3 and d["value"] > 0
     cells_z = cells if "strong" in extra else 3 * cells
     assert d["config"]["tets"] == cells * cells * cells_z * 6 and d["scaling"] == ("strong" if "strong" in extra else "weak")
@@ -178,7 +209,7 @@ def test_real_torch_distributed_adapter_with_one_rank(how):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(MASTER_ADDR="127.0.0.1", MASTER_PORT="29581")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--cells", "14", "--steps", "3", "--warmup", "1",
-                        "--no-cpu-baseline"] + how, capture_output=True, text=True, timeout=900, env=env)
+                        "--no-cpu-baseline", "--full"] + how, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, r.stdout[-2000:]

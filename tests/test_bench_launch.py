@@ -130,3 +130,44 @@ def test_the_headline_of_an_n_rank_run_is_the_faster_transport_only_when_validat
         assert b.promote_p2p(out, bad, 20, 8) is False and out == line()
     out = line()
     assert b.promote_p2p(out, dict(good), 20, 8, mode="rccl") is False and out == line()
+
+
+def test_dumped_outputs_stay_under_their_budget_with_a_fixed_sample(tmp_path):
+    """bench.py --dump-outputs (benchlib/body.py dump_outputs): float32 .npy files named after the arrays; past the byte budget every array
+    keeps the same fraction of its rows, the same rows from run to run; an N-rank run's files carry the rank."""
+    import numpy as np
+    from benchlib.body import dump_outputs
+    rng = np.random.RandomState(0)
+    arrays = {"pos": rng.rand(5000, 3), "quats": rng.rand(20000, 4).astype(np.float32)}
+    dump_outputs(str(tmp_path / "whole"), arrays)
+    for name, a in arrays.items():
+        x = np.load(tmp_path / "whole" / (name + ".npy"))
+        assert x.dtype == np.float32 and np.array_equal(x, a.astype(np.float32))
+    budget = 200_000
+    for d in ("s1", "s2"):
+        dump_outputs(str(tmp_path / d), arrays, budget=budget)
+    total = 0
+    for name, a in arrays.items():
+        x, y = np.load(tmp_path / "s1" / (name + ".npy")), np.load(tmp_path / "s2" / (name + ".npy"))
+        assert x.dtype == np.float32 and 0 < len(x) < len(a) and x.shape[1:] == a.shape[1:] and np.array_equal(x, y)
+        rows = {r.tobytes(): i for i, r in enumerate(a.astype(np.float32))}
+        idx = [rows[r.tobytes()] for r in x]
+        assert idx == sorted(idx)                          # the sample keeps the caller's row order
+        total += os.path.getsize(tmp_path / "s1" / (name + ".npy"))
+    assert total <= budget
+    dump_outputs(str(tmp_path / "ranks"), arrays, rank=2, world=4)
+    assert sorted(os.listdir(tmp_path / "ranks")) == ["pos_rank2.npy", "quats_rank2.npy"]
+
+
+def test_full_and_dump_outputs_are_options_and_full_is_off_by_default():
+    b = _bench()
+    saved = sys.argv
+    try:
+        sys.argv = ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"]
+        a = b.parse_args()
+        assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+        sys.argv = ["bench.py", "--full", "--dump-outputs", "out"]
+        a = b.parse_args()
+        assert a.full is True and a.dump_outputs == "out"
+    finally:
+        sys.argv = saved

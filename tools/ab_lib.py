@@ -14,7 +14,7 @@ libs = args[:args.index("--")] if "--" in args else args
 for rep in range(3):
     for lib in libs:
         env = dict(os.environ, TETSIM_HIP_LIB=os.path.abspath(lib))
-        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-other-configs",
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-other-configs",
                               "--no-beyond-mall"] + extra, env=env, capture_output=True, text=True)
         try:
             d = json.loads(out.stdout.strip().splitlines()[-1])

@@ -14,7 +14,7 @@ if not os.path.exists(LIB):
     raise SystemExit("build the ablation library first: python -m tetsim_amd.build --ablation")
 for it in ("0", "3", "6", "9"):
     env = dict(os.environ, TETSIM_DEBUG_ITERS=it, TETSIM_HIP_LIB=LIB)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "30", "--warmup", "5", "--no-cpu-baseline", "--no-other-configs", "--no-beyond-mall"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "30", "--warmup", "5", "--no-cpu-baseline", "--no-other-configs", "--no-beyond-mall"],
                          env=env, capture_output=True, text=True).stdout
     d = json.loads(out.strip().splitlines()[-1])
     assert d["library"]["ablation"] is True

@@ -1,5 +1,5 @@
 """Per-FRAME means of the tet kernel, the particle kernel and the substep (start-to-start of consecutive tet kernels) from a rocprofv3
---kernel-trace csv of `bench.py --steps K --warmup W`: the headline body's W + K frames (graph replays, FAST exit), then the first
+--kernel-trace csv of `bench.py --full --steps K --warmup W`: the headline body's W + K frames (graph replays, FAST exit), then the first
 reference-threshold body's (graph replays) -- how the kernel's duration moves with the phase of the fall, inside the graphs.
 python tools/attic/trace_frames.py <..._kernel_trace.csv> K W [every=10]"""
 import csv, sys

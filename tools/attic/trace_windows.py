@@ -1,4 +1,4 @@
-"""The dominant kernel per WINDOW of `bench.py --steps K --warmup W` (N = 1, polar, FAST), from a rocprofv3 --kernel-trace csv of that
+"""The dominant kernel per WINDOW of `bench.py --full --steps K --warmup W` (N = 1, polar, FAST), from a rocprofv3 --kernel-trace csv of that
 command.  Windows in the order bench.py issues them (benchlib/headline.py):
   headline body:            W warm-up frames + K TIMED frames                      (graph replays, FAST exit)
   replay body:              W + K frames                                           (per-launch events, FAST exit)

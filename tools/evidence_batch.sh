@@ -18,10 +18,10 @@ python tools/tolerance_report.py "$OUT/errors.jsonl" > "$OUT/tolerances.txt" 2>&
 timeout 900 bash tools/mutation_check.sh "$OUT/mutation" > "$OUT/mutation.txt" 2>&1
 MUTATION=iters timeout 900 bash tools/mutation_check.sh "$OUT/mutation_iters" > "$OUT/mutation_iters.txt" 2>&1
 timeout 1500 bash tools/ceiling_batch.sh $TAG > "$OUT/ceiling_batch.log" 2>&1
-timeout 300 python bench.py > "$OUT/bench_200.json" 2>> "$OUT/bench.err"
+timeout 300 python bench.py --full > "$OUT/bench_200.json" 2>> "$OUT/bench.err"
 BENCH_ARGS="--solver neohookean" timeout 900 bash tools/pmc_run.sh $TAG/pmc_nh > "$OUT/pmc_nh.log" 2>&1
 python tools/pmc_summary.py "$OUT/pmc_nh" > "$OUT/pmc_counters_nh.txt" 2>&1
-( cd /tmp && export TMPDIR=/tmp && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats_nh" -o s -- python "$ROOT/bench.py" --solver neohookean --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/stats_nh.log" 2>&1 )
+( cd /tmp && export TMPDIR=/tmp && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats_nh" -o s -- python "$ROOT/bench.py" --full --solver neohookean --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/stats_nh.log" 2>&1 )
 rm -f "$OUT"/stats_nh/*kernel_trace.csv "$OUT"/pmc_nh/pass*/*kernel_trace.csv
 timeout 300 python tools/dragon_time.py > "$OUT/dragon.txt" 2>&1
 timeout 300 python tools/nh_time.py 55 clustered > "$OUT/nh_time.txt" 2>&1

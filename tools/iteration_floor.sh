@@ -11,7 +11,7 @@ res = {n: [] for n, _ in libs}
 for rep in range(3):
     for n, lib in libs:
         env = dict(os.environ, TETSIM_HIP_LIB=os.path.abspath(os.path.join("tetsim_amd", lib)))
-        out = subprocess.run([sys.executable, "bench.py", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-other-configs", "--no-beyond-mall"],
+        out = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-other-configs", "--no-beyond-mall"],
                              env=env, capture_output=True, text=True)
         try:
             r = json.loads(out.stdout.strip().splitlines()[-1])["roofline"]

@@ -5,8 +5,9 @@ set -u
 TAG=${1:-pmc}
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
+ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 cd /tmp && export TMPDIR=/tmp
-CMD="python $GRAFT_REPO_ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-other-configs --no-beyond-mall ${BENCH_ARGS:-}"
+CMD="python $ROOT/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-other-configs --no-beyond-mall ${BENCH_ARGS:-}"
 i=0
 while read -r group; do
   [ -z "$group" ] && continue
