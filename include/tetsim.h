@@ -371,6 +371,48 @@ int tetsim_start_grab(tetsim_handle h, const float xyz[3], int32_t *id_out);
  * tetsim_set_grab(id, xyz) on every partition -- only the owner pins it. */
 int tetsim_nearest_particle(tetsim_handle h, const float xyz[3], int32_t *global_id, double *dist2);
 
+/* --- kinematic colliders ------------------------------------------------------------------------ */
+
+/* Obstacles the body cannot enter: spheres, capsules, oriented boxes and half-spaces, moved by the host between calls.  An
+ * ADDITIVE extension of ABI version 5 (TETSIM_ABI_VERSION is unchanged; no existing struct changed): look the symbol up.
+ *
+ * The list is handle state, like the grab: it takes effect at the next step call and stays fixed for every substep of that call.
+ * One list applies to every body of a batch; each partition takes the list its caller gives it and applies it to every particle it
+ * advances (first-layer ghosts of TETSIM_FLAG_DEEP_GHOSTS included).  It is not solver state: tetsim_save_state blobs do not hold it.
+ *
+ * Per particle and substep the colliders run AFTER the reference's clamp, floor and grab and BEFORE the velocity, in list order,
+ * one pass each, and never on a grabbed particle.  With p the position so far, prev the end of the previous substep and
+ * dot(u, v) = (u.x*v.x + u.y*v.y) + u.z*v.z:
+ *   sphere   d = p - a, L = sqrt(dot(d, d)); hit = L < radius && L > 0; n = d / L, depth = radius - L
+ *   capsule  ab = b - a, t = dot(p - a, ab) / dot(ab, ab) (0 if dot(ab, ab) == 0), t = min(max(t, 0), 1); d = p - (a + ab*t),
+ *            then as the sphere
+ *   box      l_k = dot(p - a, axes[k]); hit iff |l_k| < b[k] for k = 0, 1, 2; k = the smallest b[k] - |l_k| (lowest k on ties);
+ *            n = l_k >= 0 ? axes[k] : -axes[k], depth = b[k] - |l_k|
+ *   plane    s = dot(p - a, b); hit = s < 0, n = b, depth = -s
+ * and on a hit:  p = p + n*depth;  D = (prev - p) + velocity*dt;  T = D - n*dot(D, n);  p = p + T*min(1, dt*friction).
+ * The plane y = 0 with normal (0, 1, 0), velocity 0 and the call's friction is the reference's floor.  Arithmetic: f32 in the
+ * polar solver (PRECISE: no contraction, correctly rounded / and sqrt, the order above); Neo-Hookean PRECISE: f64 on the stored
+ * f32 positions and the f64 collider values, p rounded to f32 after the push and again after the friction; FAST: f32 with
+ * contraction and hardware reciprocals (tolerance level). */
+enum { TETSIM_COLLIDER_SPHERE = 0, TETSIM_COLLIDER_CAPSULE = 1, TETSIM_COLLIDER_BOX = 2, TETSIM_COLLIDER_PLANE = 3 };
+#define TETSIM_MAX_COLLIDERS 8
+typedef struct TetSimCollider {
+    int32_t kind;        /* TETSIM_COLLIDER_* */
+    int32_t reserved;    /* must be 0 */
+    double a[3];         /* sphere / box centre, capsule end A, a point on the plane */
+    double b[3];         /* capsule end B; box half-extents; plane normal (points out of the solid) */
+    double axes[9];      /* box only: its local x, y, z axes in world space (rows) */
+    double radius;       /* sphere, capsule */
+    double friction;     /* like physicsParams.friction: min(1, dt*friction) of the tangential slip is removed per contact */
+    double velocity[3];  /* the collider's own velocity (m/s); friction acts on motion relative to it */
+} TetSimCollider;
+/* Replace the handle's list (count 0: none; colliders may then be NULL).  TETSIM_EINVAL, leaving the previous list in force, for:
+ * count > TETSIM_MAX_COLLIDERS; an unknown kind or a non-zero `reserved`; a non-finite value in any field; a negative
+ * radius, half-extent or friction; a zero-length plane normal or box axis; box axes that are not orthogonal (|u_i . u_j| > 1e-5
+ * after normalisation).  Plane normals and box axes are normalised here in f64 (v / sqrt(v . v)); the f32 paths use the values
+ * rounded once to f32. */
+int tetsim_set_colliders(tetsim_handle h, const TetSimCollider *colliders, uint32_t count);
+
 /* --- measurement ----------------------------------------------------------------------------- */
 
 /* Run n substeps eagerly on the handle's own stream; every POLAR_JACOBI kernel carries its own begin/end HIP

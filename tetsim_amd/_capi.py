@@ -17,6 +17,8 @@ FLAG_REF_SLOT_TABLE, FLAG_REF_FIXED_BOUNDS, FLAG_GATHER_FORMULATION, FLAG_CONSTA
 FLAG_REF_ROTATION_EXIT = 64
 FLAG_LEAN_STATE = 128
 K_TET, K_VERTEX, K_HALO, K_COUNT = 0, 1, 2, 3
+COLLIDER_SPHERE, COLLIDER_CAPSULE, COLLIDER_BOX, COLLIDER_PLANE = 0, 1, 2, 3
+MAX_COLLIDERS = 8
 
 
 class TetSimParams(C.Structure):
@@ -88,6 +90,11 @@ class TetSimError(RuntimeError):
         self.code = code
 
 
+class TetSimCollider(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("a", C.c_double * 3), ("b", C.c_double * 3), ("axes", C.c_double * 9),
+                ("radius", C.c_double), ("friction", C.c_double), ("velocity", C.c_double * 3)]
+
+
 # every symbol include/tetsim.h declares (tests check the library exports exactly these)
 SYMBOLS = [
     "tetsim_abi_version", "tetsim_default_options", "tetsim_default_params", "tetsim_create", "tetsim_create_batch", "tetsim_get_batch_layout", "tetsim_destroy",
@@ -96,7 +103,7 @@ SYMBOLS = [
     "tetsim_read_positions", "tetsim_read_positions_pinned", "tetsim_read_prev_positions", "tetsim_read_velocities", "tetsim_read_quats",
     "tetsim_read_vol_error", "tetsim_write_state", "tetsim_get_owned_ids", "tetsim_get_local_tets",
     "tetsim_get_tet_order", "tetsim_get_level_offsets", "tetsim_read_inv_mass", "tetsim_set_visual_mesh", "tetsim_get_visual_ids", "tetsim_halo_refresh_final", "tetsim_group_refresh_final", "tetsim_halo_probe", "tetsim_halo_p2p_probe",
-    "tetsim_read_visual_mesh", "tetsim_set_visual_triangles", "tetsim_read_visual_vertex_normals", "tetsim_visual_vertex_normals_from", "tetsim_group_read_visual_vertex_normals", "tetsim_set_grab",
+    "tetsim_read_visual_mesh", "tetsim_set_visual_triangles", "tetsim_read_visual_vertex_normals", "tetsim_visual_vertex_normals_from", "tetsim_group_read_visual_vertex_normals", "tetsim_set_grab", "tetsim_set_colliders",
     "tetsim_start_grab", "tetsim_nearest_particle", "tetsim_profile", "tetsim_time_kernels", "tetsim_time_step_n", "tetsim_measure_copy_bandwidth", "tetsim_measure_stream_bandwidth",
     "tetsim_comm_unique_id", "tetsim_comm_init", "tetsim_comm_info", "tetsim_comm_selftest", "tetsim_comm_probe", "tetsim_group_step_n", "tetsim_halo_exchange_local", "tetsim_get_halo_plan",
     "tetsim_halo_p2p_export", "tetsim_halo_p2p_connect",
@@ -106,6 +113,9 @@ SYMBOLS = [
     "tetsim_plan_create_deep", "tetsim_plan_layers", "tetsim_plan_neighbour_layer2", "tetsim_plan_neighbour_layer2_ids",
     "tetsim_mesh_write", "tetsim_mesh_open", "tetsim_mesh_arrays", "tetsim_mesh_close", "tetsim_create_from_file",
 ]
+
+# additive to ABI 5 (looked up by name: a library built before them lacks them and still loads; calling one then raises)
+OPTIONAL_SYMBOLS = ("tetsim_set_colliders",)
 
 _lib = None
 
@@ -169,6 +179,8 @@ def lib():
     L.tetsim_visual_vertex_normals_from.argtypes = [H, fp, fp]
     L.tetsim_group_read_visual_vertex_normals.argtypes = [C.POINTER(H), u32, fp, fp]
     L.tetsim_set_grab.argtypes = [H, i32, fp]
+    if hasattr(L, "tetsim_set_colliders"):   # (additive to ABI 5: a library built before it lacks the symbol and still loads)
+        L.tetsim_set_colliders.argtypes = [H, C.POINTER(TetSimCollider), u32]
     L.tetsim_start_grab.argtypes = [H, fp, ip]
     L.tetsim_profile.argtypes = [H, u32, dbl, PP, C.POINTER(TetSimProfile)]
     L.tetsim_time_kernels.argtypes = [H, u32, dbl, PP, C.POINTER(TetSimProfile)]
@@ -207,6 +219,8 @@ def lib():
     L.tetsim_plan_neighbour_layer2.argtypes = [H, u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
     L.tetsim_plan_neighbour_layer2_ids.argtypes = [H, u32, ip, ip, ip]
     for s in SYMBOLS:
+        if s in OPTIONAL_SYMBOLS and not hasattr(L, s):
+            continue
         f = getattr(L, s)
         if s not in ("tetsim_default_options", "tetsim_default_params", "tetsim_destroy", "tetsim_last_error",
                      "tetsim_plan_destroy"):

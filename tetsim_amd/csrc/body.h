@@ -166,6 +166,10 @@ struct tetsim_body {
     int32_t grab_global = -1;
     int32_t grab_ref[2] = {-1, -1};  // particles the reference's indexFromUV pins for grab_global (TETSIM_FLAG_REF_GRAB_TEXEL)
     float grab_pos[3] = {0, 0, 0};
+    // kinematic colliders (tetsim_set_colliders), normalised, in the two views fill_params copies into DevParams
+    uint32_t n_colliders = 0;
+    DevColliderF col[kMaxColliders] = {};
+    DevColliderD d_col[kMaxColliders] = {};
     std::map<uint32_t, hipGraphExec_t> graphs;
     std::vector<void*> allocs;
     std::vector<float> h_verts;

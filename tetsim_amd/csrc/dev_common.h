@@ -3,9 +3,23 @@
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
 
 namespace tetsim {
+
+// A kinematic collider (tetsim_set_colliders; collide.h), in the two arithmetic views the kernels read: the host normalises plane
+// normals and box axes in f64 and rounds the f32 view once.  a: sphere / box centre, capsule end A, point on the plane; b: capsule
+// end B, box half-extents, plane normal; u: box axes (rows); v: the collider's velocity.
+constexpr uint32_t kMaxColliders = 8;   // TETSIM_MAX_COLLIDERS
+struct DevColliderF {
+    float a[3], b[3], u[9], radius, friction, v[3];
+    int32_t kind, pad;
+};
+struct DevColliderD {
+    double a[3], b[3], u[9], radius, friction, v[3];
+    int32_t kind, pad;
+};
 
 // Per-step dynamic parameters, resident in device memory so that captured HIP graphs stay valid when
 // the caller changes dt / physicsParams / grab between frames (kernels read it with scalar loads).
@@ -19,11 +33,31 @@ struct DevParams {
     int32_t grab_local2; // second pinned particle (TETSIM_FLAG_REF_GRAB_TEXEL can select two), -1 = none
     uint32_t epoch;      // persistent frame kernel (pj_blocked.hip): sequence number of this call's first substep (the host advances it by 65536 per parameter push: tetsim_api.hip push_params)
     int32_t poll_delay;  // pj_quad.hip frame kernel: s_sleep units (64 clocks each) between a tile's partial-sum store and its first look at the neighbours'
-    int32_t pad3[1];
+    uint32_t n_colliders;  // colliders in use (col / d_col below), 0 = none
     // f64 view -- NEOHOOKEAN_GS: JS numbers (Softbody.js:195-240)
     double d_dt, d_gravity, d_friction, d_dev_compliance, d_vol_compliance;
     double d_lo[3], d_hi[3];
+    // kinematic colliders (collide.h): entries [0, n_colliders) are meaningful, in both views.  Behind every field above, so that a
+    // body without colliders reads what it always read at the offsets it always read it from.
+    DevColliderF col[kMaxColliders];     // f32 view: polar solver, FAST Neo-Hookean
+    DevColliderD d_col[kMaxColliders];   // f64 view: PRECISE Neo-Hookean
 };
+// The fields in front of the colliders: what every launch that takes the parameters by value copies into DevParams whatever the list.
+constexpr size_t kDevParamsHead = offsetof(DevParams, col);
+static_assert(kDevParamsHead % 8 == 0 && offsetof(DevParams, d_col) % 8 == 0, "DevParams layout");
+// By-value parameter blocks (DevParams plus a launch's other arguments, e.g. PJBlk for pjb_call_kernel) must stay within the kernel-argument
+// limit HIP guarantees (4 KiB, as CUDA before 12.1; no ROCm header names it).  Each launcher static_asserts its own block against it.
+constexpr size_t kKernelArgLimit = 4096;
+static_assert(sizeof(DevParams) <= 2560, "DevParams must leave room for the other by-value arguments of a launch");
+// A launch's parameters into DevParams by its first lane: the fixed fields, then only the colliders in use (a body without colliders
+// copies what it always copied).
+__device__ __forceinline__ void store_params(DevParams* dst, const DevParams& v) {
+    const uint2* s = reinterpret_cast<const uint2*>(&v);   // (8-byte words: the struct's alignment, wherever the argument sits)
+    uint2* d = reinterpret_cast<uint2*>(dst);
+#pragma unroll
+    for (size_t i = 0; i < kDevParamsHead / 8; i++) d[i] = s[i];
+    for (uint32_t k = 0; k < v.n_colliders && k < kMaxColliders; k++) { dst->col[k] = v.col[k]; dst->d_col[k] = v.d_col[k]; }
+}
 
 // ---- POLAR_JACOBI device state (all arrays 16-byte elements: one dwordx4 per lane) ----------------
 struct PJDev {
@@ -316,4 +350,11 @@ void util_launch_p2p_probe(hipStream_t s, const P2PProbe& p, uint32_t base, uint
 void util_launch_gather4(hipStream_t s, const float4* src, const int32_t* idx, float4* dst, uint32_t n);
 
 
+}  // namespace tetsim
+
+namespace tetsim {
+// the largest by-value argument blocks: a PJBlk or NHDev with the parameters and at most a dozen scalars / pointers
+// (pjb_call_kernel, the frame kernels, nh_predict_value_kernel, nh_frame_kernel)
+static_assert(sizeof(PJBlk) + sizeof(DevParams) + 128 <= kKernelArgLimit, "PJBlk + DevParams exceed the kernel-argument limit");
+static_assert(sizeof(NHDev) + sizeof(DevParams) + 128 <= kKernelArgLimit, "NHDev + DevParams exceed the kernel-argument limit");
 }  // namespace tetsim

@@ -10,6 +10,7 @@
 // (host_prep.cpp prep_levels); tets of one level share no vertex, and any two tets that do share a
 // vertex keep their sequential order, so every lane sees exactly the positions the sequential sweep
 // would have given it.
+#include "collide.h"
 #include "dev_common.h"
 #include "dev_store.h"
 
@@ -198,6 +199,7 @@ struct VParams {
     T dt, gravity, friction, lo[3], hi[3];
     int32_t grab_local;
     float grab[3];
+    const DevParams* all;   // the colliders (collide.h)
 };
 __device__ __forceinline__ VParams load_vparams(const DevParams& P) {
     VParams q;
@@ -209,6 +211,7 @@ __device__ __forceinline__ VParams load_vparams(const DevParams& P) {
 #pragma unroll
     for (int k = 0; k < 3; k++) { q.lo[k] = static_cast<T>(P.d_lo[k]); q.hi[k] = static_cast<T>(P.d_hi[k]); q.grab[k] = P.grab[k]; }
     q.grab_local = P.grab_local;
+    q.all = &P;
     return q;
 }
 
@@ -237,7 +240,7 @@ __global__ __launch_bounds__(256) void TETSIM_SFX(nh_predict_kernel_)(NHDev d) {
 // ... with the call's parameters among its arguments: the first kernel of a call that is launched directly (nh_call_kernel's prediction)
 // brings them along and leaves them in DevParams for the kernels behind it -- no upload in front of the call.
 __global__ __launch_bounds__(256) void TETSIM_SFX(nh_predict_value_kernel_)(NHDev d, DevParams pv, DevParams* pdev) {
-    if (blockIdx.x == 0u && threadIdx.x == 0u) *pdev = pv;
+    if (blockIdx.x == 0u && threadIdx.x == 0u) store_params(pdev, pv);
     const uint32_t v = blockIdx.x * 256u + threadIdx.x;
     if (v >= d.nv) return;
     float4 vel = d.vel[v], pos = d.pos[v], prev;
@@ -283,7 +286,15 @@ __device__ __forceinline__ void post_vertex(const VParams& P, uint32_t v, float4
         pos.x = fr(static_cast<T>(pos.x) + static_cast<T>(Fx) * m);
         pos.z = fr(static_cast<T>(pos.z) + static_cast<T>(Fz) * m);
     }
-    if (static_cast<int32_t>(v) == P.grab_local) { pos.x = P.grab[0]; pos.y = P.grab[1]; pos.z = P.grab[2]; }
+    const bool grabbed = static_cast<int32_t>(v) == P.grab_local;
+    if (grabbed) { pos.x = P.grab[0]; pos.y = P.grab[1]; pos.z = P.grab[2]; }
+    if (P.all->n_colliders != 0u && !grabbed) {   // kinematic colliders (collide.h)
+#if TETSIM_FAST
+        collide_f32<true>(pos.x, pos.y, pos.z, prev.x, prev.y, prev.z, *P.all);
+#else
+        collide_f64(pos.x, pos.y, pos.z, prev.x, prev.y, prev.z, *P.all);
+#endif
+    }
 #if TETSIM_FAST
     const T inv_dt = __builtin_amdgcn_rcpf(dt);
 #else
@@ -601,7 +612,7 @@ __device__ __forceinline__ T nh_solve_record_quad(float* const sp, const NHTetRe
 // leaves them in DevParams for the kernels behind this one).
 __global__ __launch_bounds__(512) void TETSIM_SFX(nh_frame_kernel_)(NHDev d, const uint32_t* __restrict__ seg, const uint32_t* __restrict__ first_vert,
                                                                    uint32_t levels, uint32_t bodies, uint32_t n, DevParams pv, DevParams* pdev) {
-    if (blockIdx.x == 0u && threadIdx.x == 0u) *pdev = pv;
+    if (blockIdx.x == 0u && threadIdx.x == 0u) store_params(pdev, pv);
     extern __shared__ float4 s_frame[];
     const uint32_t body = blockIdx.x, vbase = first_vert[body], nvb = first_vert[body + 1u] - vbase;
     float4* const s_pos = s_frame;                                        // [nvb] xyz + inverse mass

@@ -43,6 +43,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "collide.h"
 #include "dev_common.h"
 #include "dev_store.h"
 #include "host_prep.h"
@@ -73,7 +74,8 @@ __device__ __forceinline__ VertexOut pjb_vertex_update(f3 acc, float wsum, f3 pr
     const float rw = __builtin_amdgcn_rcpf(wsum);
     f3 p = F3(acc.x * rw, acc.y * rw, acc.z * rw);  // 0 * inf = NaN for a particle without tets, as in the reference
     // P6, SoftbodyGPU.js:340-355
-    if (static_cast<int32_t>(v) == P.grab_local || static_cast<int32_t>(v) == P.grab_local2) p = F3(P.grab[0], P.grab[1], P.grab[2]);
+    const bool grabbed = static_cast<int32_t>(v) == P.grab_local || static_cast<int32_t>(v) == P.grab_local2;
+    if (grabbed) p = F3(P.grab[0], P.grab[1], P.grab[2]);
     p.x = fminf(fmaxf(p.x, P.lo[0]), P.hi[0]);
     p.y = fminf(fmaxf(p.y, P.lo[1]), P.hi[1]);
     p.z = fminf(fmaxf(p.z, P.lo[2]), P.hi[2]);
@@ -84,6 +86,7 @@ __device__ __forceinline__ VertexOut pjb_vertex_update(f3 acc, float wsum, f3 pr
         p.x = fmaf(Fx, fr, p.x);
         p.z = fmaf(Fz, fr, p.z);
     }
+    if (P.n_colliders != 0u && !grabbed) collide_f32<true>(p.x, p.y, p.z, prev.x, prev.y, prev.z, P);   // kinematic colliders (collide.h)
     // P7, :364-372, then P1 + P2 of the next substep
     const float dt = P.dt;
     const float rdt = __builtin_amdgcn_rcpf(dt);
@@ -621,7 +624,7 @@ __device__ __forceinline__ void pjb_frame_body(const PJBlk& d, const DevParams& 
 #define TETSIM_FRAME_KERNEL(name, mode, local)                                                                                         \
     __global__ __launch_bounds__(kTile, 2) void name(PJBlk d, uint32_t n, const int32_t* block_tile, float4* pbuf0, float4* pbuf1, uint32_t* err, \
                                                      uint32_t timeout_ms, DevParams pv, DevParams* pdev) {                             \
-        if (blockIdx.x == 0u && threadIdx.x == 0u) *pdev = pv; /* (parameters by value: see pjb_call_kernel) */                      \
+        if (blockIdx.x == 0u && threadIdx.x == 0u) store_params(pdev, pv); /* (parameters by value: see pjb_call_kernel) */             \
         pjb_frame_body<mode, local>(d, pv, n, block_tile, pbuf0, pbuf1, err, timeout_ms);                                              \
     }
 TETSIM_FRAME_KERNEL(pjb_frame_kernel, kModeCarried, false)
@@ -753,7 +756,7 @@ __global__ __launch_bounds__(kTile, 2) void pjb_call_kernel(PJBlk d, uint32_t n_
                                                            uint32_t* err, uint32_t timeout_ms, DevParams pv, DevParams* pdev TETSIM_DBG_PARAM) {
     const uint32_t sub = blockIdx.x / blocks_per_sub, r = blockIdx.x - sub * blocks_per_sub;   // (blocks_per_sub is a multiple of 8: r and blockIdx.x land on the same XCD)
     const uint32_t stamp = (d.epoch ? d.epoch : pv.epoch) + sub + 1u;
-    if (blockIdx.x == 0u && threadIdx.x == 0u) *pdev = pv;
+    if (blockIdx.x == 0u && threadIdx.x == 0u) store_params(pdev, pv);
     if (r < tet_blocks) {
         const PJPoll poll = {r, sub ? stamp - 1u : 0u, err, timeout_ms};
         pjb_tet_body<kMode, false, false, false, true>(d, 0u, tile_count, tiles_per_xcd TETSIM_DBG_ARG, nullptr, stamp, &poll);

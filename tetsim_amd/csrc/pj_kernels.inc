@@ -14,6 +14,7 @@
 //                                prediction x* = x_final + v*dt.
 // The arithmetic inside each lane is written in the order of the GLSL source so that the PRECISE build
 // (IEEE f32, no contraction) differs from the CPU restatement only through sin().
+#include "collide.h"
 #include "dev_common.h"
 #include "pj_lab.h"
 
@@ -102,7 +103,8 @@ __global__ __launch_bounds__(256) void TETSIM_SFX(pj_vertex_kernel_)(PJDev d, ui
 
     // P6, :340-355
     const f3 prev = xyz(prev4);  // end of the previous substep == texturePrevPos after P1
-    if (static_cast<int32_t>(v) == P.grab_local || static_cast<int32_t>(v) == P.grab_local2) p = F3(P.grab[0], P.grab[1], P.grab[2]);
+    const bool grabbed = static_cast<int32_t>(v) == P.grab_local || static_cast<int32_t>(v) == P.grab_local2;
+    if (grabbed) p = F3(P.grab[0], P.grab[1], P.grab[2]);
     p.x = fminf(fmaxf(p.x, P.lo[0]), P.hi[0]);
     p.y = fminf(fmaxf(p.y, P.lo[1]), P.hi[1]);
     p.z = fminf(fmaxf(p.z, P.lo[2]), P.hi[2]);
@@ -113,6 +115,7 @@ __global__ __launch_bounds__(256) void TETSIM_SFX(pj_vertex_kernel_)(PJDev d, ui
         p.x += F.x * fr;
         p.z += F.z * fr;
     }
+    if (P.n_colliders != 0u && !grabbed) collide_f32<kFast>(p.x, p.y, p.z, prev.x, prev.y, prev.z, P);   // kinematic colliders (collide.h)
     // P7, :364-372
     const f3 dpos = p - prev;
     f3 vel;

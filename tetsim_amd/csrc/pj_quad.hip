@@ -27,6 +27,7 @@
 // Differences from the other FAST formulations are summation order only (64-tet tiles, component-wise sums): tolerance level.
 #include <cstdint>
 
+#include "collide.h"
 #include "dev_common.h"
 #include "dev_store.h"
 #include "host_prep.h"
@@ -147,7 +148,7 @@ __device__ __forceinline__ void pjq_solve(float cur[4], float rest[4], QRot& q, 
 }
 
 // ---- P5's division + P6 + P7 (+ P1, P2 of the next substep) for one component of one particle ---------------------------------
-struct QParams { float dt, rdt, fr, g_dt, lo, hi, grab; int32_t grab0, grab1; };
+struct QParams { float dt, rdt, fr, g_dt, lo, hi, grab; int32_t grab0, grab1; const DevParams* all; };   // all: the colliders
 __device__ __forceinline__ QParams load_qparams(const DevParams& P, uint32_t c) {
     QParams o;
     o.dt = P.dt;
@@ -158,15 +159,24 @@ __device__ __forceinline__ QParams load_qparams(const DevParams& P, uint32_t c) 
     o.hi = c == 0u ? P.hi[0] : c == 1u ? P.hi[1] : P.hi[2];
     o.grab = c == 0u ? P.grab[0] : c == 1u ? P.grab[1] : P.grab[2];
     o.grab0 = P.grab_local; o.grab1 = P.grab_local2;
+    o.all = &P;
     return o;
 }
 struct QVertex { float p, vel, pred; };
 __device__ __forceinline__ QVertex pjq_vertex_update(float acc, float wsum, float prev, const QParams& P, uint32_t vid, uint32_t c) {
     float p = acc * __builtin_amdgcn_rcpf(wsum);   // 0 * inf = NaN for a particle without tets, as in the reference
     // P6, SoftbodyGPU.js:340-355
-    if (static_cast<int32_t>(vid) == P.grab0 || static_cast<int32_t>(vid) == P.grab1) p = P.grab;
+    const bool grabbed = static_cast<int32_t>(vid) == P.grab0 || static_cast<int32_t>(vid) == P.grab1;
+    if (grabbed) p = P.grab;
     p = fminf(fmaxf(p, P.lo), P.hi);
     if (dpp<kLane1>(p) < 0.0f) p = c == 1u ? 0.0f : fmaf(prev - p, P.fr, p);   // below the floor: y = 0, x and z rubbed back
+    if (P.all->n_colliders != 0u) {   // kinematic colliders (collide.h): every lane of the quad gathers the particle's x, y, z, evaluates
+                                      // the contacts alike (same inputs, same instructions: same bits) and keeps its own component
+        float x = dpp<kLane0>(p), y = dpp<kLane1>(p), z = dpp<kLane2>(p);
+        const float qx = dpp<kLane0>(prev), qy = dpp<kLane1>(prev), qz = dpp<kLane2>(prev);
+        if (!grabbed) collide_f32<true>(x, y, z, qx, qy, qz, *P.all);
+        p = c == 0u ? x : c == 1u ? y : c == 2u ? z : p;
+    }
     // P7, :364-372, then P1 + P2 of the next substep
     QVertex o;
     o.p = p;
@@ -391,7 +401,7 @@ __device__ __forceinline__ void pjq_body(const PJBlk& d, const DevParams& P, con
 template <bool kLocal>
 __global__ __launch_bounds__(kQThreads, 4) void pjq_frame_kernel(PJBlk d, uint32_t n, const int32_t* block_tile, float4* pbuf0, float4* pbuf1, uint32_t* err,
                                                               uint32_t timeout_ms, DevParams pv, DevParams* pdev) {
-    if (blockIdx.x == 0u && threadIdx.x == 0u) *pdev = pv;
+    if (blockIdx.x == 0u && threadIdx.x == 0u) store_params(pdev, pv);
     const int32_t bt = block_tile[blockIdx.x];
     if (bt < 0) return;   // (a block that only pads the grid so that the others land on the intended XCDs)
     pjq_body<kModeFrame, kLocal>(d, pv, n, static_cast<uint32_t>(bt), pbuf0, pbuf1, err, timeout_ms);

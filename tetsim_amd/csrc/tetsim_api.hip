@@ -94,6 +94,8 @@ void fill_params(const tetsim_body* h, double dt, const TetSimParams& p, DevPara
     o->d_friction = p.friction;
     o->d_dev_compliance = p.devCompliance;
     o->d_vol_compliance = p.volCompliance;
+    o->n_colliders = h->n_colliders;
+    for (uint32_t k = 0; k < h->n_colliders; k++) { o->col[k] = h->col[k]; o->d_col[k] = h->d_col[k]; }
 }
 
 // A fresh block of 65,536 sequence numbers for the partial sums of a persistent frame kernel (h->frame_epoch + the substep's index

@@ -261,6 +261,62 @@ int tetsim_set_grab(tetsim_handle h, int32_t id, const float xyz[3]) {
     if (xyz) std::memcpy(h->grab_pos, xyz, 3 * sizeof(float));
     return 0;
 }
+
+// Kinematic colliders: checked and normalised in f64 as a whole, then they replace the list (a rejected call leaves the old one).
+int tetsim_set_colliders(tetsim_handle h, const TetSimCollider* colliders, uint32_t count) {
+    if (!h) return TETSIM_EINVAL;
+    if (count > TETSIM_MAX_COLLIDERS) return fail(h, TETSIM_EINVAL, "more than TETSIM_MAX_COLLIDERS colliders");
+    if (count && !colliders) return fail(h, TETSIM_EINVAL, "colliders is null");
+    DevColliderD d[kMaxColliders] = {};
+    DevColliderF f[kMaxColliders] = {};
+    for (uint32_t k = 0; k < count; k++) {
+        const TetSimCollider& c = colliders[k];
+        const std::string at = "collider " + std::to_string(k) + ": ";
+        if (c.kind < TETSIM_COLLIDER_SPHERE || c.kind > TETSIM_COLLIDER_PLANE) return fail(h, TETSIM_EINVAL, at + "unknown kind");
+        if (c.reserved != 0) return fail(h, TETSIM_EINVAL, at + "reserved must be 0");
+        const bool box = c.kind == TETSIM_COLLIDER_BOX, plane = c.kind == TETSIM_COLLIDER_PLANE, round = !box && !plane;
+        bool finite = std::isfinite(c.radius) && std::isfinite(c.friction);   // every value, used by the kind or not
+        for (int j = 0; j < 3; j++) finite = finite && std::isfinite(c.a[j]) && std::isfinite(c.b[j]) && std::isfinite(c.velocity[j]);
+        for (int j = 0; j < 9; j++) finite = finite && std::isfinite(c.axes[j]);
+        if (!finite) return fail(h, TETSIM_EINVAL, at + "non-finite value");
+        if (c.friction < 0.0 || (round && c.radius < 0.0)) return fail(h, TETSIM_EINVAL, at + "negative radius or friction");
+        DevColliderD& o = d[k];
+        o.kind = c.kind;
+        o.radius = round ? c.radius : 0.0;
+        o.friction = c.friction;
+        for (int j = 0; j < 3; j++) { o.a[j] = c.a[j]; o.b[j] = c.b[j]; o.v[j] = c.velocity[j]; }
+        auto unit = [](const double* v, double* out) {   // v / sqrt(v . v); false for a zero vector
+            const double l2 = (v[0] * v[0] + v[1] * v[1]) + v[2] * v[2];
+            if (!(l2 > 0.0)) return false;
+            const double l = std::sqrt(l2);
+            for (int j = 0; j < 3; j++) out[j] = v[j] / l;
+            return true;
+        };
+        if (plane && !unit(c.b, o.b)) return fail(h, TETSIM_EINVAL, at + "zero-length plane normal");
+        if (box) {
+            for (int j = 0; j < 3; j++) {
+                if (c.b[j] < 0.0) return fail(h, TETSIM_EINVAL, at + "negative half-extent");
+                if (!unit(c.axes + 3 * j, o.u + 3 * j)) return fail(h, TETSIM_EINVAL, at + "zero-length box axis");
+            }
+            for (int i = 0; i < 3; i++)
+                for (int j = i + 1; j < 3; j++) {
+                    const double* ui = o.u + 3 * i;
+                    const double* uj = o.u + 3 * j;
+                    if (std::fabs((ui[0] * uj[0] + ui[1] * uj[1]) + ui[2] * uj[2]) > 1e-5) return fail(h, TETSIM_EINVAL, at + "box axes are not orthogonal");
+                }
+        }
+        DevColliderF& g = f[k];   // the f32 view: every value rounded once
+        g.kind = o.kind;
+        g.radius = static_cast<float>(o.radius);
+        g.friction = static_cast<float>(o.friction);
+        for (int j = 0; j < 3; j++) { g.a[j] = static_cast<float>(o.a[j]); g.b[j] = static_cast<float>(o.b[j]); g.v[j] = static_cast<float>(o.v[j]); }
+        for (int j = 0; j < 9; j++) g.u[j] = static_cast<float>(o.u[j]);
+    }
+    h->n_colliders = count;
+    for (uint32_t k = 0; k < kMaxColliders; k++) { h->col[k] = f[k]; h->d_col[k] = d[k]; }
+    return 0;
+}
+
 namespace {
 // argmin of Softbody.js:279-291 over this handle's OWNED particles, on the device: one (d2, index) candidate per 256
 // particles comes back.  *local receives the API-local index (first minimum), *best its squared distance (f64).

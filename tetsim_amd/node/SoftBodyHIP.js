@@ -276,6 +276,31 @@ class SoftBodyHIP {
         this._api.setGrab(this._h, -1, 0, 0, 0);
     }
 
+    // kinematic colliders (tetsim.h tetsim_set_colliders): at most 8 of
+    //   {kind: "sphere", a: {x,y,z}, radius, friction, velocity}        {kind: "capsule", a, b, radius, friction, velocity}
+    //   {kind: "box", a: centre, b: half-extents, axes: [u, v, w], friction, velocity}    {kind: "plane", a: a point, b: normal, friction, velocity}
+    // ({x,y,z} objects or [x, y, z] arrays; absent fields 0, box axes the world's).  [] clears.  The list holds from the next
+    // simulate / simulateSubsteps call on; move a collider by calling this again between frames, with its `velocity`.
+    setColliders(list) {
+        const kinds = { sphere: 0, capsule: 1, box: 2, plane: 3 };
+        const k = new Int32Array(2 * list.length), v = new Float64Array(20 * list.length);
+        const put = (o, at, p) => {
+            if (p === undefined) return;
+            v[o + at] = Array.isArray(p) ? p[0] : p.x; v[o + at + 1] = Array.isArray(p) ? p[1] : p.y; v[o + at + 2] = Array.isArray(p) ? p[2] : p.z;
+        };
+        list.forEach((c, i) => {
+            const o = 20 * i;
+            k[2 * i] = typeof c.kind === "string" ? (c.kind in kinds ? kinds[c.kind] : -1) : c.kind;
+            k[2 * i + 1] = c.reserved || 0;
+            put(o, 0, c.a); put(o, 3, c.b);
+            const axes = c.axes || [{ x: 1, y: 0, z: 0 }, { x: 0, y: 1, z: 0 }, { x: 0, y: 0, z: 1 }];
+            put(o, 6, axes[0]); put(o, 9, axes[1]); put(o, 12, axes[2]);
+            v[o + 15] = c.radius || 0; v[o + 16] = c.friction || 0;
+            put(o, 17, c.velocity);
+        });
+        this._api.setColliders(this._h, k, v);
+    }
+
     // per-tet rotation quaternions (textureQuat, SoftbodyGPU.js:55; consumed by the normal path :440) -- a zero-copy view of the
     // handle's pinned host buffer, [4 * localElems] in the body's local tet order, refreshed by every call
     readQuats() {

@@ -54,6 +54,7 @@ struct Api {
     decltype(&tetsim_visual_vertex_normals_from) visual_vertex_normals_from = nullptr;
     decltype(&tetsim_set_grab) set_grab = nullptr;
     decltype(&tetsim_start_grab) start_grab = nullptr;
+    decltype(&tetsim_set_colliders) set_colliders = nullptr;   // (an additive ABI-5 symbol: looked up, not required)
     decltype(&tetsim_abi_version) abi_version = nullptr;
     decltype(&tetsim_comm_unique_id) comm_unique_id = nullptr;
     decltype(&tetsim_comm_init) comm_init = nullptr;
@@ -92,6 +93,7 @@ bool load_lib(const std::string& hint) {
     SYM(prep_partition, "tetsim_prep_partition") SYM(prep_partition_quality, "tetsim_prep_partition_quality")
     SYM(visual_vertex_normals_from, "tetsim_visual_vertex_normals_from") SYM(halo_refresh_final, "tetsim_halo_refresh_final") SYM(group_refresh_final, "tetsim_group_refresh_final") SYM(group_step_n, "tetsim_group_step_n")
 #undef SYM
+    g.set_colliders = reinterpret_cast<decltype(g.set_colliders)>(dlsym(g.lib, "tetsim_set_colliders"));
     return true;
 }
 
@@ -651,6 +653,32 @@ napi_value SetGrab(napi_env env, napi_callback_info info) {
     const float p[3] = {static_cast<float>(x), static_cast<float>(y), static_cast<float>(z)};
     return check(env, g.set_grab(h, id, p), h);
 }
+// setColliders(handle, Int32Array [kind, reserved] per collider, Float64Array [a3 b3 axes9 radius friction velocity3] per collider):
+// the TetSimCollider fields in declaration order (SoftBodyHIP.js packs them from its {x, y, z} objects)
+napi_value SetColliders(napi_env env, napi_callback_info info) {
+    napi_value a[3];
+    if (!get_args(env, info, 3, a)) return nullptr;
+    tetsim_handle h = handle_of(env, a[0]);
+    if (!h) return nullptr;
+    if (!g.set_colliders) return throw_err(env, "libtetsim_hip lacks tetsim_set_colliders");
+    int32_t* kinds = nullptr;
+    double* vals = nullptr;
+    size_t nk = 0, nv = 0;
+    if (!typed_array(env, a[1], napi_int32_array, &kinds, &nk) || nk % 2) return throw_err(env, "kinds must be an Int32Array of [kind, reserved] pairs");
+    if (!typed_array(env, a[2], napi_float64_array, &vals, &nv) || nv != nk / 2 * 20) return throw_err(env, "values must be a Float64Array of 20 numbers per collider");
+    const size_t n = nk / 2;
+    std::vector<TetSimCollider> c(n);
+    for (size_t i = 0; i < n; i++) {
+        const double* v = vals + 20 * i;
+        c[i].kind = kinds[2 * i];
+        c[i].reserved = kinds[2 * i + 1];
+        for (int j = 0; j < 3; j++) { c[i].a[j] = v[j]; c[i].b[j] = v[3 + j]; c[i].velocity[j] = v[17 + j]; }
+        for (int j = 0; j < 9; j++) c[i].axes[j] = v[6 + j];
+        c[i].radius = v[15];
+        c[i].friction = v[16];
+    }
+    return check(env, g.set_colliders(h, n ? c.data() : nullptr, static_cast<uint32_t>(n)), h);
+}
 // startGrab(handle, x, y, z) -> particle id
 napi_value StartGrab(napi_env env, napi_callback_info info) {
     napi_value a[4];
@@ -799,6 +827,8 @@ napi_value Init(napi_env env, napi_value exports) {
         {"readVisualVertexNormals", nullptr, ReadVisualVertexNormals, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
         {"visualVertexNormalsFrom", nullptr, VisualVertexNormalsFrom, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
         {"setGrab", nullptr, SetGrab, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
+        // (not enumerable: an additive entry point of ABI 5, looked up by name like its C symbol; the enumerable exports stay the ABI-5 set)
+        {"setColliders", nullptr, SetColliders, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"startGrab", nullptr, StartGrab, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
         {"info", nullptr, Info, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
     };

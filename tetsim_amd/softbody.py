@@ -31,6 +31,37 @@ def _ip(a):
     return a.ctypes.data_as(C.POINTER(C.c_int32))
 
 
+_COLLIDER_KINDS = {"sphere": capi.COLLIDER_SPHERE, "capsule": capi.COLLIDER_CAPSULE, "box": capi.COLLIDER_BOX, "plane": capi.COLLIDER_PLANE}
+
+
+def _vec(v, n=3):
+    """[x, y, z] or {x, y, z} (a list of n/3 of either for n > 3) -> n floats."""
+    if isinstance(v, dict):
+        return [float(v["x"]), float(v["y"]), float(v["z"])]
+    a = np.asarray(v, dtype=np.float64).reshape(-1) if not isinstance(v[0], dict) else np.asarray([_vec(r) for r in v], dtype=np.float64).reshape(-1)
+    if a.size != n:
+        raise ValueError("expected %d numbers, got %d" % (n, a.size))
+    return [float(x) for x in a]
+
+
+def make_colliders(colliders):
+    """list of dicts -> (TetSimCollider * n).  Each dict: kind ("sphere" / "capsule" / "box" / "plane") and the fields of
+    include/tetsim.h TetSimCollider that the kind uses -- a, b, axes (3 rows), radius, friction, velocity; absent ones are 0
+    (axes: the world axes)."""
+    arr = (capi.TetSimCollider * max(1, len(colliders)))()
+    for c, d in zip(arr, colliders):
+        kind = d["kind"]
+        c.kind = _COLLIDER_KINDS[kind] if isinstance(kind, str) else int(kind)
+        c.reserved = int(d.get("reserved", 0))
+        c.a[:] = _vec(d.get("a", (0.0, 0.0, 0.0)))
+        c.b[:] = _vec(d.get("b", (0.0, 0.0, 0.0)))
+        c.axes[:] = _vec(d.get("axes", ((1.0, 0.0, 0.0), (0.0, 1.0, 0.0), (0.0, 0.0, 1.0))), 9)
+        c.radius = float(d.get("radius", 0.0))
+        c.friction = float(d.get("friction", 0.0))
+        c.velocity[:] = _vec(d.get("velocity", (0.0, 0.0, 0.0)))
+    return arr
+
+
 def make_params(physicsParams):
     """physicsParams object (main.js:22-36) -> TetSimParams."""
     p = capi.TetSimParams()
@@ -376,6 +407,14 @@ class SoftBodyHIP:
     def endGrab(self):
         capi.check(self._L.tetsim_set_grab(self._h, -1, None), self._h)
         self.grabId = -1
+
+    # -- kinematic colliders (include/tetsim.h tetsim_set_colliders) ---------------------------------
+    def setColliders(self, colliders):
+        """Replace the body's obstacles: a list of at most 8 dicts (make_colliders); [] clears.  They take effect at the next step
+        call and stay fixed for its substeps; move one by calling this again between frames (and give it `velocity` so friction
+        acts on the motion relative to it).  Raises TetSimError(EINVAL) for an invalid list, which leaves the previous one."""
+        arr = make_colliders(list(colliders))
+        capi.check(self._L.tetsim_set_colliders(self._h, arr, len(colliders)), self._h)
 
     # -- measurement ----------------------------------------------------------------------------------
     def profile(self, n, dt, physicsParams=None):
