@@ -144,6 +144,24 @@ struct NHDev {
     uint32_t* corner_slots = nullptr;  // [nt] TETSIM_ORDER_CLUSTERED: the corners' cluster-local vertex slots, a byte each
     const DevParams* params = nullptr;
 };
+// ---- grids of the one-launch calls (pjb_call_kernel, nh_call_kernel): n substeps x the workgroups of one substep ----------------
+// A dispatch holds at most 2^32 - 1 WORK-ITEMS (the AQL packet's grid size is a 32-bit count of work-items), not workgroups.
+constexpr uint32_t max_grid_blocks(uint32_t threads) { return 0xffffffffu / threads; }
+// pjb_call_kernel: the tiles rounded up to whole rows of 8 (one per XCD), then the owned particles' workgroups, the sum rounded up to 8
+// again (block r of every substep lands on the XCD of block r of the first).  The launch and tetsim_step_n's chunking both use this.
+constexpr uint32_t pjb_call_blocks_per_sub(uint32_t nb, uint32_t nv_owned, uint32_t threads) {
+    return (((nb + 7u) & ~7u) + (nv_owned + threads - 1u) / threads + 7u) & ~7u;
+}
+// nh_call_kernel: the clusters' blocks of all colours, rounded up to 8
+constexpr uint32_t nh_call_blocks_per_sub(uint32_t blocks) { return (blocks + 7u) & ~7u; }
+// the most substeps one such launch may hold: its grid within the dispatch limit, and at most `cap` (the stamps' own bound)
+constexpr uint32_t call_chunk(uint32_t per_sub, uint32_t threads, uint32_t cap) {
+    const uint32_t fit = per_sub ? max_grid_blocks(threads) / per_sub : cap;
+    return fit < 1u ? 1u : fit < cap ? fit : cap;
+}
+static_assert(call_chunk(pjb_call_blocks_per_sub(2282u, 103823u, 256u), 256u, 8192u) == 6223u, "46-cell lattice: 2,696 blocks per substep");
+static_assert(call_chunk(nh_call_blocks_per_sub(2601u), 256u, 65000u / 8u) == 6432u, "55-cell lattice, clustered: 2,608 blocks per substep");
+
 // One launch of the clustered Gauss-Seidel schedule (host_prep.h ClusterPlan): lane = cluster, step j = tets first[j] + lane
 // for lanes < count[j] (count non-increasing), slot_vid = [kNHClusterVerts][clusters] vertex ids (-1 = unused).
 constexpr uint32_t kNHClusterVerts = 8, kNHClusterTets = 8;

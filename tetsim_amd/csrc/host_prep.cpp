@@ -447,6 +447,9 @@ void build_blocks(const float* verts, const int32_t* tets, uint32_t nt, uint32_t
     B.blk_tet_off.push_back(0);
     B.blk_vert_off.push_back(0);
     std::vector<std::vector<uint32_t>> vert_partials(nv_sum);
+    // tile slots of a particle with no live entry (the incidence table dropped every contribution the tile has for it): the tile stages
+    // the particle and stores a zero sum for it
+    std::vector<std::vector<uint32_t>> vert_staged(nv_sum);
     for (const Run& r : runs) {
         const uint32_t t0 = r.begin, i = r.end;
         if (!r.ghost && r.cls == 0) B.num_interior_blocks++;
@@ -483,6 +486,7 @@ void build_blocks(const float* verts, const int32_t* tets, uint32_t nt, uint32_t
             const int32_t v = touched[u];
             B.blk_verts.push_back(v);
             if (static_cast<uint32_t>(v) < nv_sum && cnt[u + 1] > cnt[u]) vert_partials[v].push_back(v0 + u);
+            else if (static_cast<uint32_t>(v) < nv_sum) vert_staged[v].push_back(v0 + u);
             slot_of[v] = -1;
         }
         B.blk_tet_off.push_back(i);
@@ -498,9 +502,17 @@ void build_blocks(const float* verts, const int32_t* tets, uint32_t nt, uint32_t
     B.vp_idx.reserve(B.vp_off[nv_sum]);
     for (uint32_t v = 0; v < nv_sum; v++) B.vp_idx.insert(B.vp_idx.end(), vert_partials[v].begin(), vert_partials[v].end());
     B.nv_pad = (nv_sum + 63u) & ~63u;
-    B.vp_ell.assign(static_cast<size_t>(std::max(B.max_partials, 1u)) * B.nv_pad, 0xffffffffu);
-    for (uint32_t v = 0; v < nv_sum; v++)
-        for (size_t j = 0; j < vert_partials[v].size(); j++) B.vp_ell[j * B.nv_pad + v] = vert_partials[v][j];
+    // The particle passes' lists (vp_ell) name those zero sums too, behind the live ones: the one-launch call's particle lane overwrites
+    // its prediction once every sum on its list carries the substep's stamp -- and a tile that stages the particle without summing for it
+    // must have staged it by then (pjb_call_kernel).  Adding +0 leaves every sum as it was.
+    B.vp_cols = 0;
+    for (uint32_t v = 0; v < nv_sum; v++) B.vp_cols = std::max<uint32_t>(B.vp_cols, static_cast<uint32_t>(vert_partials[v].size() + vert_staged[v].size()));
+    B.vp_ell.assign(static_cast<size_t>(std::max(B.vp_cols, 1u)) * B.nv_pad, 0xffffffffu);
+    for (uint32_t v = 0; v < nv_sum; v++) {
+        const size_t live = vert_partials[v].size();
+        for (size_t j = 0; j < live; j++) B.vp_ell[j * B.nv_pad + v] = vert_partials[v][j];
+        for (size_t j = 0; j < vert_staged[v].size(); j++) B.vp_ell[(live + j) * B.nv_pad + v] = vert_staged[v][j];
+    }
     // fused particle pass: every tile slot carries its particle's list of partial sums; the list's first slot is the owner
     const uint32_t ns = static_cast<uint32_t>(B.blk_verts.size());
     B.ns_pad = (ns + 63u) & ~63u;

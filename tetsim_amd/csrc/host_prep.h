@@ -125,7 +125,9 @@ struct BlockPlan {
     std::vector<uint16_t> lc_ent;        // [4*nt] per tile: corner*256 + tetLocal (word offset into the goal planes) grouped by LDS slot, tet order inside
     std::vector<uint32_t> vp_off;        // [nv_sum+1] per summed vertex: range into vp_idx
     std::vector<uint32_t> vp_idx;        // indices into the partial-sum array, ascending tile
-    std::vector<uint32_t> vp_ell;        // the same lists as ELL [max_partials][nv_pad], 0xffffffff = none
+    std::vector<uint32_t> vp_ell;        // the same lists as ELL [vp_cols][nv_pad], 0xffffffff = none, followed by the particle's ZERO sums: tile
+                                         //   slots that stage it without a live entry for it (every such contribution dropped by the incidence table)
+    uint32_t vp_cols = 0;                // >= max_partials
     // fused particle pass (pj_blocked.hip): per tile slot, the partial sums of ITS particle (= the particle's vp list) as ELL
     // [max_partials][ns_pad], 0xffffffff = none; per tile, the longest such list among its slots
     std::vector<uint32_t> slot_src;

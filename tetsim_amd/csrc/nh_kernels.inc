@@ -1057,7 +1057,7 @@ __global__ __launch_bounds__(256) void nh_call_kernel(const NHSweepColour* __res
 #if TETSIM_FAST
 void nh_launch_call_fast(hipStream_t s, const NHDev& d, const NHSweep& w, uint32_t n) {
     if (w.blocks == 0 || n == 0) return;
-    const uint32_t per_sub = (w.blocks + 7u) & ~7u;
+    const uint32_t per_sub = nh_call_blocks_per_sub(w.blocks);
     hipLaunchKernelGGL(nh_call_kernel, dim3(per_sub * n), dim3(256), 0, s, w.colours, w.ncolours, w.exchange, n, per_sub, w.blocks, w.error, w.timeout_ms, d);
 }
 void nh_launch_sweep1_fast(hipStream_t s, const NHDev& d, const NHSweep& w, bool fold, uint32_t sub_index, uint32_t epoch) {

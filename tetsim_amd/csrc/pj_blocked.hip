@@ -744,7 +744,8 @@ __global__ __launch_bounds__(64) void pjb_vertex_kernel(PJBlk d, uint32_t first,
 // All looks are memory-side loads (the writer may sit on another XCD, no kernel boundary in between) and bounded.  Nothing is double
 // buffered: a tile's partial sums are read by the particle lanes of its own particles only, and the tile overwrites them after it has
 // staged those particles' next predictions, which their lanes wrote after reading the sums; a prediction is overwritten by its lane after
-// all tiles around the particle delivered their sums, i.e. after they staged it.  No launch boundary inside a call, and the particle
+// all tiles around the particle delivered their sums, i.e. after they staged it (every tile that stages it is on its list, also one whose
+// contributions to it the slot table dropped: a zero sum, host_prep.cpp).  No launch boundary inside a call, and the particle
 // pass -- two dependent memory trips and little else -- and the tiles' staging run under the neighbouring passes' compute.  The
 // arithmetic is pjb_tet_body's and pjb_vertex_update's, operation for operation: a call equals the same substeps through the two
 // kernels (tetsim_step, tetsim_profile) bit for bit.
@@ -947,7 +948,7 @@ void pjb_launch_tet(hipStream_t s, const PJBlk& d, uint32_t tile_first, uint32_t
 }
 void pjb_launch_call(hipStream_t s, const PJBlk& d, uint32_t n, uint32_t* err, uint32_t timeout_ms, const DevParams& params, DevParams* params_dev) {
     if (d.nb == 0 || n == 0) return;
-    const uint32_t per_xcd = (d.nb + 7u) / 8u, tet_blocks = per_xcd * 8u, per_sub = (tet_blocks + (d.nv_owned + kTile - 1u) / kTile + 7u) & ~7u;
+    const uint32_t per_xcd = (d.nb + 7u) / 8u, tet_blocks = per_xcd * 8u, per_sub = pjb_call_blocks_per_sub(d.nb, d.nv_owned, kTile);
     const int mode = blk_mode(d);
     auto* kernel = mode == kModeConstantRest ? pjb_call_kernel<kModeConstantRest> : mode == kModeLeanState ? pjb_call_kernel<kModeLeanState> : pjb_call_kernel<kModeCarried>;
     hipLaunchKernelGGL(kernel, dim3(per_sub * n), dim3(kTile), 0, s, d, n, d.nb, per_xcd, tet_blocks, per_sub, err, timeout_ms, params, params_dev TETSIM_DBG_LAUNCH);

@@ -100,8 +100,11 @@ void fill_params(const tetsim_body* h, double dt, const TetSimParams& p, DevPara
 
 // A fresh block of 65,536 sequence numbers for the partial sums of a persistent frame kernel (h->frame_epoch + the substep's index
 // inside the launch; tetsim_step_n chunks longer calls): stale sums of an earlier launch never match.  Before the 32-bit counter wraps
-// -- 65,535 blocks, minutes at interactive rates -- the numbers left in both buffers are wiped (in stream order, behind every kernel
-// that reads them) and the count restarts: a sum of 65,536 launches ago can never pass for a fresh one.
+// -- 65,535 blocks, minutes at interactive rates -- the numbers left in the partial-sum buffers and the Neo-Hookean exchange array are
+// wiped (in stream order, behind every kernel that reads them) and the count restarts: a sum of 65,536 launches ago can never pass for
+// a fresh one.  The one-launch call (pjb_call_kernel) also stamps the predictions and end-of-substep positions it leaves behind; the
+// count restarts at every body's creation, so those stamps must not travel in a checkpoint -- tetsim_save_state and tetsim_load_state
+// clear them (tetsim_state.hip: clear_stamps).
 int next_epoch_block(tetsim_body* h) {
     if (h->frame_epoch >= 0xfffe0000u) {
         if (h->partial_b && h->partial_slots) {
@@ -151,7 +154,7 @@ int push_params(tetsim_body* h, double dt, const TetSimParams* params, bool reus
 
 // The parameters of a call whose ONE launch takes them by value (pjb_call_kernel: its first workgroup leaves them in DevParams for the
 // kernels behind it): the same checks, a fresh block of sequence numbers, the host's record of what the device holds once the launch has
-// run -- and no copy, no event, no pinned slot.
+// run -- and no copy, no event, no pinned slot.  (A launch that is not enqueued takes that record back: launched_with_params.)
 int stage_params(tetsim_body* h, double dt, const TetSimParams* params) {
     if (!params) return fail(h, TETSIM_EINVAL, "params is null");
     if (!(dt > 0.0) || !std::isfinite(dt)) return fail(h, TETSIM_EINVAL, "dt must be a positive finite number");
@@ -306,21 +309,27 @@ int launch_in_turn(tetsim_body* h, F&& launch) {
     t.last = h;
     return 0;
 }
+// The outcome of a launch that took the call's parameters by value (stage_params): if it was not enqueued, DevParams does not hold
+// them, and the next call must not take the "same parameters, no upload" path (push_params: reuse_ok).
+int launched_with_params(tetsim_body* h) {
+    const hipError_t le = hipGetLastError();
+    if (le == hipSuccess) return 0;
+    h->params_known = false;
+    return fail(h, TETSIM_EHIP, std::string("kernel launch: ") + hipGetErrorString(le));
+}
 // the persistent frame kernel of a small polar body for n substeps; epoch 0 = the block DevParams::epoch names (graph capture)
 int launch_frame_kernel(tetsim_body* h, uint32_t n, uint32_t epoch) {
     PJBlk k = h->blk;
     k.epoch = epoch;
     if (h->quad) pjq_launch_frame(h->stream, k, n, h->d_block_tile, h->frame_blocks, h->frame_local, h->blk.partial, h->partial_b, h->d_frame_err, halo_timeout_ms(h), h->params_on_device, h->d_params);
     else pjb_launch_frame(h->stream, k, n, h->d_block_tile, h->frame_blocks, h->frame_local, h->blk.partial, h->partial_b, h->d_frame_err, halo_timeout_ms(h), h->params_on_device, h->d_params);
-    const hipError_t le = hipGetLastError();
-    return le == hipSuccess ? 0 : fail(h, TETSIM_EHIP, std::string("kernel launch: ") + hipGetErrorString(le));
+    return launched_with_params(h);
 }
 // the single-workgroup frame kernel of a small Neo-Hookean body for n substeps, the call's parameters among its arguments
 int launch_nh_frame_kernel(tetsim_body* h, uint32_t n) {
     h->fast ? nh_launch_frame_fast(h->stream, h->nh, h->nh_frame_launch, n, h->params_on_device, h->d_params)
             : nh_launch_frame_precise(h->stream, h->nh, h->nh_frame_launch, n, h->params_on_device, h->d_params);
-    const hipError_t le = hipGetLastError();
-    return le == hipSuccess ? 0 : fail(h, TETSIM_EHIP, std::string("kernel launch: ") + hipGetErrorString(le));
+    return launched_with_params(h);
 }
 
 // one substep's launches (parameters already on the device)
@@ -716,16 +725,16 @@ int tetsim_step_n(tetsim_handle h, uint32_t n, double dt, const TetSimParams* pa
         if (int rc = tetsim_step_n(h, 32768u, dt, params)) return rc;
         n -= 32768u;
     }
-    if (h->pj_one_launch) {   // (the one-launch call of large polar bodies: n x (tiles + particle workgroups) in one grid, stamps inside one block)
-        const uint64_t per_sub = (static_cast<uint64_t>(h->blk.nb) + 7u) / 8u * 8u + (h->blk.nv_owned + kBlockTile - 1u) / kBlockTile + 8u;
-        const uint32_t most = static_cast<uint32_t>(std::max<uint64_t>(1u, std::min<uint64_t>(8192u, 0x7fffffffull / per_sub)));
+    if (h->pj_one_launch) {   // (the one-launch call of large polar bodies: n x (tiles + particle workgroups) in one grid of at most 2^32 - 1 work-items, stamps inside one block)
+        const uint32_t most = call_chunk(pjb_call_blocks_per_sub(h->blk.nb, h->blk.nv_owned, kBlockTile), kBlockTile, 8192u);
         while (n > most) {
             if (int rc = tetsim_step_n(h, most, dt, params)) return rc;
             n -= most;
         }
     }
-    if (h->nh_one_launch) {            // (the one-launch sweep stamps substep x colour inside one block too)
-        const uint32_t most = 65000u / h->nh_sweep1.ncolours;
+    if (h->nh_one_launch) {            // (the one-launch sweep stamps substep x colour inside one block too; the call kernel's grid is n x its blocks)
+        const uint32_t stamps = 65000u / h->nh_sweep1.ncolours;
+        const uint32_t most = h->nh_call ? call_chunk(nh_call_blocks_per_sub(h->nh_sweep1.blocks), 256u, stamps) : stamps;
         while (n > most) {
             if (int rc = tetsim_step_n(h, most, dt, params)) return rc;
             n -= most;
@@ -740,8 +749,7 @@ int tetsim_step_n(tetsim_handle h, uint32_t n, double dt, const TetSimParams* pa
             nh_launch_predict_value_fast(h->stream, h->nh, h->params_on_device, h->d_params);
             nh_launch_call_fast(h->stream, h->nh, h->nh_sweep1, n);
             nh_launch_post_fast(h->stream, h->nh);
-            const hipError_t le = hipGetLastError();
-            return le == hipSuccess ? 0 : fail(h, TETSIM_EHIP, std::string("kernel launch: ") + hipGetErrorString(le));
+            return launched_with_params(h);
         });
     }
     if (h->nh_frame) {   // small Neo-Hookean bodies: the whole call is ONE single-workgroup launch with every particle in LDS (nh_kernels.inc: nh_frame_kernel)
@@ -757,8 +765,7 @@ int tetsim_step_n(tetsim_handle h, uint32_t n, double dt, const TetSimParams* pa
         return launch_in_turn(h, [&]() -> int {
             if (h->frame) return launch_frame_kernel(h, n, 0u);
             pjb_launch_call(h->stream, h->blk, n, h->d_substep_err, halo_timeout_ms(h), h->params_on_device, h->d_params);
-            const hipError_t le = hipGetLastError();
-            return le == hipSuccess ? 0 : fail(h, TETSIM_EHIP, std::string("kernel launch: ") + hipGetErrorString(le));
+            return launched_with_params(h);
         });
     }
     int rc = push_params(h, dt, params);

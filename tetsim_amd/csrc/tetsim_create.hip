@@ -411,7 +411,7 @@ int create_polar(tetsim_body* h, const float* verts, uint32_t nv, const int32_t*
         if ((rc = upload(h, vpe, B.vp_ell))) return rc;
         HIPCHK(h, hipMemset(k.partial, 0, std::max<size_t>(nslots, 1) * sizeof(float4)));
         k.blk_tet_off = bto; k.blk_vert_off = bvo; k.blk_verts = bv; k.tet_lidx = lidx; k.vol = vol;
-        k.lc_range = lcr; k.lc_ent = lce; k.vp_ell = vpe; k.vp_cols = B.max_partials; k.nv_pad = B.nv_pad;
+        k.lc_range = lcr; k.lc_ent = lce; k.vp_ell = vpe; k.vp_cols = B.vp_cols; k.nv_pad = B.nv_pad;
         d.quat = k.quat;  // tetsim_read_quats
 #ifdef TETSIM_ABLATION
         if (lab_env("TETSIM_DEBUG_ITER_HIST")) {  // development: rotation-iteration statistics of every tet-kernel launch (pjb_log_iterations)

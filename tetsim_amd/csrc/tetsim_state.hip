@@ -215,6 +215,16 @@ int await_peer_deliveries(tetsim_body* h) {
         std::this_thread::sleep_for(std::chrono::microseconds(50));
     }
 }
+// The one-launch call (pj_blocked.hip: pjb_call_kernel) leaves its last substep's sequence number in the fourth float of every prediction
+// and end-of-substep position, and its waves of substep s look for s's number there.  Numbers restart with every body (tetsim_api.hip:
+// next_epoch_block), so a restored stamp could pass for a fresh one in another body: a checkpoint holds 0 there, as every other path
+// stores -- and no call looks for 0.  Cleared in the blob a save writes AND in what a load uploads (blobs of older builds carry stamps).
+bool is_stamped_section(const tetsim_body* h, const void* ptr) {
+    return h->opt.solver == TETSIM_SOLVER_POLAR_JACOBI && (ptr == h->pj.pos_pred || ptr == h->pj.pos_final);
+}
+void clear_stamps(char* section, size_t bytes) {
+    for (size_t off = 0; off + sizeof(float4) <= bytes; off += sizeof(float4)) std::memset(section + off + 3 * sizeof(float), 0, sizeof(float));
+}
 int ghosts_from_tail(tetsim_body* h) {
     const size_t ng = h->pj.nv_local - h->pj.nv_owned;
     if (h->partitioned && h->ghost_alt && ng)
@@ -245,6 +255,7 @@ int tetsim_save_state(tetsim_handle h, void* blob, uint64_t bytes) {
     for (const StateSection& sec : secs) {
         if (sec.bytes) HIPCHK(h, hipMemcpy(out, sec.ptr, sec.bytes, hipMemcpyDeviceToHost));
         if (sec.ptr == h->pj.pos_pred && h->opt.solver == TETSIM_SOLVER_POLAR_JACOBI) { if (int rc = patch_blob_ghosts(h, out)) return rc; }
+        if (is_stamped_section(h, sec.ptr)) clear_stamps(out, sec.bytes);
         out += sec.bytes;
     }
     return 0;
@@ -267,8 +278,15 @@ int tetsim_load_state(tetsim_handle h, const void* blob, uint64_t bytes) {
     const char* src = static_cast<const char*>(blob) + sizeof(in);
     std::vector<StateSection> secs;
     state_sections(h, secs);
+    std::vector<char> scrubbed;
     for (const StateSection& sec : secs) {
-        if (sec.bytes) HIPCHK(h, hipMemcpy(sec.ptr, src, sec.bytes, hipMemcpyHostToDevice));
+        const char* from = src;
+        if (sec.bytes && is_stamped_section(h, sec.ptr)) {
+            scrubbed.assign(src, src + sec.bytes);
+            clear_stamps(scrubbed.data(), sec.bytes);
+            from = scrubbed.data();
+        }
+        if (sec.bytes) HIPCHK(h, hipMemcpy(sec.ptr, from, sec.bytes, hipMemcpyHostToDevice));
         src += sec.bytes;
     }
     if (int rc = ghosts_from_tail(h)) return rc;
