@@ -105,6 +105,32 @@ def test_prep_rest_bit_exact_vs_reference(mesh):
     assert np.array_equal(irv.view(np.uint32), load_f32(mesh + "_invRestVolume.f32").view(np.uint32))
 
 
+# The 3-cell lattice at this density gives its eight inner particles the inverse mass 0x3F800009 = 1 + 65,536 x 0x3F80 + 8: the stamp the
+# clustered FAST Neo-Hookean call kernel (8 colours) waits for in prev.w at substep 2 of the call whose block is 0x3F80 -- the 16,256th
+# tetsim_step_n call of the body (next_epoch_block: frame_epoch = 1 + 65,536 x calls; stamps of substep s are frame_epoch + 8 s + colour,
+# and substep 2's first touchers look for frame_epoch + 8 in prev.w).  tests/test_gpu_nh_one_launch_irregular.py runs through it.
+STAMP_DENSITY = 26.99997
+STAMP_BITS = 0x3F800009
+
+
+def test_stamp_density_gives_the_colliding_inverse_mass():
+    L = capi.lib()
+    v, t = make_lattice(3, y0=0.3)
+    vv, tt = np.ascontiguousarray(v.ravel()), np.ascontiguousarray(t.ravel().astype(np.int32))
+    nv, nt = len(v), len(t)
+    im, irp, irv = np.empty(nv, np.float32), np.empty(9 * nt, np.float32), np.empty(nt, np.float32)
+    assert L.tetsim_prep_rest(fp(vv), nv, ip(tt), nt, STAMP_DENSITY, fp(im), fp(irp), fp(irv)) == 0
+    hit = np.flatnonzero(im.view(np.uint32) == STAMP_BITS)
+    inner = [i + 4 * (j + 4 * k) for k in (1, 2) for j in (1, 2) for i in (1, 2)]
+    assert hit.tolist() == inner
+    out = [np.full(nt, -1, np.int32) for _ in range(4)]
+    nl, nc = C.c_uint32(), C.c_uint32()
+    assert L.tetsim_prep_clusters(ip(tt), nt, nv, *[ip(a) for a in out], C.byref(nl), C.byref(nc)) == 0
+    assert nl.value == 8 and nc.value == 27 and np.unique(t).size == nv          # the call kernel's body: 2..127 colours, no free particle
+    calls = 16256
+    assert 1 + 65536 * calls + 8 == STAMP_BITS
+
+
 def _py_levels(t, nv):
     last = np.full(nv, -1, dtype=np.int64)
     out = np.empty(len(t), dtype=np.int32)

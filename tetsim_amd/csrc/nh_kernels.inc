@@ -245,6 +245,11 @@ __global__ __launch_bounds__(256) void TETSIM_SFX(nh_predict_value_kernel_)(NHDe
     if (v >= d.nv) return;
     float4 vel = d.vel[v], pos = d.pos[v], prev;
     predict_vertex(load_vparams(pv), vel, pos, prev);
+    // nh_call_kernel polls prev.w for its own fold's stamp of one substep before, and may look before that store has landed: it then
+    // finds this value.  `prev = pos` carries the inverse mass, any non-negative float -- one whose bits equal the awaited stamp was
+    // taken for the fold's store (a velocity from the wrong previous position).  0 is no stamp (tetsim_api.hip: next_epoch_block);
+    // nothing reads prev.w as a mass.
+    prev.w = 0.0f;
     d.vel[v] = vel;
     d.prev[v] = prev;
     d.pos[v] = pos;
@@ -985,7 +990,7 @@ __global__ __launch_bounds__(256) void nh_call_kernel(const NHSweepColour* __res
     if (pend_a && __float_as_uint(xa.w) == want_a) { ga = xa; pend_a = false; }
     if (pend_b && __float_as_uint(xb.w) == want_b) { gb = xb; pend_b = false; }
     // (the previous position of a folded particle: this lane's own store of one substep ago, stamped with that substep's base; the
-    // prediction kernel's at the launch's second substep)
+    // prediction kernel's at the launch's second substep; until the awaited store lands the lane holds 0 or an older substep's base, never it)
     bool ppend_a = fold_a && sub > 1u && __float_as_uint(pa.w) != sub_base - ncol, ppend_b = fold_b && sub > 1u && __float_as_uint(pb.w) != sub_base - ncol;
     if (__builtin_amdgcn_ballot_w64(pend_a || pend_b || ppend_a || ppend_b) != 0ull) {
         const long long t0 = wall_clock64(), limit = 100000ll * timeout_ms;   // 100 MHz ticks; 0 = unbounded

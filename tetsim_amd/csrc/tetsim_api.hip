@@ -98,13 +98,21 @@ void fill_params(const tetsim_body* h, double dt, const TetSimParams& p, DevPara
     for (uint32_t k = 0; k < h->n_colliders; k++) { o->col[k] = h->col[k]; o->d_col[k] = h->d_col[k]; }
 }
 
-// A fresh block of 65,536 sequence numbers for the partial sums of a persistent frame kernel (h->frame_epoch + the substep's index
-// inside the launch; tetsim_step_n chunks longer calls): stale sums of an earlier launch never match.  Before the 32-bit counter wraps
-// -- 65,535 blocks, minutes at interactive rates -- the numbers left in the partial-sum buffers and the Neo-Hookean exchange array are
-// wiped (in stream order, behind every kernel that reads them) and the count restarts: a sum of 65,536 launches ago can never pass for
-// a fresh one.  The one-launch call (pjb_call_kernel) also stamps the predictions and end-of-substep positions it leaves behind; the
-// count restarts at every body's creation, so those stamps must not travel in a checkpoint -- tetsim_save_state and tetsim_load_state
-// clear them (tetsim_state.hip: clear_stamps).
+// A fresh block of 65,536 sequence numbers (stamps) for the launches of one call: h->frame_epoch = 1 + 65,536 k, and a launch numbers its
+// substeps (and colours) inside the block -- tetsim_step_n chunks longer calls -- so stamps of an earlier block never match.  Before the
+// 32-bit counter wraps (65,535 blocks, minutes at interactive rates) the stamps left in the polar partial-sum buffers and the Neo-Hookean
+// exchange array are wiped (in stream order, behind every kernel that reads them) and the count restarts: a stamp of 65,536 blocks ago
+// can never pass for a fresh one.  The largest stamp is below 0xfffe0001 + 65,536: no stamp is 0.
+// THE INVARIANT of every poll: a lane that a kernel polls for a stamp holds a stamp of this body or 0 -- nothing else.  What else stands
+// there, lane by lane:
+//   * polar partial sums (.w; pjb_frame_body, pjb_call_kernel): 0 from every other kernel and from the wipe;
+//   * polar pos_pred.w and pos_final.w (pjb_call_kernel): 0 from every other kernel, from creation and from a loaded checkpoint;
+//   * the Neo-Hookean exchange array (.w; nh_sweep1_kernel, nh_call_kernel): 0 from creation and from the wipe -- only those kernels store there;
+//   * Neo-Hookean prev.w (nh_call_kernel, from its third substep): 0 from the call's prediction (nh_predict_value_kernel), the base of an
+//     earlier substep of the same call from the lane's own fold.  The other particle kernels copy the inverse mass there (`prev = pos`),
+//     which can have any stamp's bits: none of them runs between the call's prediction and its sweep.
+// Stamps restart at every body's creation, so none may travel in a checkpoint: tetsim_save_state and tetsim_load_state write 0 in
+// pos_pred.w, pos_final.w and Neo-Hookean prev.w (tetsim_state.hip: clear_stamps).
 int next_epoch_block(tetsim_body* h) {
     if (h->frame_epoch >= 0xfffe0000u) {
         if (h->partial_b && h->partial_slots) {

@@ -216,11 +216,14 @@ int await_peer_deliveries(tetsim_body* h) {
     }
 }
 // The one-launch call (pj_blocked.hip: pjb_call_kernel) leaves its last substep's sequence number in the fourth float of every prediction
-// and end-of-substep position, and its waves of substep s look for s's number there.  Numbers restart with every body (tetsim_api.hip:
-// next_epoch_block), so a restored stamp could pass for a fresh one in another body: a checkpoint holds 0 there, as every other path
-// stores -- and no call looks for 0.  Cleared in the blob a save writes AND in what a load uploads (blobs of older builds carry stamps).
+// and end-of-substep position, and its waves of substep s look for s's number there; the Neo-Hookean call (nh_kernels.inc: nh_call_kernel)
+// leaves one in prev.w, where the other Neo-Hookean paths leave the inverse mass.  Numbers restart with every body (tetsim_api.hip:
+// next_epoch_block), so a restored stamp could pass for a fresh one in another body: a checkpoint holds 0 there -- no call looks for 0,
+// and the blob does not depend on the path that ran.  Cleared in the blob a save writes AND in what a load uploads (blobs of older
+// builds carry stamps).
 bool is_stamped_section(const tetsim_body* h, const void* ptr) {
-    return h->opt.solver == TETSIM_SOLVER_POLAR_JACOBI && (ptr == h->pj.pos_pred || ptr == h->pj.pos_final);
+    if (h->opt.solver == TETSIM_SOLVER_POLAR_JACOBI) return ptr == h->pj.pos_pred || ptr == h->pj.pos_final;
+    return ptr == h->nh.prev;
 }
 void clear_stamps(char* section, size_t bytes) {
     for (size_t off = 0; off + sizeof(float4) <= bytes; off += sizeof(float4)) std::memset(section + off + 3 * sizeof(float), 0, sizeof(float));
