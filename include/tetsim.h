@@ -371,6 +371,55 @@ int tetsim_start_grab(tetsim_handle h, const float xyz[3], int32_t *id_out);
  * tetsim_set_grab(id, xyz) on every partition -- only the owner pins it. */
 int tetsim_nearest_particle(tetsim_handle h, const float xyz[3], int32_t *global_id, double *dist2);
 
+/* --- picking: ray casts and the bounding sphere of the visual mesh ----------------------------- */
+
+/* Grabber.start / GPUGrabber.start (Softbody.js:440-456, SoftbodyGPU.js:788-811) cast the pointer's ray against visMesh with
+ * three.js's Raycaster -- the reference's GPU path reads the mesh back for it (:789-795) -- and every endFrame ends with
+ * geometry.computeBoundingSphere() (Softbody.js:256,276; SoftbodyGPU.js:689).  Both run here on the device, on the positions the
+ * skinning kernel produces.  An ADDITIVE extension of ABI version 5 (TETSIM_ABI_VERSION is unchanged; no existing struct changed).
+ *
+ * tetsim_raycast_visual: for every ray the FIRST entry of what three.js r160
+ *     new Raycaster(origin, direction, near, far).intersectObject(visMesh)
+ * returns for a THREE.Mesh with an identity world matrix, a front-side material and an indexed BufferGeometry whose `position`
+ * holds what tetsim_read_visual_mesh returns and whose index is the list given to tetsim_set_visual_triangles -- bit for bit:
+ * hit (0/1), distance, point, triangle (three's faceIndex: the triangle's position in the caller's list) and body (the body of a
+ * batch whose tets carry the triangle's first vertex; 0 for a single body).  A miss: hit 0, body -1, triangle -1, zeros.
+ * The definition (three's Mesh.raycast, checkGeometryIntersection, Ray.intersectTriangle, restated; tests/raycast_ref.py is the
+ * same in numpy, pinned to three's own answers): f64 arithmetic on the f32 positions, every operation rounded separately, sums
+ * left to right, dot(u, v) = u.x*v.x + u.y*v.y + u.z*v.z.
+ *   1. The bounding-sphere cull, with (centre, radius) of tetsim_read_visual_bounding_sphere and the direction as given:
+ *      o2 = origin + direction*near; unless |o2 - centre|^2 <= radius^2:  v = centre - o2, tca = v.direction,
+ *      d2 = v.v - tca*tca; a miss if d2 > radius^2; thc = sqrt(radius^2 - d2), t0 = tca - thc, t1 = tca + thc; a miss if t1 < 0;
+ *      at = o2 + direction*(t0 < 0 ? t1 : t0); a miss if |o2 - at|^2 > (far - near)^2.
+ *   2. The ray in the mesh's local space: the origin as given; the direction goes through Vector3.transformDirection, which
+ *      NORMALISES it: dir = direction * (1 / (sqrt(direction.direction) || 1)).  (A unit vector computed in f64 may change in its
+ *      last bits; distances are lengths in world units whatever the given direction's length.)
+ *   3. Per triangle (a, b, c): e1 = b - a, e2 = c - a, n = e1 x e2, DdN = dir.n; DdN > 0 is a back face and is culled, DdN == 0
+ *      misses; sign = -1, DdN = -DdN; diff = origin - a; DdQxE2 = sign * dir.(diff x e2) >= 0; DdE1xQ = sign * dir.(e1 x diff) >= 0;
+ *      DdQxE2 + DdE1xQ <= DdN; QdN = -sign * diff.n >= 0; point = origin + dir*(QdN / DdN); distance = |origin - point| (the
+ *      square root of the sum of squares); kept iff near <= distance <= far.
+ *   4. The winner is the smallest distance, the LOWEST triangle index among equal distances (three sorts with a stable sort).
+ * TETSIM_EINVAL: a null pointer with count > 0; a non-finite origin or direction; a zero direction; near < 0; far < near; a NaN
+ * in near or far (far may be +infinity).  TETSIM_ESTATE: no visual mesh or no triangles attached; a partitioned body (a
+ * triangle's corners may be skinned by different ranks, as for tetsim_read_visual_vertex_normals).  count == 0 succeeds; any
+ * count works (the launches are chunked by the grid limits).  The call skins first, like tetsim_read_visual_mesh, so the answer
+ * belongs to the last completed substep; it synchronises once and changes no solver state.
+ * Out of scope: partitioned bodies; all hits along a ray; back-side or double-side materials; the edge wireframe's LineSegments;
+ * an acceleration structure (brute force: every ray against every triangle); closest-point queries. */
+typedef struct TetSimRay    { double origin[3], direction[3], near, far; } TetSimRay;       /* far may be +inf */
+typedef struct TetSimRayHit { int32_t hit, body, triangle, reserved; double distance, point[3]; } TetSimRayHit;
+int tetsim_raycast_visual(tetsim_handle h, const TetSimRay *rays, uint32_t count, TetSimRayHit *hits);
+/* Grabber.start in one call: cast `ray`; on a hit the point origin + direction*distance (f64, Softbody.js:449-450) rounded to f32
+ * goes through exactly what tetsim_start_grab does (*id_out = the grabbed particle); on a miss the grab stays as it was,
+ * *id_out = -1 and the call returns TETSIM_OK.  hit_out and id_out may be NULL.  Unpartitioned bodies only.  The grabbed point uses
+ * the direction AS GIVEN times the world-length distance, as Grabber.start does: for a direction that is not a unit vector it is not
+ * hit_out->point (setFromCamera hands over a unit vector). */
+int tetsim_start_grab_ray(tetsim_handle h, const TetSimRay *ray, TetSimRayHit *hit_out, int32_t *id_out);
+/* three.js r160 BufferGeometry.computeBoundingSphere() of the positions tetsim_read_visual_mesh returns, bit for bit: centre =
+ * (min + max) * 0.5 of the component-wise f64 min / max, radius = sqrt(max_i |centre - p_i|^2), the difference taken as
+ * centre - p.  TETSIM_ESTATE: no visual mesh, or a partitioned body. */
+int tetsim_read_visual_bounding_sphere(tetsim_handle h, double centre[3], double *radius);
+
 /* --- kinematic colliders ------------------------------------------------------------------------ */
 
 /* Obstacles the body cannot enter: spheres, capsules, oriented boxes and half-spaces, moved by the host between calls.  An
@@ -548,6 +597,17 @@ int tetsim_prep_slot_table(const int32_t *tets, uint32_t nt, uint32_t nv, int32_
 /* The particle(s) SoftbodyGPU.js:335-338,345 pins for `grab_id` on a mesh with num_elems tets (texture side
  * ceil(sqrt(num_elems))): out[0..1], -1 = none.  What TETSIM_FLAG_REF_GRAB_TEXEL uses. */
 int tetsim_prep_ref_grab_texels(int32_t grab_id, uint32_t num_elems, uint32_t num_particles, int32_t out[2]);
+/* A visual mesh for a body WITHOUT an artist's mesh (Softbody.js:46-50 take one from the caller): the tet mesh's boundary faces
+ * -- faces of exactly one tet -- oriented outward (counter-clockwise seen from outside: the normal points away from the tet's
+ * opposite corner in the rest configuration `verts`; verts == NULL, or a zero-volume tet: the tet is taken as positively
+ * oriented, det[v1-v0, v2-v0, v3-v0] > 0, the convention of initPhysics, Softbody.js:69-72), in the reference's own format: one row
+ * (tetNr, b0, b1, b2) per boundary VERTEX with one barycentric weight equal to 1 (its skinned position is the particle's position),
+ * and triangles over those rows.  Rows ascend by particle id (tetNr = the lowest tet containing it), triangles by (tet, face;
+ * face k lies opposite corner k).  *nrows / *ntri receive the counts; vis_verts / tri_ids may both be NULL to query them.  Host only. */
+int tetsim_prep_boundary_surface(const float *verts /* [3*nv] rest positions, or NULL */,
+                                 const int32_t *tets, uint32_t nt, uint32_t nv,
+                                 float *vis_verts /*[4*nrows]*/, int32_t *tri_ids /*[3*ntri]*/,
+                                 uint32_t *nrows, uint32_t *ntri);
 /* Rest data of Softbody.js:60-87 in JS number semantics: invMass[nv], invRestPose[9*nt] (column-major),
  * invRestVolume[nt]. */
 int tetsim_prep_rest(const float *verts, uint32_t nv, const int32_t *tets, uint32_t nt, double density,

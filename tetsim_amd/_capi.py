@@ -95,6 +95,15 @@ class TetSimCollider(C.Structure):
                 ("radius", C.c_double), ("friction", C.c_double), ("velocity", C.c_double * 3)]
 
 
+class TetSimRay(C.Structure):
+    _fields_ = [("origin", C.c_double * 3), ("direction", C.c_double * 3), ("near", C.c_double), ("far", C.c_double)]
+
+
+class TetSimRayHit(C.Structure):
+    _fields_ = [("hit", C.c_int32), ("body", C.c_int32), ("triangle", C.c_int32), ("reserved", C.c_int32), ("distance", C.c_double),
+                ("point", C.c_double * 3)]
+
+
 # every symbol include/tetsim.h declares (tests check the library exports exactly these)
 SYMBOLS = [
     "tetsim_abi_version", "tetsim_default_options", "tetsim_default_params", "tetsim_create", "tetsim_create_batch", "tetsim_get_batch_layout", "tetsim_destroy",
@@ -111,11 +120,12 @@ SYMBOLS = [
     "tetsim_prep_tiles", "tetsim_prep_slot_table", "tetsim_prep_ref_grab_texels", "tetsim_prep_rest", "tetsim_prep_partition", "tetsim_prep_partition_quality", "tetsim_plan_create", "tetsim_plan_destroy", "tetsim_plan_sizes",
     "tetsim_plan_arrays", "tetsim_plan_neighbour", "tetsim_plan_neighbour_ids",
     "tetsim_plan_create_deep", "tetsim_plan_layers", "tetsim_plan_neighbour_layer2", "tetsim_plan_neighbour_layer2_ids",
+    "tetsim_raycast_visual", "tetsim_start_grab_ray", "tetsim_read_visual_bounding_sphere", "tetsim_prep_boundary_surface",
     "tetsim_mesh_write", "tetsim_mesh_open", "tetsim_mesh_arrays", "tetsim_mesh_close", "tetsim_create_from_file",
 ]
 
 # additive to ABI 5 (looked up by name: a library built before them lacks them and still loads; calling one then raises)
-OPTIONAL_SYMBOLS = ("tetsim_set_colliders",)
+OPTIONAL_SYMBOLS = ("tetsim_set_colliders", "tetsim_raycast_visual", "tetsim_start_grab_ray", "tetsim_read_visual_bounding_sphere", "tetsim_prep_boundary_surface")
 
 _lib = None
 
@@ -182,6 +192,11 @@ def lib():
     if hasattr(L, "tetsim_set_colliders"):   # (additive to ABI 5: a library built before it lacks the symbol and still loads)
         L.tetsim_set_colliders.argtypes = [H, C.POINTER(TetSimCollider), u32]
     L.tetsim_start_grab.argtypes = [H, fp, ip]
+    if hasattr(L, "tetsim_raycast_visual"):   # (additive to ABI 5, like the colliders)
+        L.tetsim_raycast_visual.argtypes = [H, C.c_void_p, u32, C.c_void_p]
+        L.tetsim_start_grab_ray.argtypes = [H, C.POINTER(TetSimRay), C.POINTER(TetSimRayHit), ip]
+        L.tetsim_read_visual_bounding_sphere.argtypes = [H, dp, dp]
+        L.tetsim_prep_boundary_surface.argtypes = [fp, ip, u32, u32, fp, ip, C.POINTER(u32), C.POINTER(u32)]
     L.tetsim_profile.argtypes = [H, u32, dbl, PP, C.POINTER(TetSimProfile)]
     L.tetsim_time_kernels.argtypes = [H, u32, dbl, PP, C.POINTER(TetSimProfile)]
     L.tetsim_time_step_n.argtypes = [H, u32, dbl, PP, dp]

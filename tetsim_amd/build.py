@@ -57,6 +57,8 @@ UNITS = {
     "nh_fast.hip": ["-ffp-contract=on", "-mllvm", "-amdgpu-kernarg-preload-count=9"],
     "util_kernels.hip": ["-ffp-contract=off"],
     "skin_kernels.hip": ["-ffp-contract=off"],
+    # three.js ray casts and bounding sphere in f64: bit-equality with JavaScript needs every multiply and add rounded on its own
+    "query_kernels.hip": ["-ffp-contract=off"],
     "build_info.cpp": ["-x", "hip"],
 }
 HEADERS = ["body.h", "dev_common.h", "dev_store.h", "host_prep.h", "mesh_file.h", "pj_kernels.inc", "pj_math.inc", "pj_lab.h", "pj_blocked_lab.inc", "nh_kernels.inc", "collide.h", os.path.join("..", "..", "include", "tetsim.h")]

@@ -269,6 +269,11 @@ struct tetsim_body {
     float* pinned_quat = nullptr;  // tetsim_read_quats_pinned: host-pinned xyzw per local tet
     uint32_t* d_api2dev = nullptr; // device copy of api2dev (pack / nearest kernels), null = identity
     double* d_best = nullptr; uint32_t* d_best_id = nullptr;  // tetsim_start_grab candidates
+    // tetsim_raycast_visual / tetsim_read_visual_bounding_sphere (query_kernels.hip): allocated by the first query, grown on demand
+    uint32_t* d_sphere = nullptr;
+    RayIn* d_rays = nullptr; RayPrep* d_ray_prep = nullptr; RayOut* d_ray_hits = nullptr; RayCand* d_ray_cand = nullptr;
+    size_t ray_cap = 0, ray_prep_cap = 0, ray_hits_cap = 0, ray_cand_cap = 0;   // elements in d_rays / d_ray_prep / d_ray_hits / d_ray_cand
+    std::vector<int32_t> vis_row_body, tri_body;   // batches: the body behind every visual row / behind every triangle's first vertex
 
     // NEOHOOKEAN_GS
     NHDev nh;
@@ -323,6 +328,21 @@ inline int dev_alloc(tetsim_body* h, Tp** p, size_t count) {
     h->info.device_bytes += bytes;
     *p = static_cast<Tp*>(raw);
     return 0;
+}
+// a buffer that grows on demand: the old one is released (and leaves device_bytes) before the larger one is allocated
+template <class Tp>
+inline int dev_grow(tetsim_body* h, Tp** p, size_t* cap, size_t need) {
+    if (*p && need <= *cap) return 0;
+    if (*p) {
+        h->allocs.erase(std::find(h->allocs.begin(), h->allocs.end(), static_cast<void*>(*p)));
+        (void)hipFree(*p);
+        h->info.device_bytes -= std::max<size_t>(*cap, 1) * sizeof(Tp);
+        *p = nullptr;
+    }
+    *cap = 0;
+    const int rc = dev_alloc(h, p, need);
+    if (rc == 0) *cap = need;
+    return rc;
 }
 template <class Tp>
 inline int upload(tetsim_body* h, Tp* dst, const std::vector<Tp>& src) {

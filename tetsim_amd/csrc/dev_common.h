@@ -367,6 +367,27 @@ void util_launch_set_params(hipStream_t s, DevParams* dst, const DevParams& v); 
 void util_launch_p2p_probe(hipStream_t s, const P2PProbe& p, uint32_t base, uint32_t reps, unsigned long long* ticks, uint32_t* error, uint32_t timeout_ms);   // loopback measurements: a stand-in for wire latency
 void util_launch_gather4(hipStream_t s, const float4* src, const int32_t* idx, float4* dst, uint32_t n);
 
+// ---- queries on the skinned visual mesh (query_kernels.hip): three.js r160 Raycaster / computeBoundingSphere on the device ----
+struct RayIn { double o[3], d[3], near, far; };                                               // = TetSimRay
+struct RayOut { int32_t hit, body, triangle, reserved; double distance, point[3]; };          // = TetSimRayHit
+struct RayPrep { double o[3], d[3], near, far; uint32_t culled, pad; };   // the ray in the mesh's local space (direction normalised as three does), after the sphere cull
+struct RayCand { double distance; uint32_t triangle, pad; };              // a block's best; triangle 0xffffffff = none
+constexpr uint32_t kRayNone = 0xffffffffu;
+constexpr uint32_t kSphereWords = 8;   // order-preserving keys: ~min xyz, max xyz (u32 each), then the largest squared distance to the centre (f64 bits, u64)
+struct QueryDev {
+    uint32_t nvis = 0, ntri = 0;
+    const float4* pos = nullptr;   // SkinDev::out_pos
+    const int4* tri = nullptr;     // SkinDev::tri
+    uint32_t* sphere = nullptr;    // [kSphereWords]
+};
+// the bounding sphere of q.pos into q.sphere (a memset and two reductions, in stream order)
+void query_launch_sphere(hipStream_t s, const QueryDev& q);
+// rays [count] -> hits [count] (body left 0 on a hit): q.sphere must be current; cand holds count * blocks_per_ray entries
+void query_launch_rays(hipStream_t s, const QueryDev& q, const RayIn* rays, RayPrep* prep, RayCand* cand, RayOut* hits, uint32_t count, uint32_t blocks_per_ray);
+uint32_t query_blocks_per_ray(uint32_t ntri, uint32_t count);
+// what q.sphere holds, decoded with the arithmetic of the kernels (host side of tetsim_read_visual_bounding_sphere)
+void query_decode_sphere(const uint32_t words[kSphereWords], double centre[3], double* radius);
+
 
 }  // namespace tetsim
 

@@ -107,6 +107,72 @@ int tetsim_prep_ref_grab_texels(int32_t grab_id, uint32_t num_elems, uint32_t nu
     ref_grab_texels(grab_id, num_elems, num_particles, out);
     return 0;
 }
+int tetsim_prep_boundary_surface(const float* verts, const int32_t* tets, uint32_t nt, uint32_t nv, float* vis_verts, int32_t* tri_ids,
+                                 uint32_t* nrows, uint32_t* ntri) {
+    if ((nt && !tets) || !nrows || !ntri || (!vis_verts != !tri_ids)) return fail(nullptr, TETSIM_EINVAL, "tetsim_prep_boundary_surface: null argument");
+    if (nt && nv == 0) return fail(nullptr, TETSIM_EINVAL, "tetsim_prep_boundary_surface: tets without particles (nv == 0)");
+    std::string e = validate_mesh(reinterpret_cast<const float*>(tets), nv ? nv : 1, tets, nt, false);
+    if (!e.empty()) return fail(nullptr, TETSIM_EINVAL, e);
+    if (nt > (1u << 24)) return fail(nullptr, TETSIM_EINVAL, "tetsim_prep_boundary_surface: a tet id above 2^24 does not fit the f32 row format");
+    // face k lies opposite corner k; for a positively oriented tet these windings look counter-clockwise from outside
+    static const int kFace[4][3] = {{1, 2, 3}, {0, 3, 2}, {0, 1, 3}, {0, 2, 1}};
+    struct Face { int32_t key[3]; uint32_t tet, face; };
+    std::vector<Face> faces(4ull * nt);
+    for (uint32_t t = 0; t < nt; t++)
+        for (uint32_t k = 0; k < 4; k++) {
+            Face& f = faces[4ull * t + k];
+            for (int j = 0; j < 3; j++) f.key[j] = tets[4 * t + kFace[k][j]];
+            std::sort(f.key, f.key + 3);
+            f.tet = t; f.face = k;
+        }
+    std::sort(faces.begin(), faces.end(), [](const Face& a, const Face& b) {
+        return std::lexicographical_compare(a.key, a.key + 3, b.key, b.key + 3) || (std::equal(a.key, a.key + 3, b.key) && (a.tet < b.tet || (a.tet == b.tet && a.face < b.face)));
+    });
+    std::vector<uint64_t> boundary;   // 4 * tet + face, ascending
+    for (size_t i = 0; i < faces.size();) {
+        size_t j = i + 1;
+        while (j < faces.size() && std::equal(faces[i].key, faces[i].key + 3, faces[j].key)) j++;
+        if (j - i == 1) boundary.push_back(4ull * faces[i].tet + faces[i].face);
+        i = j;
+    }
+    std::sort(boundary.begin(), boundary.end());
+    std::vector<int32_t> row(nv, -1);   // particle -> row
+    for (uint64_t b : boundary)
+        for (int j = 0; j < 3; j++) row[tets[4 * (b >> 2) + kFace[b & 3][j]]] = 0;
+    uint32_t rows = 0;
+    for (uint32_t v = 0; v < nv; v++)
+        if (row[v] == 0) row[v] = static_cast<int32_t>(rows++);
+    *nrows = rows;
+    *ntri = static_cast<uint32_t>(boundary.size());
+    if (!vis_verts) return 0;
+    std::vector<uint8_t> done(rows, 0);
+    for (uint32_t t = 0; t < nt; t++)   // ascending: the lowest tet containing the particle, its first corner there
+        for (int k = 0; k < 4; k++) {
+            const int32_t r = row[tets[4 * t + k]];
+            if (r < 0 || done[r]) continue;
+            done[r] = 1;
+            vis_verts[4 * r] = static_cast<float>(t);
+            for (int j = 0; j < 3; j++) vis_verts[4 * r + 1 + j] = j == k ? 1.0f : 0.0f;   // (corner 3: b3 = 1 - 0 - 0 - 0)
+        }
+    for (size_t i = 0; i < boundary.size(); i++) {
+        const uint32_t t = static_cast<uint32_t>(boundary[i] >> 2), k = static_cast<uint32_t>(boundary[i] & 3);
+        bool flip = false;
+        if (verts) {
+            const int32_t* c = tets + 4 * t;
+            double m[3][3];
+            for (int a = 0; a < 3; a++)
+                for (int x = 0; x < 3; x++) m[a][x] = static_cast<double>(verts[3 * c[a + 1] + x]) - static_cast<double>(verts[3 * c[0] + x]);
+            const double det = m[0][0] * (m[1][1] * m[2][2] - m[1][2] * m[2][1]) - m[0][1] * (m[1][0] * m[2][2] - m[1][2] * m[2][0]) +
+                               m[0][2] * (m[1][0] * m[2][1] - m[1][1] * m[2][0]);
+            flip = det < 0.0;
+        }
+        const int32_t a = row[tets[4 * t + kFace[k][0]]], b = row[tets[4 * t + kFace[k][1]]], c2 = row[tets[4 * t + kFace[k][2]]];
+        tri_ids[3 * i] = a;
+        tri_ids[3 * i + 1] = flip ? c2 : b;
+        tri_ids[3 * i + 2] = flip ? b : c2;
+    }
+    return 0;
+}
 int tetsim_prep_rest(const float* verts, uint32_t nv, const int32_t* tets, uint32_t nt, double density, float* inv_mass, float* inv_rest_pose, float* inv_rest_volume) {
     if (!inv_mass || (nt && (!inv_rest_pose || !inv_rest_volume))) return TETSIM_EINVAL;
     std::string e = validate_mesh(verts, nv, tets, nt, false);

@@ -32,7 +32,7 @@ int tetsim_set_visual_mesh(tetsim_handle h, const float* vis_verts, uint32_t nvi
     }
     std::vector<int4> corner;
     std::vector<float4> weight, n0;
-    std::vector<int32_t> qidx, kept;
+    std::vector<int32_t> qidx, kept, row_body;   // (row_body: batches -- moved into the handle only when the call has succeeded)
     for (uint32_t i = 0; i < nvis; i++) {
         const float tn = vis_verts[4 * i];
         if (!(tn >= 0.0f) || tn >= static_cast<float>(nt) || tn != std::floor(tn)) return fail(h, TETSIM_EINVAL, "visual vertex " + std::to_string(i) + " references a tet outside the mesh");
@@ -68,6 +68,8 @@ int tetsim_set_visual_mesh(tetsim_handle h, const float* vis_verts, uint32_t nvi
         qidx.push_back(pjs ? tet_pos[el] : 0);
         if (rest_normals) n0.push_back(make_float4(rest_normals[3 * i], rest_normals[3 * i + 1], rest_normals[3 * i + 2], 0.0f));
         kept.push_back(static_cast<int32_t>(i));
+        if (!h->batch_first_tet.empty())   // (ray casts name the body of a hit: the body whose tets carry the row)
+            row_body.push_back(static_cast<int32_t>(std::upper_bound(h->batch_first_tet.begin(), h->batch_first_tet.end(), e) - h->batch_first_tet.begin()) - 1);
     }
     const uint32_t nk = static_cast<uint32_t>(kept.size());
     SkinDev& k = h->skin;
@@ -88,6 +90,7 @@ int tetsim_set_visual_mesh(tetsim_handle h, const float* vis_verts, uint32_t nvi
     k.corner = dc; k.weight = dw; k.qidx = dq; k.normal0 = dn;
     k.nvis = nk;
     h->vis_global = kept;
+    h->vis_row_body = row_body;
     h->vis_total = nvis;
     h->vis_attached = true;
     h->info.num_vis_verts = nk;
@@ -173,6 +176,10 @@ int tetsim_set_visual_triangles(tetsim_handle h, const int32_t* tri_ids, uint32_
     if ((rc = upload(h, doff, off))) return rc;
     if ((rc = upload(h, dent, ent))) return rc;
     k.ntri = ntri; k.tri = dt; k.vt_tri = dent;
+    if (!h->vis_row_body.empty() && !part) {
+        h->tri_body.resize(ntri);
+        for (uint32_t t = 0; t < ntri; t++) h->tri_body[t] = h->vis_row_body[tri_ids[3 * t]];
+    }
     k.vt_off = doff;
     return 0;
 }
@@ -369,6 +376,105 @@ int tetsim_nearest_particle(tetsim_handle h, const float xyz[3], int32_t* global
     int rc = nearest_owned(h, xyz, &local, dist2);
     if (rc) return rc;
     *global_id = local < 0 ? -1 : (h->partitioned ? h->part.local_to_global_vert[local] : local);
+    return 0;
+}
+
+// ---- picking: three.js r160 ray casts and the bounding sphere of the skinned visual mesh (query_kernels.hip) ----------------------
+namespace {
+static_assert(sizeof(TetSimRay) == sizeof(RayIn) && sizeof(TetSimRayHit) == sizeof(RayOut), "the ABI's ray records are the kernels' records");
+const char* const kPartitionedQuery = "a partition skins only its own rows, and a triangle's corners may belong to other ranks: ray casts and the bounding sphere "
+                                      "of a partitioned body are not supported (put the ranks' skins together with tetsim_read_visual_mesh + tetsim_get_visual_ids)";
+
+// the visual positions of the last completed substep in skin.out_pos and their bounding sphere in d_sphere, on h->stream
+int skin_and_sphere(tetsim_body* h, QueryDev* q) {
+    HIPCHK(h, hipSetDevice(h->opt.device));
+    const bool pjs = h->opt.solver == TETSIM_SOLVER_POLAR_JACOBI;
+    if (pjs) { if (int rc = ensure_quats(h)) return rc; }
+    if (!h->d_sphere) { if (int rc = dev_alloc(h, &h->d_sphere, kSphereWords)) return rc; }
+    skin_launch(h->stream, h->skin, pjs ? h->pj.pos_final : h->nh.pos, pjs ? h->pj.quat : nullptr, !pjs);
+    q->nvis = h->skin.nvis; q->ntri = h->skin.ntri; q->pos = h->skin.out_pos; q->tri = h->skin.tri; q->sphere = h->d_sphere;
+    query_launch_sphere(h->stream, *q);
+    return 0;
+}
+
+int check_query_state(tetsim_body* h, bool need_triangles) {
+    if (!h->vis_attached) return fail(h, TETSIM_ESTATE, "no visual mesh attached (tetsim_set_visual_mesh)");
+    if (need_triangles && (!h->skin.vt_off || h->skin.ntri == 0)) return fail(h, TETSIM_ESTATE, "no visual triangles attached (tetsim_set_visual_triangles)");
+    if (h->partitioned) return fail(h, TETSIM_ESTATE, kPartitionedQuery);
+    if (h->skin.nvis == 0) return fail(h, TETSIM_ESTATE, "the visual mesh has no vertices");
+    return 0;
+}
+
+int check_rays(tetsim_body* h, const TetSimRay* rays, uint32_t count) {
+    for (uint32_t i = 0; i < count; i++) {
+        const TetSimRay& r = rays[i];
+        const std::string at = "ray " + std::to_string(i) + ": ";
+        bool finite = true;
+        for (int k = 0; k < 3; k++) finite = finite && std::isfinite(r.origin[k]) && std::isfinite(r.direction[k]);
+        if (!finite) return fail(h, TETSIM_EINVAL, at + "non-finite origin or direction");
+        if (r.direction[0] == 0.0 && r.direction[1] == 0.0 && r.direction[2] == 0.0) return fail(h, TETSIM_EINVAL, at + "zero direction");
+        if (r.near != r.near || r.far != r.far) return fail(h, TETSIM_EINVAL, at + "near or far is NaN");
+        if (r.near < 0.0) return fail(h, TETSIM_EINVAL, at + "near < 0");
+        if (r.far < r.near) return fail(h, TETSIM_EINVAL, at + "far < near");
+    }
+    return 0;
+}
+
+int cast_rays(tetsim_body* h, const TetSimRay* rays, uint32_t count, TetSimRayHit* hits) {
+    if (int rc = check_rays(h, rays, count)) return rc;
+    QueryDev q;
+    HIPCHK(h, hipSetDevice(h->opt.device));
+    const uint32_t per_ray = query_blocks_per_ray(h->skin.ntri, count);
+    int rc;
+    const size_t want = std::max<size_t>(count, 64);   // (one capacity per buffer: a failed allocation leaves the others' bookkeeping right)
+    if ((rc = dev_grow(h, &h->d_rays, &h->ray_cap, want)) || (rc = dev_grow(h, &h->d_ray_prep, &h->ray_prep_cap, want)) ||
+        (rc = dev_grow(h, &h->d_ray_hits, &h->ray_hits_cap, want))) return rc;
+    if ((rc = dev_grow(h, &h->d_ray_cand, &h->ray_cand_cap, static_cast<size_t>(count) * per_ray))) return rc;
+    HIPCHK(h, hipMemcpy(h->d_rays, rays, count * sizeof(RayIn), hipMemcpyHostToDevice));
+    if ((rc = skin_and_sphere(h, &q))) return rc;
+    query_launch_rays(h->stream, q, h->d_rays, h->d_ray_prep, h->d_ray_cand, h->d_ray_hits, count, per_ray);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(hits, h->d_ray_hits, count * sizeof(RayOut), hipMemcpyDeviceToHost));
+    if (!h->tri_body.empty())
+        for (uint32_t i = 0; i < count; i++)
+            if (hits[i].hit) hits[i].body = h->tri_body[hits[i].triangle];
+    return 0;
+}
+}  // namespace
+
+int tetsim_raycast_visual(tetsim_handle h, const TetSimRay* rays, uint32_t count, TetSimRayHit* hits) {
+    if (!h) return fail(h, TETSIM_EINVAL, "null argument");
+    if (count && (!rays || !hits)) return fail(h, TETSIM_EINVAL, "null argument");
+    if (int rc = check_query_state(h, true)) return rc;
+    if (count == 0) return 0;
+    return cast_rays(h, rays, count, hits);
+}
+
+int tetsim_start_grab_ray(tetsim_handle h, const TetSimRay* ray, TetSimRayHit* hit_out, int32_t* id_out) {
+    if (!h || !ray) return fail(h, TETSIM_EINVAL, "null argument");
+    if (int rc = check_query_state(h, true)) return rc;
+    TetSimRayHit hit;
+    if (int rc = cast_rays(h, ray, 1, &hit)) return rc;
+    if (hit_out) *hit_out = hit;
+    if (id_out) *id_out = -1;
+    if (!hit.hit) return 0;   // (the grab stays as it was)
+    // Grabber.start (Softbody.js:448-451): origin.clone().addScaledVector(direction, distance), handed to startGrab
+    float xyz[3];
+    for (int k = 0; k < 3; k++) xyz[k] = static_cast<float>(ray->origin[k] + ray->direction[k] * hit.distance);
+    return tetsim_start_grab(h, xyz, id_out);
+}
+
+int tetsim_read_visual_bounding_sphere(tetsim_handle h, double centre[3], double* radius) {
+    if (!h || !centre || !radius) return fail(h, TETSIM_EINVAL, "null argument");
+    if (int rc = check_query_state(h, false)) return rc;
+    QueryDev q;
+    if (int rc = skin_and_sphere(h, &q)) return rc;
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    uint32_t words[kSphereWords];
+    HIPCHK(h, hipMemcpy(words, h->d_sphere, sizeof(words), hipMemcpyDeviceToHost));
+    query_decode_sphere(words, centre, radius);
     return 0;
 }
 

@@ -69,6 +69,7 @@ class SoftBodyHIP {
 
         // display objects (Softbody.js:36-57 / SoftbodyGPU.js:415-461), only when three.js was injected
         const THREE = (world && world.THREE) || SoftBodyHIP.THREE || null;
+        this._THREE = THREE;
         this.edgeMesh = null;
         this.visMesh = null;
         this.visVerts = visVerts || new Float32Array(0);
@@ -202,7 +203,38 @@ class SoftBodyHIP {
             else this.visMesh.geometry.computeVertexNormals();
         }
         this.visMesh.geometry.attributes.position.needsUpdate = true;
-        this.visMesh.geometry.computeBoundingSphere();
+        // Softbody.js:276: computeBoundingSphere(), evaluated on the device from the same skinned positions (bit for bit three's);
+        // partitions and bodies whose skin stays on the host keep the geometry's own.  So does an injected library without a Sphere class:
+        // three.js always has one, so this only concerns stand-ins (a host's own scene classes, the counting stubs of test_softbody.js),
+        // which are left to compute -- or count -- their bounding spheres themselves.
+        if (this._visOnDevice && !this._visIds && !this._partitioned && this._api.readVisualBoundingSphere && this._THREE && typeof this._THREE.Sphere === 'function') {
+            const s = this._api.readVisualBoundingSphere(this._h), g = this.visMesh.geometry;
+            if (g.boundingSphere == null) g.boundingSphere = new this._THREE.Sphere();
+            g.boundingSphere.center.set(s[0], s[1], s[2]);
+            g.boundingSphere.radius = s[3];
+        } else this.visMesh.geometry.computeBoundingSphere();
+    }
+
+    // ---- picking (tetsim.h tetsim_raycast_visual): Grabber.start's ray cast (Softbody.js:440-451) without reading the mesh back ----
+    // raycaster: a THREE.Raycaster (its ray, near, far).  null, or three's first intersection {distance, point, faceIndex, object}
+    _point(x, y, z) { return this._THREE ? new this._THREE.Vector3(x, y, z) : { x, y, z }; }
+    raycast(raycaster) {
+        const r = raycaster.ray, far = raycaster.far === undefined ? Infinity : raycaster.far;
+        const res = this._api.raycastVisual(this._h, Float64Array.of(r.origin.x, r.origin.y, r.origin.z), Float64Array.of(r.direction.x, r.direction.y, r.direction.z),
+            raycaster.near || 0, far);
+        if (!res.ints[0]) return null;
+        return { distance: res.reals[0], point: this._point(res.reals[1], res.reals[2], res.reals[3]), faceIndex: res.ints[2], body: res.ints[1], object: this.visMesh };
+    }
+    // Grabber.start in one call: cast the raycaster's ray, grab the particle nearest to the hit; returns the intersection or null (a miss
+    // leaves the grab as it was)
+    startGrabRay(raycaster) {
+        const r = raycaster.ray, far = raycaster.far === undefined ? Infinity : raycaster.far;
+        const o = this._api.startGrabRay(this._h, Float64Array.of(r.origin.x, r.origin.y, r.origin.z, r.direction.x, r.direction.y, r.direction.z, raycaster.near || 0, far));
+        if (!o[1]) return null;
+        this.grabId = o[0];
+        const d = o[4];   // the grabbed point as Grabber.start computes it: origin + direction * distance, stored as f32
+        this.grabPos[0] = r.origin.x + r.direction.x * d; this.grabPos[1] = r.origin.y + r.direction.y * d; this.grabPos[2] = r.origin.z + r.direction.z * d;
+        return { distance: d, point: this._point(o[5], o[6], o[7]), faceIndex: o[3], body: o[2], object: this.visMesh };
     }
 
     readVisualVertexNormals(out) {                      // Float32Array [3*numVisVerts]: three.js computeVertexNormals on the GPU

@@ -65,6 +65,10 @@ struct Api {
     decltype(&tetsim_create_from_file) create_from_file = nullptr;
     decltype(&tetsim_prep_partition) prep_partition = nullptr;
     decltype(&tetsim_prep_partition_quality) prep_partition_quality = nullptr;
+    // additive to ABI 5 (looked up without failing: a library built before them lacks them)
+    decltype(&tetsim_raycast_visual) raycast_visual = nullptr;
+    decltype(&tetsim_start_grab_ray) start_grab_ray = nullptr;
+    decltype(&tetsim_read_visual_bounding_sphere) read_visual_bounding_sphere = nullptr;
     std::string err;
 } g;
 
@@ -94,6 +98,9 @@ bool load_lib(const std::string& hint) {
     SYM(visual_vertex_normals_from, "tetsim_visual_vertex_normals_from") SYM(halo_refresh_final, "tetsim_halo_refresh_final") SYM(group_refresh_final, "tetsim_group_refresh_final") SYM(group_step_n, "tetsim_group_step_n")
 #undef SYM
     g.set_colliders = reinterpret_cast<decltype(g.set_colliders)>(dlsym(g.lib, "tetsim_set_colliders"));
+    g.raycast_visual = reinterpret_cast<decltype(g.raycast_visual)>(dlsym(g.lib, "tetsim_raycast_visual"));
+    g.start_grab_ray = reinterpret_cast<decltype(g.start_grab_ray)>(dlsym(g.lib, "tetsim_start_grab_ray"));
+    g.read_visual_bounding_sphere = reinterpret_cast<decltype(g.read_visual_bounding_sphere)>(dlsym(g.lib, "tetsim_read_visual_bounding_sphere"));
     return true;
 }
 
@@ -679,6 +686,90 @@ napi_value SetColliders(napi_env env, napi_callback_info info) {
     }
     return check(env, g.set_colliders(h, n ? c.data() : nullptr, static_cast<uint32_t>(n)), h);
 }
+// raycastVisual(handle, Float64Array origins [3n], Float64Array directions [3n], near, far) -> {ints: Int32Array [4n] (hit, body,
+// triangle, reserved), reals: Float64Array [4n] (distance, point)}: tetsim_raycast_visual, three.js's first intersection per ray
+napi_value make_f64(napi_env env, size_t n, double** data) {
+    napi_value ab, out;
+    void* p = nullptr;
+    napi_create_arraybuffer(env, n * sizeof(double), &p, &ab);
+    napi_create_typedarray(env, napi_float64_array, n, ab, 0, &out);
+    *data = static_cast<double*>(p);
+    return out;
+}
+napi_value RaycastVisual(napi_env env, napi_callback_info info) {
+    napi_value a[5];
+    if (!get_args(env, info, 5, a)) return nullptr;
+    tetsim_handle h = handle_of(env, a[0]);
+    if (!h) return nullptr;
+    if (!g.raycast_visual) return throw_err(env, "libtetsim_hip lacks tetsim_raycast_visual");
+    double *o = nullptr, *d = nullptr, near = 0.0, far = 0.0;
+    size_t no = 0, nd = 0;
+    if (!typed_array(env, a[1], napi_float64_array, &o, &no) || no % 3) return throw_err(env, "origins must be a Float64Array of 3 numbers per ray");
+    if (!typed_array(env, a[2], napi_float64_array, &d, &nd) || nd != no) return throw_err(env, "directions must be a Float64Array as long as origins");
+    if (!num_arg(env, a[3], &near, "near") || !num_arg(env, a[4], &far, "far")) return nullptr;
+    const size_t n = no / 3;
+    if (n > 0xffffffffull) return throw_err(env, "too many rays");
+    std::vector<TetSimRay> rays(n);
+    std::vector<TetSimRayHit> hits(n);
+    for (size_t i = 0; i < n; i++) {
+        for (int k = 0; k < 3; k++) { rays[i].origin[k] = o[3 * i + k]; rays[i].direction[k] = d[3 * i + k]; }
+        rays[i].near = near; rays[i].far = far;
+    }
+    const int rc = g.raycast_visual(h, rays.data(), static_cast<uint32_t>(n), hits.data());
+    if (rc) return check(env, rc, h);
+    napi_value ab, ints, reals, out;
+    void* pi = nullptr;
+    double* pr = nullptr;
+    napi_create_arraybuffer(env, 4 * n * sizeof(int32_t), &pi, &ab);
+    napi_create_typedarray(env, napi_int32_array, 4 * n, ab, 0, &ints);
+    reals = make_f64(env, 4 * n, &pr);
+    for (size_t i = 0; i < n; i++) {
+        int32_t* q = static_cast<int32_t*>(pi) + 4 * i;
+        q[0] = hits[i].hit; q[1] = hits[i].body; q[2] = hits[i].triangle; q[3] = hits[i].reserved;
+        pr[4 * i] = hits[i].distance;
+        for (int k = 0; k < 3; k++) pr[4 * i + 1 + k] = hits[i].point[k];
+    }
+    napi_create_object(env, &out);
+    napi_set_named_property(env, out, "ints", ints);
+    napi_set_named_property(env, out, "reals", reals);
+    return out;
+}
+// startGrabRay(handle, Float64Array [origin3, direction3, near, far]) -> Float64Array [id, hit, body, triangle, distance, point3]
+napi_value StartGrabRay(napi_env env, napi_callback_info info) {
+    napi_value a[2];
+    if (!get_args(env, info, 2, a)) return nullptr;
+    tetsim_handle h = handle_of(env, a[0]);
+    if (!h) return nullptr;
+    if (!g.start_grab_ray) return throw_err(env, "libtetsim_hip lacks tetsim_start_grab_ray");
+    double* v = nullptr;
+    size_t n = 0;
+    if (!typed_array(env, a[1], napi_float64_array, &v, &n) || n != 8) return throw_err(env, "ray must be a Float64Array [origin, direction, near, far]");
+    TetSimRay ray;
+    for (int k = 0; k < 3; k++) { ray.origin[k] = v[k]; ray.direction[k] = v[3 + k]; }
+    ray.near = v[6]; ray.far = v[7];
+    TetSimRayHit hit;
+    int32_t id = -1;
+    const int rc = g.start_grab_ray(h, &ray, &hit, &id);
+    if (rc) return check(env, rc, h);
+    double* r = nullptr;
+    napi_value out = make_f64(env, 8, &r);
+    r[0] = id; r[1] = hit.hit; r[2] = hit.body; r[3] = hit.triangle; r[4] = hit.distance;
+    for (int k = 0; k < 3; k++) r[5 + k] = hit.point[k];
+    return out;
+}
+// readVisualBoundingSphere(handle) -> Float64Array [cx, cy, cz, radius]: three.js computeBoundingSphere() of the skinned visual mesh
+napi_value ReadVisualBoundingSphere(napi_env env, napi_callback_info info) {
+    napi_value a[1];
+    if (!get_args(env, info, 1, a)) return nullptr;
+    tetsim_handle h = handle_of(env, a[0]);
+    if (!h) return nullptr;
+    if (!g.read_visual_bounding_sphere) return throw_err(env, "libtetsim_hip lacks tetsim_read_visual_bounding_sphere");
+    double* r = nullptr;
+    napi_value out = make_f64(env, 4, &r);
+    const int rc = g.read_visual_bounding_sphere(h, r, r + 3);
+    if (rc) return check(env, rc, h);
+    return out;
+}
 // startGrab(handle, x, y, z) -> particle id
 napi_value StartGrab(napi_env env, napi_callback_info info) {
     napi_value a[4];
@@ -829,6 +920,9 @@ napi_value Init(napi_env env, napi_value exports) {
         {"setGrab", nullptr, SetGrab, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
         // (not enumerable: an additive entry point of ABI 5, looked up by name like its C symbol; the enumerable exports stay the ABI-5 set)
         {"setColliders", nullptr, SetColliders, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"raycastVisual", nullptr, RaycastVisual, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"startGrabRay", nullptr, StartGrabRay, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"readVisualBoundingSphere", nullptr, ReadVisualBoundingSphere, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"startGrab", nullptr, StartGrab, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
         {"info", nullptr, Info, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
     };

@@ -62,6 +62,35 @@ def make_colliders(colliders):
     return arr
 
 
+# tetsim_raycast_visual's records as numpy sees them (include/tetsim.h: TetSimRay, TetSimRayHit)
+RAY_DTYPE = np.dtype([("origin", "<f8", (3,)), ("direction", "<f8", (3,)), ("near", "<f8"), ("far", "<f8")])
+RAY_HIT_DTYPE = np.dtype([("hit", "<i4"), ("body", "<i4"), ("triangle", "<i4"), ("reserved", "<i4"), ("distance", "<f8"), ("point", "<f8", (3,))])
+
+
+def make_rays(origins, directions, near=0.0, far=np.inf):
+    """[n, 3] origins and directions (one of them may be a single vector), near / far scalars or [n] -> TetSimRay records."""
+    o, d = np.asarray(origins, dtype=np.float64).reshape(-1, 3), np.asarray(directions, dtype=np.float64).reshape(-1, 3)
+    n = max(len(o), len(d))
+    rays = np.empty(n, dtype=RAY_DTYPE)
+    rays["origin"], rays["direction"], rays["near"], rays["far"] = o, d, near, far
+    return rays
+
+
+def boundary_surface(tets, nv, verts=None):
+    """(visVerts [rows, 4], visTriIds [triangles, 3]) of the tet mesh's boundary, oriented outward, in the reference's visual-mesh
+    format -- for bodies without an artist's mesh (include/tetsim.h: tetsim_prep_boundary_surface).  Host only, no GPU needed.
+    verts: rest positions, to orient tets of either handedness; None takes every tet as positively oriented."""
+    L = capi.lib()
+    t = np.ascontiguousarray(np.asarray(tets).reshape(-1), dtype=np.int32)
+    v = None if verts is None else _f32(verts).reshape(-1)
+    nr, ntri = C.c_uint32(), C.c_uint32()
+    args = (_fp(v) if v is not None else None, _ip(t), t.size // 4, int(nv))
+    capi.check(L.tetsim_prep_boundary_surface(*args, None, None, C.byref(nr), C.byref(ntri)))
+    vis, tri = np.empty(4 * nr.value, dtype=np.float32), np.empty(3 * ntri.value, dtype=np.int32)
+    capi.check(L.tetsim_prep_boundary_surface(*args, _fp(vis), _ip(tri), C.byref(nr), C.byref(ntri)))
+    return vis.reshape(-1, 4), tri.reshape(-1, 3)
+
+
 def make_params(physicsParams):
     """physicsParams object (main.js:22-36) -> TetSimParams."""
     p = capi.TetSimParams()
@@ -385,6 +414,34 @@ class SoftBodyHIP:
         self.grabId = gid.value
         self.grabPos[:] = p
         return self.grabId
+
+    # -- picking (include/tetsim.h: tetsim_raycast_visual; Grabber.start, Softbody.js:440-456) -------------
+    def raycastVisual(self, origins, directions, near=0.0, far=np.inf):
+        """three.js `Raycaster(origin, direction, near, far).intersectObject(visMesh)[0]` for every ray, on the device, bit for bit:
+        a structured array (RAY_HIT_DTYPE: hit, body, triangle = faceIndex, distance, point)."""
+        rays = make_rays(origins, directions, near, far)
+        hits = np.zeros(len(rays), dtype=RAY_HIT_DTYPE)
+        capi.check(self._L.tetsim_raycast_visual(self._h, rays.ctypes.data, len(rays), hits.ctypes.data), self._h)
+        return hits
+
+    def startGrabRay(self, origin, direction, near=0.0, far=np.inf):
+        """Grabber.start in one call: cast the ray, grab the particle nearest to the hit point.  Returns (grabId, hit record);
+        a miss leaves the grab as it was and returns (-1, record with hit 0)."""
+        ray = make_rays(origin, direction, near, far)
+        hit = np.zeros(1, dtype=RAY_HIT_DTYPE)
+        gid = C.c_int32(-1)
+        capi.check(self._L.tetsim_start_grab_ray(self._h, ray.ctypes.data_as(C.POINTER(capi.TetSimRay)), hit.ctypes.data_as(C.POINTER(capi.TetSimRayHit)),
+                                                 C.byref(gid)), self._h)
+        if hit["hit"][0]:
+            self.grabId = gid.value
+            self.grabPos[:] = (ray["origin"][0] + ray["direction"][0] * hit["distance"][0]).astype(np.float32)
+        return gid.value, hit[0]
+
+    def visualBoundingSphere(self):
+        """`visMesh.geometry.computeBoundingSphere()` (Softbody.js:256,276) on the device: (centre [3] f64, radius)."""
+        c, r = np.empty(3, dtype=np.float64), C.c_double()
+        capi.check(self._L.tetsim_read_visual_bounding_sphere(self._h, c.ctypes.data_as(C.POINTER(C.c_double)), C.byref(r)), self._h)
+        return c, float(r.value)
 
     def nearestParticle(self, pos):
         """(global id, squared distance) of the owned particle nearest to pos -- the building block of startGrab for partitioned
