@@ -462,6 +462,63 @@ typedef struct TetSimCollider {
  * rounded once to f32. */
 int tetsim_set_colliders(tetsim_handle h, const TetSimCollider *colliders, uint32_t count);
 
+/* --- device-side export and import: results for another GPU program, without a host copy -------- */
+
+/* Whoever consumes the state on the device -- a PyTorch model, a renderer, a training loop that resets a batch of bodies -- gets it
+ * in ITS memory, ordered against ITS stream; neither call synchronises the host.  An ADDITIVE extension of ABI version 5
+ * (TETSIM_ABI_VERSION is unchanged; no existing struct changed): look the symbols up.
+ *
+ * Rows and values are exactly what the matching host read returns, bit for bit, in the API's order (not the internal one), f32:
+ *   TETSIM_FIELD_POSITIONS / _VELOCITIES / _PREV_POSITIONS   owned_particles rows of xyz: tetsim_read_positions / _velocities /
+ *                                                            _prev_positions
+ *   TETSIM_FIELD_QUATS                                       local_elems rows of xyzw in tetsim_get_local_tets order: tetsim_read_quats
+ *                                                            (a TETSIM_FLAG_LEAN_STATE body recovers them first, on the device)
+ *   TETSIM_FIELD_VISUAL_POSITIONS / _VISUAL_NORMALS          num_vis_verts rows of xyz: the two outputs of tetsim_read_visual_mesh
+ *   TETSIM_FIELD_VISUAL_VERTEX_NORMALS                       num_vis_verts rows of xyz: tetsim_read_visual_vertex_normals
+ * (the call skins, and computes the vertex normals, first; a batch is the concatenation, as everywhere).  Row r of a field goes to
+ * dst + r * row_stride: 3 floats (QUATS: 4), and NOTHING else is written -- not the padding of a wider row, not a byte outside the
+ * rows.  All fields of one call leave in one kernel launch.
+ *
+ * THE STREAM CONTRACT.  consumer_stream / producer_stream are hipStream_t values of the handle's device; 0 (NULL) is the legacy
+ * default stream, which is what PyTorch uses unless told otherwise.  The handle steps on a non-blocking stream of its own, which
+ * nothing orders against the caller's streams but these two calls:
+ *   tetsim_export_device  (1) records an event on consumer_stream and (2) makes the handle's stream wait for it -- whatever the
+ *     caller enqueued earlier that still reads or writes `dst` is done before the export writes; (3) enqueues the export on the
+ *     handle's stream, behind every substep enqueued so far; (4) records an event there and makes consumer_stream wait for it.
+ *     After the call returns, work the caller enqueues on consumer_stream sees the data; substeps enqueued on the handle afterwards do
+ *     not disturb it (they never touch `dst`).  Work on OTHER streams of the caller needs the caller's own ordering against
+ *     consumer_stream.
+ *   tetsim_import_device  (1) the handle's stream waits for an event recorded on producer_stream -- `pos` and `vel` are complete;
+ *     (2) one kernel writes the state, behind every substep enqueued so far; (3) producer_stream waits for that kernel, so the
+ *     caller may reuse or free `pos` and `vel` in stream order.
+ * The events live in the handle (created by the first such call, destroyed by tetsim_destroy).  Only that first call of a handle may
+ * block: it allocates them and, for a body with an internal particle order, uploads the index map once.
+ *
+ * tetsim_import_device leaves the state tetsim_write_state leaves for the same numbers: pos / vel [owned_particles] rows of xyz, the
+ * inverse masses kept; POLAR_JACOBI predicts afresh at the next step; per-tet state (quaternions, carried shape) is untouched.
+ * pos_stride / vel_stride follow the rule of row_stride below.
+ *
+ * Every error is found before anything is enqueued and leaves `dst` and the state as they were.  TETSIM_EINVAL: a NULL handle,
+ * `fields`, `dst`, `pos` or `vel`; count == 0 or count > TETSIM_MAX_EXPORT_FIELDS; an unknown field; reserved != 0; a stride that is
+ * neither 0 nor a multiple of 4 of at least the row's bytes; a pointer that is not 4-byte aligned, that hipPointerGetAttributes does
+ * not report as device memory of the handle's device, or whose rows do not fit the allocation it points into.  TETSIM_ESTATE: QUATS or
+ * VISUAL_NORMALS on a NEOHOOKEAN_GS body (VISUAL_NORMALS also needs the rest normals of tetsim_set_visual_mesh); PREV_POSITIONS on
+ * a POLAR_JACOBI body; a visual field without a visual mesh, VISUAL_VERTEX_NORMALS without triangles; any partitioned body (its halo
+ * stream and ghosts need a contract of their own).
+ * Out of scope: partitioned bodies; element types other than f32; gradients; device-resident grab targets or collider lists. */
+enum { TETSIM_FIELD_POSITIONS = 0, TETSIM_FIELD_VELOCITIES = 1, TETSIM_FIELD_PREV_POSITIONS = 2,
+       TETSIM_FIELD_QUATS = 3, TETSIM_FIELD_VISUAL_POSITIONS = 4, TETSIM_FIELD_VISUAL_NORMALS = 5,
+       TETSIM_FIELD_VISUAL_VERTEX_NORMALS = 6 };
+#define TETSIM_MAX_EXPORT_FIELDS 8
+typedef struct TetSimDeviceField {
+    int32_t field, reserved;   /* reserved must be 0 */
+    void *dst;                 /* DEVICE memory of the handle's device, 4-byte aligned */
+    uint64_t row_stride;       /* bytes between rows; 0 = packed (12, QUATS 16); otherwise >= row bytes and a multiple of 4 */
+} TetSimDeviceField;
+int tetsim_export_device(tetsim_handle h, const TetSimDeviceField *fields, uint32_t count, void *consumer_stream);
+int tetsim_import_device(tetsim_handle h, const void *pos, uint64_t pos_stride,
+                         const void *vel, uint64_t vel_stride, void *producer_stream);
+
 /* --- measurement ----------------------------------------------------------------------------- */
 
 /* Run n substeps eagerly on the handle's own stream; every POLAR_JACOBI kernel carries its own begin/end HIP

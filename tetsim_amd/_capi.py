@@ -19,6 +19,8 @@ FLAG_LEAN_STATE = 128
 K_TET, K_VERTEX, K_HALO, K_COUNT = 0, 1, 2, 3
 COLLIDER_SPHERE, COLLIDER_CAPSULE, COLLIDER_BOX, COLLIDER_PLANE = 0, 1, 2, 3
 MAX_COLLIDERS = 8
+FIELD_POSITIONS, FIELD_VELOCITIES, FIELD_PREV_POSITIONS, FIELD_QUATS, FIELD_VISUAL_POSITIONS, FIELD_VISUAL_NORMALS, FIELD_VISUAL_VERTEX_NORMALS = range(7)
+MAX_EXPORT_FIELDS = 8
 
 
 class TetSimParams(C.Structure):
@@ -104,6 +106,10 @@ class TetSimRayHit(C.Structure):
                 ("point", C.c_double * 3)]
 
 
+class TetSimDeviceField(C.Structure):
+    _fields_ = [("field", C.c_int32), ("reserved", C.c_int32), ("dst", C.c_void_p), ("row_stride", C.c_uint64)]
+
+
 # every symbol include/tetsim.h declares (tests check the library exports exactly these)
 SYMBOLS = [
     "tetsim_abi_version", "tetsim_default_options", "tetsim_default_params", "tetsim_create", "tetsim_create_batch", "tetsim_get_batch_layout", "tetsim_destroy",
@@ -121,11 +127,13 @@ SYMBOLS = [
     "tetsim_plan_arrays", "tetsim_plan_neighbour", "tetsim_plan_neighbour_ids",
     "tetsim_plan_create_deep", "tetsim_plan_layers", "tetsim_plan_neighbour_layer2", "tetsim_plan_neighbour_layer2_ids",
     "tetsim_raycast_visual", "tetsim_start_grab_ray", "tetsim_read_visual_bounding_sphere", "tetsim_prep_boundary_surface",
+    "tetsim_export_device", "tetsim_import_device",
     "tetsim_mesh_write", "tetsim_mesh_open", "tetsim_mesh_arrays", "tetsim_mesh_close", "tetsim_create_from_file",
 ]
 
 # additive to ABI 5 (looked up by name: a library built before them lacks them and still loads; calling one then raises)
-OPTIONAL_SYMBOLS = ("tetsim_set_colliders", "tetsim_raycast_visual", "tetsim_start_grab_ray", "tetsim_read_visual_bounding_sphere", "tetsim_prep_boundary_surface")
+OPTIONAL_SYMBOLS = ("tetsim_set_colliders", "tetsim_raycast_visual", "tetsim_start_grab_ray", "tetsim_read_visual_bounding_sphere", "tetsim_prep_boundary_surface",
+                    "tetsim_export_device", "tetsim_import_device")
 
 _lib = None
 
@@ -197,6 +205,9 @@ def lib():
         L.tetsim_start_grab_ray.argtypes = [H, C.POINTER(TetSimRay), C.POINTER(TetSimRayHit), ip]
         L.tetsim_read_visual_bounding_sphere.argtypes = [H, dp, dp]
         L.tetsim_prep_boundary_surface.argtypes = [fp, ip, u32, u32, fp, ip, C.POINTER(u32), C.POINTER(u32)]
+    if hasattr(L, "tetsim_export_device"):   # (additive to ABI 5; pointers and streams travel as plain addresses)
+        L.tetsim_export_device.argtypes = [H, C.POINTER(TetSimDeviceField), u32, C.c_void_p]
+        L.tetsim_import_device.argtypes = [H, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]
     L.tetsim_profile.argtypes = [H, u32, dbl, PP, C.POINTER(TetSimProfile)]
     L.tetsim_time_kernels.argtypes = [H, u32, dbl, PP, C.POINTER(TetSimProfile)]
     L.tetsim_time_step_n.argtypes = [H, u32, dbl, PP, dp]

@@ -35,6 +35,7 @@ UNITS = {
     "tetsim_state.hip": ["-ffp-contract=off"],
     "tetsim_visual.hip": ["-ffp-contract=off"],
     "tetsim_measure.hip": ["-ffp-contract=off"],
+    "device_io.hip": ["-ffp-contract=off"],
     "tetsim_create.hip": ["-ffp-contract=off"],
     "tetsim_halo.hip": ["-ffp-contract=off"],
     "tetsim_comm.hip": ["-ffp-contract=off"],

@@ -3,6 +3,7 @@
 //   tetsim_api.hip     lifecycle, stepping (streams / graphs)
 //   tetsim_state.hip   state read-back (copying / pinned), checkpoint and resume, plan getters
 //   tetsim_visual.hip  embedded visual mesh (skinning, vertex normals), grab (pin, nearest-particle query)
+//   device_io.hip     export / import of the state in device memory, ordered against a caller's stream (no host copy, no host sync)
 //   tetsim_measure.hip measurement: per-kernel profile, kernel timing loops, device copy bandwidth
 //   tetsim_create.hip  construction of the two solvers' device state (host preprocessing -> uploads)
 //   tetsim_halo.hip    multi-GPU: per-substep halo choreography (two queues, flag or event synchronised), in-process group stepping
@@ -268,6 +269,10 @@ struct tetsim_body {
     float* d_packed = nullptr;     //   and its device-side staging
     float* pinned_quat = nullptr;  // tetsim_read_quats_pinned: host-pinned xyzw per local tet
     uint32_t* d_api2dev = nullptr; // device copy of api2dev (pack / nearest kernels), null = identity
+    // tetsim_export_device / tetsim_import_device (device_io.hip): [call parity][0 = recorded on the caller's stream, 1 = on h->stream],
+    // created by the first such call; double buffered like the halo events above
+    hipEvent_t ev_io[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
+    uint32_t io_parity = 0;
     double* d_best = nullptr; uint32_t* d_best_id = nullptr;  // tetsim_start_grab candidates
     // tetsim_raycast_visual / tetsim_read_visual_bounding_sphere (query_kernels.hip): allocated by the first query, grown on demand
     uint32_t* d_sphere = nullptr;

@@ -682,7 +682,7 @@ void tetsim_destroy(tetsim_handle h) {
     if (h->pinned_quat) (void)hipHostFree(h->pinned_quat);
     for (hipEvent_t ev : {h->ev_a, h->ev_b, h->ev_halo, h->ev_boundary2[0], h->ev_boundary2[1], h->ev_packed2[0], h->ev_packed2[1],
                           h->ev_sent2[0], h->ev_sent2[1]}) if (ev) (void)hipEventDestroy(ev);
-    for (hipEvent_t ev : {h->ev_fork, h->ev_bnd_tet}) if (ev) (void)hipEventDestroy(ev);
+    for (hipEvent_t ev : {h->ev_fork, h->ev_bnd_tet, h->ev_io[0][0], h->ev_io[0][1], h->ev_io[1][0], h->ev_io[1][1]}) if (ev) (void)hipEventDestroy(ev);
     if (h->comm_stream) (void)hipStreamDestroy(h->comm_stream);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;

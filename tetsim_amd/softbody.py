@@ -107,6 +107,20 @@ def make_params(physicsParams):
     return p
 
 
+# exportTensors: name -> (TETSIM_FIELD_*, the TetSimInfo count of its rows, floats per row)
+_EXPORT_FIELDS = {"pos": (capi.FIELD_POSITIONS, "owned_particles", 3), "vel": (capi.FIELD_VELOCITIES, "owned_particles", 3),
+                  "prevPos": (capi.FIELD_PREV_POSITIONS, "owned_particles", 3), "quats": (capi.FIELD_QUATS, "local_elems", 4),
+                  "visPos": (capi.FIELD_VISUAL_POSITIONS, "num_vis_verts", 3), "visNormals": (capi.FIELD_VISUAL_NORMALS, "num_vis_verts", 3),
+                  "visVertexNormals": (capi.FIELD_VISUAL_VERTEX_NORMALS, "num_vis_verts", 3)}
+
+
+def _check_rows(torch, t, dev, n, width, name):
+    """A tensor the device hand-over may read or write: float32 [n, width] on dev, every row contiguous, rows not overlapping."""
+    if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != dev or tuple(t.shape) != (n, width)
+            or (n and t.stride(1) != 1) or (n > 1 and t.stride(0) < width)):
+        raise ValueError("%s must be a float32 tensor on %s of shape (%d, %d) with contiguous, non-overlapping rows" % (name, dev, n, width))
+
+
 class SoftBodyHIP:
     """Drop-in for `new SoftBody(...)` / `new SoftBodyGPU(...)`; `solver` picks which one is mirrored.
 
@@ -185,6 +199,7 @@ class SoftBodyHIP:
         self.info = capi.TetSimInfo()
         capi.check(L.tetsim_get_info(self._h, C.byref(self.info)), self._h)
         self._L = L
+        self._export_cache = {}   # exportTensors: name -> the tensor it allocated
         self.numVisVerts = 0
         if visVerts is not None and len(visVerts):   # Softbody.js:46-47: rows (tetNr, b0, b1, b2); a partition keeps the rows of the tets it owns (visualIds)
             if mesh_file is not None:   # tetsim_create_from_file attached the stored visual mesh already
@@ -335,6 +350,54 @@ class SoftBodyHIP:
     def writeState(self, pos, vel):
         p, v = _f32(pos).reshape(-1), _f32(vel).reshape(-1)
         capi.check(self._L.tetsim_write_state(self._h, _fp(p), _fp(v)), self._h)
+
+    # -- device-side hand-over to PyTorch (include/tetsim.h: tetsim_export_device / tetsim_import_device) -----------
+    def _torch_stream(self, torch, stream):
+        dev = torch.device("cuda", self.info.device)
+        if stream is None:
+            return dev, torch.cuda.current_stream(dev).cuda_stream
+        return dev, int(getattr(stream, "cuda_stream", stream))
+
+    def exportTensors(self, fields=("pos",), out=None, stream=None):
+        """{name: torch.Tensor} of the named fields (_EXPORT_FIELDS: pos, vel, prevPos, quats, visPos, visNormals, visVertexNormals) on
+        the handle's device, float32 [rows, 3] ([rows, 4] for quats), bit for bit what the host read of the same name returns -- without
+        a host copy and without synchronising: the tensors are valid for work enqueued on `stream` (a torch stream or a raw
+        hipStream_t; None = torch's current stream of that device) after this returns.  All fields leave in one kernel launch.
+        The tensors are allocated once and reused by later calls unless `out` supplies them ({name: tensor}; rows may be strided:
+        the row stride is out[name].stride(0), anything between the rows is left alone)."""
+        import torch
+        dev, s = self._torch_stream(torch, stream)
+        names = [fields] if isinstance(fields, str) else list(fields)
+        cache = self._export_cache
+        arr = (capi.TetSimDeviceField * max(1, len(names)))()
+        res = {}
+        for f, name in zip(arr, names):
+            field, rows, width = _EXPORT_FIELDS[name]
+            n = int(getattr(self.info, rows))
+            t = out.get(name) if out is not None else None
+            if t is None:
+                t = cache.get(name)
+                if t is None or t.shape[0] != n:   # (num_vis_verts changes when a visual mesh is attached)
+                    t = cache[name] = torch.empty((n, width), dtype=torch.float32, device=dev)
+            else:
+                _check_rows(torch, t, dev, n, width, "out[%r]" % name)
+            f.field, f.reserved, f.dst = field, 0, t.data_ptr()
+            f.row_stride = 4 * t.stride(0) if n > 1 else 0
+            res[name] = t
+        capi.check(self._L.tetsim_export_device(self._h, arr, len(names), s), self._h)
+        return res
+
+    def importTensors(self, pos, vel, stream=None):
+        """writeState from device tensors: float32 [owned_particles, 3] on the handle's device, rows contiguous (the rows themselves may
+        be strided).  No host copy, no synchronisation: the state is written behind the substeps enqueued so far once `stream` (None =
+        torch's current stream) has produced the tensors, and `stream` may reuse them afterwards."""
+        import torch
+        dev, s = self._torch_stream(torch, stream)
+        n = self.info.owned_particles
+        _check_rows(torch, pos, dev, n, 3, "pos")
+        _check_rows(torch, vel, dev, n, 3, "vel")
+        capi.check(self._L.tetsim_import_device(self._h, pos.data_ptr(), 4 * pos.stride(0) if n > 1 else 0,
+                                                vel.data_ptr(), 4 * vel.stride(0) if n > 1 else 0, s), self._h)
 
     # -- embedded visual mesh (Softbody.js:259-277 / SoftbodyGPU.js:424-448), skinned on the device ---------------
     def setVisualMesh(self, visVerts, restNormals=None):
