@@ -158,7 +158,9 @@ typedef struct TetSimInfo {
     uint32_t max_valence;        /* max incident tets per vertex used by the scatter table */
     uint32_t dropped_slots;      /* (tet,vertex) contributions dropped by TETSIM_FLAG_REF_SLOT_TABLE */
     uint32_t num_neighbours;     /* partitions this handle exchanges a halo with */
-    uint64_t device_bytes;       /* HBM allocated by this handle */
+    uint64_t device_bytes;       /* HBM allocated by this handle so far: buffers of the read-out and query calls are allocated by the first
+                                    call that needs them (the staging buffer of the pinned reads, tetsim_read_visual_mesh and
+                                    tetsim_read_visual_vertex_normals by the first of those, grown to the largest request) and count from then on */
     int32_t solver, precision, order, device;
     uint32_t flags;
     uint32_t num_vis_verts;      /* visual vertices attached by tetsim_set_visual_mesh / a .tetsim file (0 = none); since ABI 3 */

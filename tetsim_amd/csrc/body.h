@@ -1,9 +1,12 @@
 // body.h -- the handle behind tetsim_handle and the helpers the translation units of the C ABI share.
 //
 //   tetsim_api.hip     lifecycle, stepping (streams / graphs)
-//   tetsim_state.hip   state read-back (copying / pinned), checkpoint and resume, plan getters
-//   tetsim_visual.hip  embedded visual mesh (skinning, vertex normals), grab (pin, nearest-particle query)
-//   device_io.hip     export / import of the state in device memory, ordered against a caller's stream (no host copy, no host sync)
+//   tetsim_state.hip   the state's host entry points: reads (copying: on the host; pinned: through the gather), tetsim_write_state,
+//                      checkpoint and resume, plan getters
+//   tetsim_visual.hip  embedded visual mesh (its set-up and its host reads), grab (pin, nearest-particle query), picking
+//   device_io.hip      how rows leave and enter the device arrays, for all of the above: the table of TETSIM_FIELD_* (source, rows, width,
+//                      index map, what must run first, which requests are errors), the one gather kernel and the staging buffer of the
+//                      host reads that use it; and export / import in device memory, ordered against a caller's stream
 //   tetsim_measure.hip measurement: per-kernel profile, kernel timing loops, device copy bandwidth
 //   tetsim_create.hip  construction of the two solvers' device state (host preprocessing -> uploads)
 //   tetsim_halo.hip    multi-GPU: per-substep halo choreography (two queues, flag or event synchronised), in-process group stepping
@@ -266,9 +269,10 @@ struct tetsim_body {
     uint32_t vis_total = 0;            // rows of the caller's visVerts (a partition keeps num_vis_verts of them)
     float4* d_vis_full = nullptr;      // partitions with visual triangles: every rank's skin put together, [vis_total] (tetsim_visual_vertex_normals_from)
     float* pinned_pos = nullptr;   // tetsim_read_positions_pinned: host-pinned xyz
-    float* d_packed = nullptr;     //   and its device-side staging
+    float* d_packed = nullptr;     // staging of the pinned and the visual reads: packed rows, grown to the largest request so far (read_rows)
+    size_t packed_cap = 0;         //   floats in it
     float* pinned_quat = nullptr;  // tetsim_read_quats_pinned: host-pinned xyzw per local tet
-    uint32_t* d_api2dev = nullptr; // device copy of api2dev (pack / nearest kernels), null = identity
+    uint32_t* d_api2dev = nullptr; // device copy of api2dev (gather / scatter / nearest kernels), null = identity
     // tetsim_export_device / tetsim_import_device (device_io.hip): [call parity][0 = recorded on the caller's stream, 1 = on h->stream],
     // created by the first such call; double buffered like the halo events above
     hipEvent_t ev_io[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
@@ -386,11 +390,26 @@ void nh_sweep(tetsim_body* h, bool fold = false, bool last = true, bool one_laun
 // first / last: position inside a run of substeps enqueued back to back with one dt
 int enqueue_substep(tetsim_body* h, bool first = true, bool last = true);
 int ensure_prediction(tetsim_body* h, double dt);
-int read_float4_as_xyz(tetsim_body* h, const float4* src, uint32_t n, float* out);
 // ---- state read-back helpers (tetsim_state.hip)
 const float4* current_positions(tetsim_body* h);   // end-of-substep positions of either solver
 int ensure_quats(tetsim_body* h);                  // lean-state bodies: pj.quat brought up to date on h->stream (behind both queues' work); else nothing
-int ensure_index_map(tetsim_body* h);              // device copy of api2dev (pack / nearest kernels)
+int ensure_index_map(tetsim_body* h);              // device copy of api2dev (gather / scatter / nearest kernels)
+// ---- rows out of and into the device arrays (device_io.hip)
+int drain(tetsim_body* h);                         // set the device, wait for h->stream, then for h->comm_stream if there is one
+struct FieldSrc {                                  // a TETSIM_FIELD_* on this body: row r = `width` floats of src[mapped ? d_api2dev[r] : r]
+    const float4* src = nullptr;
+    uint32_t rows = 0, width = 3;
+    bool mapped = false;
+    bool quats = false, skin = false, vnrm = false;   // what runs first: quaternion recovery, skinning, vertex normals
+};
+// 0, or TETSIM_ESTATE / TETSIM_EINVAL and in *why the reason the body has no such field (host_reader: in the tetsim_read_* wording)
+int resolve_field(tetsim_body* h, int32_t field, bool host_reader, FieldSrc* f, std::string* why);
+int prepare_fields(tetsim_body* h, const FieldSrc* f, uint32_t count);   // once per request, on h->stream: index map, quaternions, skin, vertex normals
+// the pinned reads and the visual mesh's reads: comm_stream drained, prepare_fields, then read_rows -- the gather into the staging buffer on h->stream and one copy per
+// field to out[k], behind a stream sync (pinned: an async copy in stream order, then the sync); count <= TETSIM_MAX_EXPORT_FIELDS
+int read_fields(tetsim_body* h, const FieldSrc* f, float* const* out, uint32_t count, bool pinned = false);
+// (on its own for tetsim_visual_vertex_normals_from, which computes the normals of the caller's positions and must not skin first)
+int read_rows(tetsim_body* h, const FieldSrc* f, float* const* out, uint32_t count, bool pinned = false);
 
 // ---- construction (tetsim_create.hip)
 int create_polar(tetsim_body* h, const float* verts, uint32_t nv, const int32_t* tets, uint32_t nt);

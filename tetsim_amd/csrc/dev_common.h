@@ -353,7 +353,6 @@ struct SkinDev {
 void skin_launch(hipStream_t s, const SkinDev& d, const float4* pos, const float4* quat, bool js_order);
 void skin_launch_vertex_normals(hipStream_t s, const SkinDev& d);   // three.js computeVertexNormals of d.out_pos -> d.out_vnrm
 
-void util_launch_pack_xyz(hipStream_t s, const float4* src, const uint32_t* map, float* out, uint32_t n);
 void util_launch_nearest(hipStream_t s, const float4* pos, const uint32_t* map, uint32_t n, double px, double py, double pz,
                          double* best_d2, uint32_t* best_id);
 void util_launch_copy(hipStream_t s, const float4* src, float4* dst, uint64_t n);

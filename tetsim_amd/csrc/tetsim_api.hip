@@ -454,21 +454,6 @@ int build_graph(tetsim_body* h, uint32_t n, hipGraphExec_t* out) {
     return 0;
 }
 
-int read_float4_as_xyz(tetsim_body* h, const float4* src, uint32_t n, float* out) {
-    if (!out) return fail(h, TETSIM_EINVAL, "output pointer is null");
-    HIPCHK(h, hipSetDevice(h->opt.device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->comm_stream) HIPCHK(h, hipStreamSynchronize(h->comm_stream));
-    std::vector<float4> tmp(n);
-    if (n) HIPCHK(h, hipMemcpy(tmp.data(), src, n * sizeof(float4), hipMemcpyDeviceToHost));
-    const bool perm = h->opt.solver == TETSIM_SOLVER_POLAR_JACOBI && !h->api2dev.empty();
-    for (uint32_t i = 0; i < n; i++) {
-        const float4& t = tmp[perm ? h->api2dev[i] : i];  // owned particles keep their segment: api2dev[i] < n
-        out[3 * i] = t.x; out[3 * i + 1] = t.y; out[3 * i + 2] = t.z;
-    }
-    return 0;
-}
-
 }  // namespace tetsim
 
 
@@ -640,7 +625,7 @@ int tetsim_get_batch_layout(tetsim_handle h, uint32_t* first_particle, uint32_t*
 
 void tetsim_destroy(tetsim_handle h) {
     if (!h) return;
-    (void)hipSetDevice(h->opt.device);
+    (void)hipSetDevice(h->opt.device);   // (not drain(): every queue is tried, whatever the one before it answered)
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     if (h->comm_stream) (void)hipStreamSynchronize(h->comm_stream);
     // an in-process group: the other members' queues may still hold transfers into THIS body's ghost ranges; and they forget this body
@@ -846,9 +831,7 @@ int tetsim_step_n(tetsim_handle h, uint32_t n, double dt, const TetSimParams* pa
 
 int tetsim_sync(tetsim_handle h) {
     if (!h) return TETSIM_EINVAL;
-    HIPCHK(h, hipSetDevice(h->opt.device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->comm_stream) HIPCHK(h, hipStreamSynchronize(h->comm_stream));
+    if (int rc = drain(h)) return rc;
     if (h->d_frame_err) {   // persistent frame kernel: a tile's wait for its neighbours' partial sums gave up (never in a correct run)
         uint32_t err = 0;
         HIPCHK(h, hipMemcpy(&err, h->d_frame_err, sizeof err, hipMemcpyDeviceToHost));

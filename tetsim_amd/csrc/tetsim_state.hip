@@ -1,5 +1,6 @@
-// tetsim_state.hip -- C ABI, part 2 (include/tetsim.h): reading the solver's state back (copying and pinned zero-copy reads),
-// checkpoint / resume of the complete state, and the small getters (plans, orders, inverse masses).  See body.h.
+// tetsim_state.hip -- C ABI, part 2 (include/tetsim.h): the host entry points that read the solver's state back (what a field is: device_io.hip;
+// copying reads narrow on the host, pinned zero-copy reads gather on the device) and write it, checkpoint / resume of the
+// complete state, and the small getters (plans, orders, inverse masses).  See body.h.
 #include <thread>
 
 #include "body.h"
@@ -30,61 +31,49 @@ int ensure_index_map(tetsim_body* h) {  // internal Morton numbering -> API numb
 
 extern "C" {
 
-int tetsim_read_positions(tetsim_handle h, float* out) {
-    if (!h) return TETSIM_EINVAL;
-    return h->opt.solver == TETSIM_SOLVER_POLAR_JACOBI ? read_float4_as_xyz(h, h->pj.pos_final, h->pj.nv_owned, out)
-                                                       : read_float4_as_xyz(h, h->nh.pos, h->nh.nv, out);
-}
-
-int tetsim_read_positions_pinned(tetsim_handle h, const float** out) {
-    if (!h || !out) return fail(h, TETSIM_EINVAL, "null argument");
-    HIPCHK(h, hipSetDevice(h->opt.device));
-    const uint32_t n = h->info.owned_particles;
-    int rc;
-    if (!h->pinned_pos) {
-        HIPCHK(h, hipHostMalloc(reinterpret_cast<void**>(&h->pinned_pos), std::max<size_t>(3ull * n, 1) * sizeof(float), hipHostMallocDefault));
-        if ((rc = dev_alloc(h, &h->d_packed, 3ull * n))) return rc;
-        if ((rc = ensure_index_map(h))) return rc;
+namespace {
+// one field to the caller's memory, or (pinned) to a host-pinned buffer of the handle's that the first call allocates
+int read_field(tetsim_body* h, int32_t field, float* out, float** pinned = nullptr) {
+    FieldSrc f;
+    std::string why;
+    if (int rc = resolve_field(h, field, true, &f, &why)) return fail(h, rc, why);
+    if (pinned) {
+        HIPCHK(h, hipSetDevice(h->opt.device));
+        if (!*pinned) HIPCHK(h, hipHostMalloc(reinterpret_cast<void**>(pinned), std::max<size_t>(size_t(f.rows) * f.width, 1) * sizeof(float), hipHostMallocDefault));
+        out = *pinned;
     }
-    if (h->comm_stream) HIPCHK(h, hipStreamSynchronize(h->comm_stream));
-    util_launch_pack_xyz(h->stream, current_positions(h), h->d_api2dev, h->d_packed, n);
-    if (n) HIPCHK(h, hipMemcpyAsync(h->pinned_pos, h->d_packed, 3ull * n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    *out = h->pinned_pos;
+    if (!out) return fail(h, TETSIM_EINVAL, "output pointer is null");
+    if (pinned || f.width == 4u) return read_fields(h, &f, &out, 1, pinned != nullptr);
+    // A copying read of particle rows stays on the host: one copy of the 16-byte rows and a loop.  Through the gather it would cost a
+    // kernel launch and the wait for it -- about 15 us, more than the whole call on a body of a thousand particles
+    // (profiles/state_io_cost.txt); a host that reads every frame has the pinned read.
+    if (int rc = drain(h)) return rc;
+    std::vector<float4> tmp(f.rows);
+    if (f.rows) HIPCHK(h, hipMemcpy(tmp.data(), f.src, f.rows * sizeof(float4), hipMemcpyDeviceToHost));
+    for (uint32_t i = 0; i < f.rows; i++) {
+        const float4& t = tmp[f.mapped ? h->api2dev[i] : i];  // owned particles keep their segment: api2dev[i] < rows
+        out[3 * i] = t.x; out[3 * i + 1] = t.y; out[3 * i + 2] = t.z;
+    }
     return 0;
 }
+}  // namespace
 
-int tetsim_read_prev_positions(tetsim_handle h, float* out) {
-    if (!h) return TETSIM_EINVAL;
-    if (h->opt.solver == TETSIM_SOLVER_POLAR_JACOBI)
-        return fail(h, TETSIM_ESTATE, "POLAR_JACOBI does not keep prevPos after a substep (it equals the previous read_positions)");
-    return read_float4_as_xyz(h, h->nh.prev, h->nh.nv, out);
-}
-int tetsim_read_velocities(tetsim_handle h, float* out) {
-    if (!h) return TETSIM_EINVAL;
-    return h->opt.solver == TETSIM_SOLVER_POLAR_JACOBI ? read_float4_as_xyz(h, h->pj.vel, h->pj.nv_owned, out)
-                                                       : read_float4_as_xyz(h, h->nh.vel, h->nh.nv, out);
-}
+int tetsim_read_positions(tetsim_handle h, float* out) { return h ? read_field(h, TETSIM_FIELD_POSITIONS, out) : TETSIM_EINVAL; }
+int tetsim_read_prev_positions(tetsim_handle h, float* out) { return h ? read_field(h, TETSIM_FIELD_PREV_POSITIONS, out) : TETSIM_EINVAL; }
+int tetsim_read_velocities(tetsim_handle h, float* out) { return h ? read_field(h, TETSIM_FIELD_VELOCITIES, out) : TETSIM_EINVAL; }
 int tetsim_read_quats(tetsim_handle h, float* out) {
     if (!h || !out) return fail(h, TETSIM_EINVAL, "null argument");
-    if (h->opt.solver != TETSIM_SOLVER_POLAR_JACOBI) return fail(h, TETSIM_ESTATE, "quaternions exist only for POLAR_JACOBI");
-    HIPCHK(h, hipSetDevice(h->opt.device));
-    if (int rc = ensure_quats(h)) return rc;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->comm_stream) HIPCHK(h, hipStreamSynchronize(h->comm_stream));
-    if (h->pj.nt) HIPCHK(h, hipMemcpy(out, h->pj.quat, h->pj.nt * sizeof(float4), hipMemcpyDeviceToHost));
+    return read_field(h, TETSIM_FIELD_QUATS, out);
+}
+int tetsim_read_positions_pinned(tetsim_handle h, const float** out) {
+    if (!h || !out) return fail(h, TETSIM_EINVAL, "null argument");
+    if (int rc = read_field(h, TETSIM_FIELD_POSITIONS, nullptr, &h->pinned_pos)) return rc;
+    *out = h->pinned_pos;
     return 0;
 }
 int tetsim_read_quats_pinned(tetsim_handle h, const float** out) {
     if (!h || !out) return fail(h, TETSIM_EINVAL, "null argument");
-    if (h->opt.solver != TETSIM_SOLVER_POLAR_JACOBI) return fail(h, TETSIM_ESTATE, "quaternions exist only for POLAR_JACOBI");
-    HIPCHK(h, hipSetDevice(h->opt.device));
-    const size_t n = h->pj.nt;
-    if (!h->pinned_quat) HIPCHK(h, hipHostMalloc(reinterpret_cast<void**>(&h->pinned_quat), std::max<size_t>(n, 1) * sizeof(float4), hipHostMallocDefault));
-    if (h->comm_stream) HIPCHK(h, hipStreamSynchronize(h->comm_stream));  // ghost tiles write their quaternions on the halo stream
-    if (int rc = ensure_quats(h)) return rc;
-    if (n) HIPCHK(h, hipMemcpyAsync(h->pinned_quat, h->pj.quat, n * sizeof(float4), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (int rc = read_field(h, TETSIM_FIELD_QUATS, nullptr, &h->pinned_quat)) return rc;
     *out = h->pinned_quat;
     return 0;
 }
@@ -174,9 +163,7 @@ int state_guard(tetsim_body* h) {
 // partitions of one process (in-process group: sender-driven copies, peer-to-peer stores through plain pointers) -- the queues of
 // the other members, whose transfers of the last substep land in THIS body's ghost range.
 int quiesce(tetsim_body* h) {
-    HIPCHK(h, hipSetDevice(h->opt.device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->comm_stream) HIPCHK(h, hipStreamSynchronize(h->comm_stream));
+    if (int rc = drain(h)) return rc;
     for (tetsim_body* g : h->group) {
         if (!g || g == h) continue;
         HIPCHK(h, hipSetDevice(g->opt.device));
@@ -303,8 +290,7 @@ int tetsim_load_state(tetsim_handle h, const void* blob, uint64_t bytes) {
 int tetsim_read_vol_error(tetsim_handle h, double* out) {
     if (!h || !out) return fail(h, TETSIM_EINVAL, "null argument");
     if (h->opt.solver != TETSIM_SOLVER_NEOHOOKEAN_GS) return fail(h, TETSIM_ESTATE, "volError exists only for NEOHOOKEAN_GS");
-    HIPCHK(h, hipSetDevice(h->opt.device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (int rc = drain(h)) return rc;
     std::vector<double> ve(h->nh.nt);
     if (h->nh.nt) HIPCHK(h, hipMemcpy(ve.data(), h->nh.vol_err, h->nh.nt * sizeof(double), hipMemcpyDeviceToHost));
     double s = 0.0;  // Softbody.js:163 accumulates in element order; :209 divides by numElems
@@ -314,8 +300,8 @@ int tetsim_read_vol_error(tetsim_handle h, double* out) {
 }
 int tetsim_write_state(tetsim_handle h, const float* pos, const float* vel) {
     if (!h || !pos || !vel) return fail(h, TETSIM_EINVAL, "null argument");
-    HIPCHK(h, hipSetDevice(h->opt.device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (h->partitioned && !h->neigh.empty()) return fail(h, TETSIM_ESTATE, "write_state is not supported on partitioned bodies");
+    if (int rc = drain(h)) return rc;
     const bool pjs = h->opt.solver == TETSIM_SOLVER_POLAR_JACOBI;
     const uint32_t n = pjs ? h->pj.nv_owned : h->nh.nv;
     std::vector<float4> p(n), v(n);
@@ -325,7 +311,6 @@ int tetsim_write_state(tetsim_handle h, const float* pos, const float* vel) {
         v[dv] = make_float4(vel[3 * i], vel[3 * i + 1], vel[3 * i + 2], 0.0f);
     }
     if (pjs) {
-        if (h->partitioned && !h->neigh.empty()) return fail(h, TETSIM_ESTATE, "write_state is not supported on partitioned bodies");
         if (n) { HIPCHK(h, hipMemcpy(h->pj.pos_final, p.data(), n * sizeof(float4), hipMemcpyHostToDevice));
                  HIPCHK(h, hipMemcpy(h->pj.pos_pred, p.data(), n * sizeof(float4), hipMemcpyHostToDevice));
                  HIPCHK(h, hipMemcpy(h->pj.vel, v.data(), n * sizeof(float4), hipMemcpyHostToDevice)); }

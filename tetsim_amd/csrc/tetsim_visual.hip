@@ -1,5 +1,5 @@
-// tetsim_visual.hip -- C ABI, part 3 (include/tetsim.h): the embedded visual mesh (skinning, three.js computeVertexNormals) and
-// the grab interface (pin a particle; nearest-particle query on the device).  See body.h.
+// tetsim_visual.hip -- C ABI, part 3 (include/tetsim.h): the embedded visual mesh (skinning, three.js computeVertexNormals; its rows
+// leave through device_io.hip) and the grab interface (pin a particle; nearest-particle query on the device).  See body.h.
 #include "body.h"
 
 using namespace tetsim;
@@ -107,30 +107,14 @@ int tetsim_get_visual_ids(tetsim_handle h, int32_t* out) {
 
 int tetsim_read_visual_mesh(tetsim_handle h, float* positions_out, float* normals_out) {
     if (!h || !positions_out) return fail(h, TETSIM_EINVAL, "null argument");
-    if (!h->vis_attached) return fail(h, TETSIM_ESTATE, "no visual mesh attached (tetsim_set_visual_mesh)");
-    const bool pjs = h->opt.solver == TETSIM_SOLVER_POLAR_JACOBI;
-    if (normals_out && h->skin.nvis && !h->skin.out_nrm) return fail(h, TETSIM_ESTATE, "normals need POLAR_JACOBI and rest normals at tetsim_set_visual_mesh");
-    HIPCHK(h, hipSetDevice(h->opt.device));
-    if (h->partitioned && !h->neigh.empty() && !h->final_ghosts_fresh)
-        // The corners this partition does not own: their end-of-substep positions come from the neighbours, by an EXPLICIT call every rank
-        // makes.  (Round 5 ran the RCCL exchange from inside this read, gated by a per-rank flag: one rank reading twice per frame, or only
-        // some ranks having refreshed, left the others alone inside a collective -- a hang.  A read never communicates.)
-        return fail(h, TETSIM_ESTATE, "the ghost particles' end-of-substep positions are stale: after the frame's last substep every rank calls tetsim_halo_refresh_final "
-                                      "(RCCL; in-process groups: tetsim_group_refresh_final) before it reads the visual mesh of a partition");
-    if (!h->skin.nvis) return 0;   // (a partition that owns no tet with a visual vertex)
-    // Softbody.js arithmetic for the solver that mirrors Softbody.js, the vertex-shader arithmetic for the other
-    if (pjs) { if (int rc = ensure_quats(h)) return rc; }   // (lean-state bodies: the quaternions the skinning shader reads, SoftbodyGPU.js:440)
-    skin_launch(h->stream, h->skin, pjs ? h->pj.pos_final : h->nh.pos, pjs ? h->pj.quat : nullptr, !pjs);
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    const uint32_t n = h->skin.nvis;
-    std::vector<float4> tmp(n);
-    HIPCHK(h, hipMemcpy(tmp.data(), h->skin.out_pos, n * sizeof(float4), hipMemcpyDeviceToHost));
-    for (uint32_t i = 0; i < n; i++) { positions_out[3 * i] = tmp[i].x; positions_out[3 * i + 1] = tmp[i].y; positions_out[3 * i + 2] = tmp[i].z; }
-    if (normals_out) {
-        HIPCHK(h, hipMemcpy(tmp.data(), h->skin.out_nrm, n * sizeof(float4), hipMemcpyDeviceToHost));
-        for (uint32_t i = 0; i < n; i++) { normals_out[3 * i] = tmp[i].x; normals_out[3 * i + 1] = tmp[i].y; normals_out[3 * i + 2] = tmp[i].z; }
-    }
-    return 0;
+    const int32_t fields[2] = {TETSIM_FIELD_VISUAL_POSITIONS, TETSIM_FIELD_VISUAL_NORMALS};
+    float* const out[2] = {positions_out, normals_out};
+    const uint32_t count = normals_out ? 2u : 1u;
+    FieldSrc f[2];
+    std::string why;
+    for (uint32_t k = 0; k < count; k++)
+        if (int rc = resolve_field(h, fields[k], true, &f[k], &why)) return fail(h, rc, why);
+    return read_fields(h, f, out, count);
 }
 
 int tetsim_set_visual_triangles(tetsim_handle h, const int32_t* tri_ids, uint32_t ntri) {
@@ -184,28 +168,14 @@ int tetsim_set_visual_triangles(tetsim_handle h, const int32_t* tri_ids, uint32_
     return 0;
 }
 
-namespace {
-int read_vnrm(tetsim_body* h, float* normals_out) {
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    const uint32_t n = h->skin.nvis;
-    std::vector<float4> tmp(n);
-    if (n) HIPCHK(h, hipMemcpy(tmp.data(), h->skin.out_vnrm, n * sizeof(float4), hipMemcpyDeviceToHost));
-    for (uint32_t i = 0; i < n; i++) { normals_out[3 * i] = tmp[i].x; normals_out[3 * i + 1] = tmp[i].y; normals_out[3 * i + 2] = tmp[i].z; }
-    return 0;
-}
-}  // namespace
-
 int tetsim_read_visual_vertex_normals(tetsim_handle h, float* normals_out) {
     if (!h || !normals_out) return fail(h, TETSIM_EINVAL, "null argument");
-    if (!h->skin.vt_off) return fail(h, TETSIM_ESTATE, "no visual triangles attached (tetsim_set_visual_triangles)");
+    FieldSrc f;
+    std::string why;
+    if (int rc = resolve_field(h, TETSIM_FIELD_VISUAL_VERTEX_NORMALS, true, &f, &why)) return fail(h, rc, why);
     if (h->partitioned) return fail(h, TETSIM_ESTATE, "a partition skins only its own rows, and a triangle's corners may belong to other ranks: put the ranks' skins together "
                                                       "(tetsim_read_visual_mesh + tetsim_get_visual_ids) and call tetsim_visual_vertex_normals_from, or tetsim_group_read_visual_vertex_normals");
-    HIPCHK(h, hipSetDevice(h->opt.device));
-    const bool pjs = h->opt.solver == TETSIM_SOLVER_POLAR_JACOBI;
-    if (pjs) { if (int rc = ensure_quats(h)) return rc; }
-    skin_launch(h->stream, h->skin, pjs ? h->pj.pos_final : h->nh.pos, pjs ? h->pj.quat : nullptr, !pjs);
-    skin_launch_vertex_normals(h->stream, h->skin);
-    return read_vnrm(h, normals_out);
+    return read_fields(h, &f, &normals_out, 1);
 }
 
 // computeVertexNormals (Softbody.js:273) of THIS handle's rows from a complete set of visual positions -- for a partition the ranks'
@@ -214,7 +184,9 @@ int tetsim_read_visual_vertex_normals(tetsim_handle h, float* normals_out) {
 // does, so the partitions' rows equal the unpartitioned body's normals bit for bit.
 int tetsim_visual_vertex_normals_from(tetsim_handle h, const float* all_positions, float* normals_out) {
     if (!h || !all_positions || !normals_out) return fail(h, TETSIM_EINVAL, "null argument");
-    if (!h->skin.vt_off) return fail(h, TETSIM_ESTATE, "no visual triangles attached (tetsim_set_visual_triangles)");
+    FieldSrc f;
+    std::string why;
+    if (int rc = resolve_field(h, TETSIM_FIELD_VISUAL_VERTEX_NORMALS, true, &f, &why)) return fail(h, rc, why);
     HIPCHK(h, hipSetDevice(h->opt.device));
     const uint32_t nrows = h->partitioned ? h->vis_total : h->skin.nvis;
     std::vector<float4> full(nrows);
@@ -224,7 +196,7 @@ int tetsim_visual_vertex_normals_from(tetsim_handle h, const float* all_position
     SkinDev k = h->skin;
     k.tri_pos = h->d_vis_full;
     skin_launch_vertex_normals(h->stream, k);
-    return read_vnrm(h, normals_out);
+    return read_rows(h, &f, &normals_out, 1);   // (the normals of THESE positions: nothing is skinned, so no prepare_fields)
 }
 
 // The partitions of ONE process: every member skins its rows (their ghosts' end-of-substep positions must be fresh:

@@ -52,15 +52,6 @@ __global__ __launch_bounds__(256) void gather16_kernel(const float4* __restrict_
     if (i < n) dst[i] = src[idx[i]];
 }
 
-// strip float4 particles to tightly packed xyz, un-permuting the internal (Morton) numbering: out[3*a..] = src[map[a]]
-__global__ __launch_bounds__(256) void pack_xyz_kernel(const float4* __restrict__ src, const uint32_t* __restrict__ map,
-                                                       float* __restrict__ out, uint32_t n) {
-    const uint32_t a = blockIdx.x * 256u + threadIdx.x;
-    if (a >= n) return;
-    const float4 p = src[map ? map[a] : a];
-    out[3 * a] = p.x; out[3 * a + 1] = p.y; out[3 * a + 2] = p.z;
-}
-
 // startGrab (Softbody.js:279-291): argmin over particles of the squared distance, evaluated in f64 exactly as the
 // JS does (a0*a0 + a1*a1 + a2*a2, left to right; build with -ffp-contract=off), first minimum wins.  One candidate per
 // workgroup; the host finishes over the few hundred candidates in index order.
@@ -130,10 +121,6 @@ __global__ void set_params_kernel(DevParams v, DevParams* dst) { store_params(ds
 void util_launch_set_params(hipStream_t s, DevParams* dst, const DevParams& v) { hipLaunchKernelGGL(set_params_kernel, dim3(1), dim3(1), 0, s, v, dst); }
 void util_launch_delay(hipStream_t s, uint32_t us) {
     if (us) hipLaunchKernelGGL(delay_kernel, dim3(1), dim3(64), 0, s, 100ll * us);
-}
-void util_launch_pack_xyz(hipStream_t s, const float4* src, const uint32_t* map, float* out, uint32_t n) {
-    if (n == 0) return;
-    hipLaunchKernelGGL(pack_xyz_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, src, map, out, n);
 }
 void util_launch_nearest(hipStream_t s, const float4* pos, const uint32_t* map, uint32_t n, double px, double py, double pz,
                          double* best_d2, uint32_t* best_id) {

@@ -9,7 +9,12 @@ frames after warm-up:
       cross-stream event waits of the contract (no substep in flight, no host synchronisation inside the window).
 (a) - (s) and (b) - (s) are what the hand-over itself adds to a frame.  Route (a) uses only entry points that exist without
 tetsim_export_device, so its figure is the baseline whichever build runs it.
-    python tools/device_io_cost.py [--reps 50] [--cells 55]"""
+Then the entry points that move rows, one by one on an idle handle with a visual mesh (the Dragon's own; the lattice's boundary):
+host wall time of a single call through the Python binding, median of --calls calls after warm-up -- the copying and the pinned
+reads, tetsim_write_state of the body's own state, and tetsim_export_device of positions + quaternions followed by
+torch.cuda.synchronize().  Lines that start with "call" are meant to be compared across builds (TETSIM_HIP_LIB selects the library;
+profiles/state_io_cost.txt).
+    python tools/device_io_cost.py [--reps 50] [--cells 55] [--calls 200]"""
 import argparse
 import os
 import sys
@@ -20,7 +25,7 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from tetsim_amd import SoftBodyHIP, library_info, make_lattice  # noqa: E402
+from tetsim_amd import SoftBodyHIP, boundary_surface, library_info, make_lattice  # noqa: E402
 
 PP = dict(gravity=-9.81, friction=1000.0, density=1000.0, devCompliance=1e-5, volCompliance=0.0, worldBounds=[-2.5, -1.0, -2.5, 2.5, 10.0, 2.5])
 G = os.path.join(ROOT, "tests", "golden")
@@ -39,10 +44,27 @@ def median_us(fn, reps):
     return ts[len(ts) // 2], ts[len(ts) // 10], ts[(9 * len(ts)) // 10]
 
 
+def per_call(name, body, calls):
+    pos, vel = body.pos, body.vel
+
+    def export():
+        body.exportTensors(("pos", "quats"))
+        torch.cuda.synchronize()
+
+    rows = [("tetsim_read_positions", lambda: body.pos), ("tetsim_read_positions_pinned", lambda: body.posPinned),
+            ("tetsim_read_quats_pinned", lambda: body.quatsPinned), ("tetsim_read_visual_mesh", body.visualPositions),
+            ("tetsim_write_state", lambda: body.writeState(pos, vel)), ("tetsim_export_device(pos+quats)", export)]
+    for label, fn in rows:
+        body.sync()
+        m, lo, hi = median_us(fn, calls)
+        print("call %-8s %-34s %9.1f us median of %d (10%% %.1f, 90%% %.1f)" % (name.split()[0], label, m, calls, lo, hi), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--cells", type=int, default=55)
+    ap.add_argument("--calls", type=int, default=200)
     a = ap.parse_args()
     print("library source_sha", library_info()["source_sha"], "torch", torch.__version__, flush=True)
     dv = np.fromfile(os.path.join(G, "dragon_verts.f32"), dtype="<f4").reshape(-1, 3)
@@ -95,6 +117,9 @@ def main():
         bytes_moved = n * (16 + 4 + 12)   # a float4 through a 4-byte index, 12 bytes out
         print("  (c) the export alone (gather kernel + the contract's two event waits), device events: %.1f us median (10%% %.1f, 90%% %.1f); "
               "%d bytes moved" % (ev[len(ev) // 2], ev[len(ev) // 10], ev[(9 * len(ev)) // 10], bytes_moved), flush=True)
+        vis = np.fromfile(os.path.join(G, "dragon_vis.f32"), dtype="<f4").reshape(-1, 4) if name == "dragon" else boundary_surface(t, len(v), v)[0]
+        body.setVisualMesh(vis)
+        per_call(name, body, a.calls)
         body.close()
 
 
