@@ -521,6 +521,61 @@ int tetsim_export_device(tetsim_handle h, const TetSimDeviceField *fields, uint3
 int tetsim_import_device(tetsim_handle h, const void *pos, uint64_t pos_stride,
                          const void *vel, uint64_t vel_stride, void *producer_stream);
 
+/* --- device snapshots: the complete state kept in device memory, captured and restored for chosen bodies -------- */
+
+/* tetsim_import_device writes positions and velocities; the per-tet state of a POLAR_JACOBI body (quaternion, carried shape) stays.  The
+ * complete restore used to be tetsim_save_state / tetsim_load_state alone: through host memory, behind a drain of the queues, for every
+ * body of the handle.  A SNAPSHOT is that same state -- every section a checkpoint holds, one device buffer each; not a second copy of
+ * the constant tables -- kept in device memory, and restored for the bodies a device-side mask names: an episode loop over a batch resets
+ * environments 3 and 17 and leaves the other 62 alone, without a host synchronisation.  An ADDITIVE extension of ABI version 5
+ * (TETSIM_ABI_VERSION is unchanged; no existing struct changed): look the symbols up.
+ *
+ *   tetsim_snapshot_create   allocates the buffers (they count into TetSimInfo.device_bytes) and captures the current state of all
+ *                            bodies, on the handle's stream behind every substep enqueued so far.  It may block: it allocates.
+ *   tetsim_snapshot_capture  overwrites the chosen bodies' part of the snapshot with their current state.
+ *   tetsim_snapshot_restore  overwrites the chosen bodies' current state with their part of the snapshot.
+ *   tetsim_snapshot_destroy  waits for the handle's stream and frees the buffers; NULL is harmless.  A snapshot belongs to the handle
+ *                            that created it, and tetsim_destroy frees the snapshots that are left (their pointers die with it).
+ *
+ * body_mask is DEVICE memory of the handle's device: TetSimInfo.num_bodies bytes, nonzero = chosen (the layout of a torch.bool
+ * tensor); NULL = all bodies (a single body: NULL or a one-byte mask).  The host never reads it.
+ *
+ * THE STREAM CONTRACT is that of tetsim_import_device: (1) the handle's stream waits for an event recorded on caller_stream -- the mask
+ * is complete before it is read; (2) ONE kernel moves every section, behind every substep enqueued so far; (3) caller_stream waits for
+ * that kernel, so the caller may overwrite or free the mask in stream order.  Neither capture nor restore synchronises the host.  Only
+ * the first such call of a handle may block: it creates the events (the export's and import's) and, with a mask, uploads the table that
+ * tells every row's body.
+ *
+ * WHAT A RESTORE LEAVES.  With a NULL mask exactly what tetsim_load_state leaves for a blob saved at the moment of the capture, bit for
+ * bit, in every section, the predictions and the recorded dt included.  The fourth float of the rows that carry a call's sequence number
+ * (POLAR_JACOBI predictions and end-of-substep positions, NEOHOOKEAN_GS previous positions) holds 0, as in a checkpoint: the kernel
+ * clears it on the way in and on the way out.  A TETSIM_FLAG_LEAN_STATE body recovers its quaternions on its stream before a capture
+ * (no host wait), so a snapshot's quaternions are the ones its shapes give; recovering them again from the same shape next to the
+ * quaternion stored there gives the same bits, so a masked restore needs no recovery of its own and leaves the "stale" mark as it was.
+ * With a mask the rows of the bodies not chosen are not written at all.
+ *
+ * FOR WHICH dt THE PREDICTIONS HOLD is host-side state (POLAR_JACOBI) and does not depend on the mask's contents.  The snapshot records
+ * it at every capture: a NULL-mask capture records the handle's, a masked one the intersection of its record and the handle's.  A masked
+ * restore leaves the handle with the intersection of its own and the snapshot's; a NULL-mask restore with the snapshot's.  "Valid for
+ * any dt" (no substep yet: the velocities are zero) intersected with X is X; two different dt have nothing in common, and then the next
+ * step predicts every particle afresh, as after tetsim_import_device.  A snapshot taken right after creation, or a loop that keeps dt
+ * fixed, never gets there, and then the bodies not chosen are untouched bit for bit.  In the empty case they get pos + vel * dt from the
+ * re-prediction kernel in place of the prediction they carried (made with the dt of their last substep: the new dt makes every
+ * prediction stale, restore or not).  That kernel and the gather formulation's particle kernel compute the same expression, a product
+ * and a sum (PRECISE: the same bits); the blocked formulation's particle kernels (FAST, the default) use one fused multiply-add where the
+ * re-prediction kernel rounds twice, so there a re-predicted value can differ from the particle kernel's in the last bit.
+ *
+ * Every error is found before anything is enqueued and leaves the state and the snapshot as they were.  TETSIM_EINVAL: a NULL handle,
+ * snapshot or `out`; a snapshot of another handle; a mask that hipPointerGetAttributes does not report as device memory of the handle's
+ * device, or whose allocation holds fewer than num_bodies bytes from that pointer.  TETSIM_ESTATE: any partitioned body.
+ * Out of scope: partitioned bodies; per-body grabs or parameters (a restore does not touch them); snapshots shared between handles; a
+ * snapshot in caller-owned memory. */
+typedef struct tetsim_snapshot_s *tetsim_snapshot;
+int tetsim_snapshot_create(tetsim_handle h, tetsim_snapshot *out);
+int tetsim_snapshot_capture(tetsim_handle h, tetsim_snapshot s, const void *body_mask, void *caller_stream);
+int tetsim_snapshot_restore(tetsim_handle h, tetsim_snapshot s, const void *body_mask, void *caller_stream);
+void tetsim_snapshot_destroy(tetsim_snapshot s);
+
 /* --- measurement ----------------------------------------------------------------------------- */
 
 /* Run n substeps eagerly on the handle's own stream; every POLAR_JACOBI kernel carries its own begin/end HIP

@@ -128,12 +128,14 @@ SYMBOLS = [
     "tetsim_plan_create_deep", "tetsim_plan_layers", "tetsim_plan_neighbour_layer2", "tetsim_plan_neighbour_layer2_ids",
     "tetsim_raycast_visual", "tetsim_start_grab_ray", "tetsim_read_visual_bounding_sphere", "tetsim_prep_boundary_surface",
     "tetsim_export_device", "tetsim_import_device",
+    "tetsim_snapshot_create", "tetsim_snapshot_capture", "tetsim_snapshot_restore", "tetsim_snapshot_destroy",
     "tetsim_mesh_write", "tetsim_mesh_open", "tetsim_mesh_arrays", "tetsim_mesh_close", "tetsim_create_from_file",
 ]
 
 # additive to ABI 5 (looked up by name: a library built before them lacks them and still loads; calling one then raises)
 OPTIONAL_SYMBOLS = ("tetsim_set_colliders", "tetsim_raycast_visual", "tetsim_start_grab_ray", "tetsim_read_visual_bounding_sphere", "tetsim_prep_boundary_surface",
-                    "tetsim_export_device", "tetsim_import_device")
+                    "tetsim_export_device", "tetsim_import_device",
+                    "tetsim_snapshot_create", "tetsim_snapshot_capture", "tetsim_snapshot_restore", "tetsim_snapshot_destroy")
 
 _lib = None
 
@@ -208,6 +210,12 @@ def lib():
     if hasattr(L, "tetsim_export_device"):   # (additive to ABI 5; pointers and streams travel as plain addresses)
         L.tetsim_export_device.argtypes = [H, C.POINTER(TetSimDeviceField), u32, C.c_void_p]
         L.tetsim_import_device.argtypes = [H, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]
+    if hasattr(L, "tetsim_snapshot_create"):   # (additive to ABI 5; the mask and the stream travel as plain addresses)
+        L.tetsim_snapshot_create.argtypes = [H, C.POINTER(H)]
+        L.tetsim_snapshot_capture.argtypes = [H, H, C.c_void_p, C.c_void_p]
+        L.tetsim_snapshot_restore.argtypes = [H, H, C.c_void_p, C.c_void_p]
+        L.tetsim_snapshot_destroy.argtypes = [H]
+        L.tetsim_snapshot_destroy.restype = None
     L.tetsim_profile.argtypes = [H, u32, dbl, PP, C.POINTER(TetSimProfile)]
     L.tetsim_time_kernels.argtypes = [H, u32, dbl, PP, C.POINTER(TetSimProfile)]
     L.tetsim_time_step_n.argtypes = [H, u32, dbl, PP, dp]
@@ -249,7 +257,7 @@ def lib():
             continue
         f = getattr(L, s)
         if s not in ("tetsim_default_options", "tetsim_default_params", "tetsim_destroy", "tetsim_last_error",
-                     "tetsim_plan_destroy"):
+                     "tetsim_plan_destroy", "tetsim_snapshot_destroy"):
             f.restype = C.c_int
     _lib = L
     return L

@@ -36,6 +36,7 @@ UNITS = {
     "tetsim_visual.hip": ["-ffp-contract=off"],
     "tetsim_measure.hip": ["-ffp-contract=off"],
     "device_io.hip": ["-ffp-contract=off"],
+    "snapshot.hip": ["-ffp-contract=off"],
     "tetsim_create.hip": ["-ffp-contract=off"],
     "tetsim_halo.hip": ["-ffp-contract=off"],
     "tetsim_comm.hip": ["-ffp-contract=off"],

@@ -7,6 +7,7 @@
 //   device_io.hip      how rows leave and enter the device arrays, for all of the above: the table of TETSIM_FIELD_* (source, rows, width,
 //                      index map, what must run first, which requests are errors), the one gather kernel and the staging buffer of the
 //                      host reads that use it; and export / import in device memory, ordered against a caller's stream
+//   snapshot.hip       the complete state kept in device memory: capture and restore of chosen bodies (tetsim_snapshot_*), one copy kernel
 //   tetsim_measure.hip measurement: per-kernel profile, kernel timing loops, device copy bandwidth
 //   tetsim_create.hip  construction of the two solvers' device state (host preprocessing -> uploads)
 //   tetsim_halo.hip    multi-GPU: per-substep halo choreography (two queues, flag or event synchronised), in-process group stepping
@@ -140,6 +141,8 @@ struct NeighDev {
 }  // namespace tetsim
 
 using namespace tetsim;  // (private header of the ABI's own translation units; the handle type lives in the global namespace)
+
+struct tetsim_snapshot_s;
 
 struct tetsim_body {
     std::string err;
@@ -277,6 +280,10 @@ struct tetsim_body {
     // created by the first such call; double buffered like the halo events above
     hipEvent_t ev_io[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
     uint32_t io_parity = 0;
+    // tetsim_snapshot_* (snapshot.hip): the snapshots this handle still owns; the body of every row, uploaded by the first masked call --
+    // [bodies + 1] first particle / first tet in device numbering, and for a Neo-Hookean batch the body of every volError entry
+    std::vector<tetsim_snapshot_s*> snapshots;
+    uint32_t *d_snap_first_vert = nullptr, *d_snap_first_elem = nullptr, *d_snap_tet_body = nullptr;
     double* d_best = nullptr; uint32_t* d_best_id = nullptr;  // tetsim_start_grab candidates
     // tetsim_raycast_visual / tetsim_read_visual_bounding_sphere (query_kernels.hip): allocated by the first query, grown on demand
     uint32_t* d_sphere = nullptr;
@@ -394,6 +401,10 @@ int ensure_prediction(tetsim_body* h, double dt);
 const float4* current_positions(tetsim_body* h);   // end-of-substep positions of either solver
 int ensure_quats(tetsim_body* h);                  // lean-state bodies: pj.quat brought up to date on h->stream (behind both queues' work); else nothing
 int ensure_index_map(tetsim_body* h);              // device copy of api2dev (gather / scatter / nearest kernels)
+// what the complete solver state is: the device arrays a checkpoint holds one after the other, and a snapshot one buffer each
+struct StateSection { void* ptr; size_t bytes; };
+void state_sections(tetsim_body* h, std::vector<StateSection>& v);
+bool is_stamped_section(const tetsim_body* h, const void* ptr);   // its float4 rows carry a call's sequence number in w; a saved state holds 0 there
 // ---- rows out of and into the device arrays (device_io.hip)
 int drain(tetsim_body* h);                         // set the device, wait for h->stream, then for h->comm_stream if there is one
 struct FieldSrc {                                  // a TETSIM_FIELD_* on this body: row r = `width` floats of src[mapped ? d_api2dev[r] : r]
@@ -410,6 +421,15 @@ int prepare_fields(tetsim_body* h, const FieldSrc* f, uint32_t count);   // once
 int read_fields(tetsim_body* h, const FieldSrc* f, float* const* out, uint32_t count, bool pinned = false);
 // (on its own for tetsim_visual_vertex_normals_from, which computes the normals of the caller's positions and must not skin first)
 int read_rows(tetsim_body* h, const FieldSrc* f, float* const* out, uint32_t count, bool pinned = false);
+// the stream contract of the device-side calls: the two events of this call, the first recorded on the caller's stream and awaited by
+// the handle's (io_begin); the second recorded on the handle's stream and awaited by the caller's (io_end)
+int io_begin(tetsim_body* h, hipStream_t caller, hipEvent_t** ev);
+int io_end(tetsim_body* h, hipStream_t caller, hipEvent_t* ev);
+int launched(tetsim_body* h);                      // hipGetLastError behind a kernel launch
+// `ptr` is device memory of the handle's device and `need` bytes from it fit the allocation it points into (`misfit`: the message if not)
+int check_device_span(tetsim_body* h, const void* ptr, uint64_t need, const std::string& what, const std::string& misfit);
+extern const char* const kPartitionedIo;           // the refusal of a partitioned body, one text for every device-side call
+void release_snapshots(tetsim_body* h);            // tetsim_destroy: the snapshots that are left (snapshot.hip)
 
 // ---- construction (tetsim_create.hip)
 int create_polar(tetsim_body* h, const float* verts, uint32_t nv, const int32_t* tets, uint32_t nt);

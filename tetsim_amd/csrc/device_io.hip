@@ -54,10 +54,6 @@ __global__ __launch_bounds__(256) void import_kernel(const char* __restrict__ po
     v[dv] = make_float4(vs[0], vs[1], vs[2], 0.0f);
 }
 
-int launched(tetsim_body* h) {
-    const hipError_t le = hipGetLastError();
-    return le == hipSuccess ? 0 : fail(h, TETSIM_EHIP, std::string("kernel launch: ") + hipGetErrorString(le));
-}
 // the gather on h->stream: row r of field k to dst[k] + r * stride[k]; a field without a dst is left out
 int gather(tetsim_body* h, const FieldSrc* s, void* const* dst, const uint64_t* stride, uint32_t count) {
     IoTable t{};
@@ -78,6 +74,19 @@ bool stride_ok(uint64_t stride, uint32_t width) { return stride == 0 || (stride 
 int check_device_rows(tetsim_body* h, const void* ptr, uint64_t stride, uint32_t rows, uint32_t width, const std::string& what) {
     if (!ptr) return fail(h, TETSIM_EINVAL, what + " is null");
     if (reinterpret_cast<uintptr_t>(ptr) % 4) return fail(h, TETSIM_EINVAL, what + " is not 4-byte aligned");
+    return check_device_span(h, ptr, rows ? static_cast<uint64_t>(rows - 1u) * stride + 4ull * width : 0u, what,
+                             std::to_string(rows) + " rows do not fit the allocation it points into");
+}
+
+}  // namespace
+
+const char* const kPartitionedIo = "device export / import of a partitioned body is not supported (its halo stream and its ghosts need a contract of their own)";
+
+int launched(tetsim_body* h) {
+    const hipError_t le = hipGetLastError();
+    return le == hipSuccess ? 0 : fail(h, TETSIM_EHIP, std::string("kernel launch: ") + hipGetErrorString(le));
+}
+int check_device_span(tetsim_body* h, const void* ptr, uint64_t need, const std::string& what, const std::string& misfit) {
     hipPointerAttribute_t at{};
     if (hipPointerGetAttributes(&at, ptr) != hipSuccess) {
         (void)hipGetLastError();
@@ -85,18 +94,14 @@ int check_device_rows(tetsim_body* h, const void* ptr, uint64_t stride, uint32_t
     }
     if (at.type != hipMemoryTypeDevice || at.device != h->opt.device)
         return fail(h, TETSIM_EINVAL, what + " is not device memory of device " + std::to_string(h->opt.device));
-    if (rows == 0) return 0;
+    if (need == 0) return 0;
     hipDeviceptr_t base = nullptr;
     size_t size = 0;
     if (hipMemGetAddressRange(&base, &size, const_cast<void*>(ptr)) != hipSuccess) { (void)hipGetLastError(); return 0; }   // (no extent on record: the type check stands)
     const uint64_t off = reinterpret_cast<uintptr_t>(ptr) - reinterpret_cast<uintptr_t>(base);
-    const uint64_t need = static_cast<uint64_t>(rows - 1u) * stride + 4ull * width;
-    if (off > size || need > size - off) return fail(h, TETSIM_EINVAL, what + ": " + std::to_string(rows) + " rows do not fit the allocation it points into");
+    if (off > size || need > size - off) return fail(h, TETSIM_EINVAL, what + ": " + misfit);
     return 0;
 }
-
-const char* const kPartitionedIo = "device export / import of a partitioned body is not supported (its halo stream and its ghosts need a contract of their own)";
-
 // the two events of this call, the first recorded on the caller's stream and awaited by the handle's
 int io_begin(tetsim_body* h, hipStream_t caller, hipEvent_t** ev) {
     for (auto& pair : h->ev_io)
@@ -112,8 +117,6 @@ int io_end(tetsim_body* h, hipStream_t caller, hipEvent_t* ev) {
     HIPCHK(h, hipStreamWaitEvent(caller, ev[1], 0));
     return 0;
 }
-
-}  // namespace
 
 int drain(tetsim_body* h) {
     HIPCHK(h, hipSetDevice(h->opt.device));

@@ -662,6 +662,7 @@ void tetsim_destroy(tetsim_handle h) {
     drop_flag_graphs(h);
     for (PeerLink& l : h->links) for (void* m : l.ipc) if (m) (void)hipIpcCloseMemHandle(m);
     if (h->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(h->comm);
+    release_snapshots(h);
     for (void* p : h->allocs) (void)hipFree(p);
     if (h->pinned_pos) (void)hipHostFree(h->pinned_pos);
     if (h->pinned_quat) (void)hipHostFree(h->pinned_quat);

@@ -27,6 +27,37 @@ int ensure_index_map(tetsim_body* h) {  // internal Morton numbering -> API numb
     if (rc) return rc;
     return upload(h, h->d_api2dev, h->api2dev);
 }
+// the complete solver state, section by section (a checkpoint: one after the other behind the header; a snapshot: one buffer each)
+void state_sections(tetsim_body* h, std::vector<StateSection>& v) {
+    if (h->opt.solver == TETSIM_SOLVER_POLAR_JACOBI) {
+        const size_t nvl = h->pj.nv_local, nt = h->pj.nt;
+        v.push_back({h->pj.pos_final, nvl * sizeof(float4)});
+        v.push_back({h->pj.vel, nvl * sizeof(float4)});
+        v.push_back({h->pj.pos_pred, nvl * sizeof(float4)});
+        v.push_back({h->pj.quat, nt * sizeof(float4)});
+        if (h->blocked) {
+            if (h->blk.lean_state) {  // three corners (the quaternion section above is brought up to date before a save: ensure_quats)
+                v.push_back({h->blk.rest_a, nt * sizeof(float4)});
+                v.push_back({h->blk.rest_b, nt * sizeof(float4)});
+                v.push_back({h->blk.rest_c1, nt * sizeof(float)});
+            } else if (!h->blk.lean) {  // constant-rest-shape bodies carry no shape state
+                v.push_back({h->blk.rest_a, nt * sizeof(float4)});
+                v.push_back({h->blk.rest_b, nt * sizeof(float4)});
+                v.push_back({h->blk.rest_c, nt * sizeof(float4)});
+            }
+        } else v.push_back({h->pj.elem, 4ull * h->pj.nt_pad * sizeof(float4)});
+    } else {
+        const size_t nv = h->nh.nv;
+        v.push_back({h->nh.pos, nv * sizeof(float4)});
+        v.push_back({h->nh.prev, nv * sizeof(float4)});
+        v.push_back({h->nh.vel, nv * sizeof(float4)});
+        v.push_back({h->nh.vol_err, h->nh.nt * sizeof(double)});
+    }
+}
+bool is_stamped_section(const tetsim_body* h, const void* ptr) {
+    if (h->opt.solver == TETSIM_SOLVER_POLAR_JACOBI) return ptr == h->pj.pos_pred || ptr == h->pj.pos_final;
+    return ptr == h->nh.prev;
+}
 }  // namespace tetsim
 
 extern "C" {
@@ -108,33 +139,6 @@ uint64_t mesh_digest(const tetsim_body* h) {
     return d;
 }
 constexpr uint32_t kStateMagic = 0x54535354u;  // "TSST"
-struct StateSection { void* ptr; size_t bytes; };
-void state_sections(tetsim_body* h, std::vector<StateSection>& v) {
-    if (h->opt.solver == TETSIM_SOLVER_POLAR_JACOBI) {
-        const size_t nvl = h->pj.nv_local, nt = h->pj.nt;
-        v.push_back({h->pj.pos_final, nvl * sizeof(float4)});
-        v.push_back({h->pj.vel, nvl * sizeof(float4)});
-        v.push_back({h->pj.pos_pred, nvl * sizeof(float4)});
-        v.push_back({h->pj.quat, nt * sizeof(float4)});
-        if (h->blocked) {
-            if (h->blk.lean_state) {  // three corners (the quaternion section above is brought up to date before a save: ensure_quats)
-                v.push_back({h->blk.rest_a, nt * sizeof(float4)});
-                v.push_back({h->blk.rest_b, nt * sizeof(float4)});
-                v.push_back({h->blk.rest_c1, nt * sizeof(float)});
-            } else if (!h->blk.lean) {  // constant-rest-shape bodies carry no shape state
-                v.push_back({h->blk.rest_a, nt * sizeof(float4)});
-                v.push_back({h->blk.rest_b, nt * sizeof(float4)});
-                v.push_back({h->blk.rest_c, nt * sizeof(float4)});
-            }
-        } else v.push_back({h->pj.elem, 4ull * h->pj.nt_pad * sizeof(float4)});
-    } else {
-        const size_t nv = h->nh.nv;
-        v.push_back({h->nh.pos, nv * sizeof(float4)});
-        v.push_back({h->nh.prev, nv * sizeof(float4)});
-        v.push_back({h->nh.vel, nv * sizeof(float4)});
-        v.push_back({h->nh.vol_err, h->nh.nt * sizeof(double)});
-    }
-}
 StateHeader state_header(tetsim_body* h) {
     StateHeader hd{};
     hd.magic = kStateMagic; hd.abi = TETSIM_ABI_VERSION;
@@ -208,10 +212,6 @@ int await_peer_deliveries(tetsim_body* h) {
 // next_epoch_block), so a restored stamp could pass for a fresh one in another body: a checkpoint holds 0 there -- no call looks for 0,
 // and the blob does not depend on the path that ran.  Cleared in the blob a save writes AND in what a load uploads (blobs of older
 // builds carry stamps).
-bool is_stamped_section(const tetsim_body* h, const void* ptr) {
-    if (h->opt.solver == TETSIM_SOLVER_POLAR_JACOBI) return ptr == h->pj.pos_pred || ptr == h->pj.pos_final;
-    return ptr == h->nh.prev;
-}
 void clear_stamps(char* section, size_t bytes) {
     for (size_t off = 0; off + sizeof(float4) <= bytes; off += sizeof(float4)) std::memset(section + off + 3 * sizeof(float), 0, sizeof(float));
 }

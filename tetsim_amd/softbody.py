@@ -121,6 +121,27 @@ def _check_rows(torch, t, dev, n, width, name):
         raise ValueError("%s must be a float32 tensor on %s of shape (%d, %d) with contiguous, non-overlapping rows" % (name, dev, n, width))
 
 
+class Snapshot:
+    """The complete solver state of one SoftBodyHIP in device memory (include/tetsim.h: tetsim_snapshot_*): made by body.snapshot(),
+    refreshed by body.capture(snap, ...), written back by body.restore(snap, ...).  close() frees it; the body's close() frees the
+    snapshots that are left."""
+
+    def __init__(self, body, handle):
+        self._body, self._s = body, handle
+
+    def close(self):
+        if self._s is not None and getattr(self._body, "_h", None):
+            self._body._L.tetsim_snapshot_destroy(self._s)
+            self._body._snapshots.remove(self)
+        self._s = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class SoftBodyHIP:
     """Drop-in for `new SoftBody(...)` / `new SoftBodyGPU(...)`; `solver` picks which one is mirrored.
 
@@ -200,6 +221,7 @@ class SoftBodyHIP:
         capi.check(L.tetsim_get_info(self._h, C.byref(self.info)), self._h)
         self._L = L
         self._export_cache = {}   # exportTensors: name -> the tensor it allocated
+        self._snapshots = []      # the live Snapshot objects of this handle
         self.numVisVerts = 0
         if visVerts is not None and len(visVerts):   # Softbody.js:46-47: rows (tetNr, b0, b1, b2); a partition keeps the rows of the tets it owns (visualIds)
             if mesh_file is not None:   # tetsim_create_from_file attached the stored visual mesh already
@@ -231,6 +253,9 @@ class SoftBodyHIP:
     # -- lifecycle ------------------------------------------------------------------------------------
     def close(self):
         if getattr(self, "_h", None):
+            for snap in getattr(self, "_snapshots", ()):   # (tetsim_destroy frees them with the handle)
+                snap._s = None
+            self._snapshots = []
             self._L.tetsim_destroy(self._h)
             self._h = None
 
@@ -398,6 +423,53 @@ class SoftBodyHIP:
         _check_rows(torch, vel, dev, n, 3, "vel")
         capi.check(self._L.tetsim_import_device(self._h, pos.data_ptr(), 4 * pos.stride(0) if n > 1 else 0,
                                                 vel.data_ptr(), 4 * vel.stride(0) if n > 1 else 0, s), self._h)
+
+    # -- device snapshots (include/tetsim.h: tetsim_snapshot_*): the complete state, kept on the device, for chosen bodies ---------
+    def _body_mask(self, torch, dev, bodies):
+        """(address or None, the tensor to keep alive) of `bodies`: None = all; a torch.bool / torch.uint8 tensor of num_bodies on the
+        body's device, used as it is; or a host sequence of truth values, copied to such a tensor (and the copy awaited)."""
+        if bodies is None:
+            return None, None
+        n = self.info.num_bodies
+        if isinstance(bodies, torch.Tensor):
+            if bodies.dtype not in (torch.bool, torch.uint8) or bodies.device != dev or bodies.numel() != n or not bodies.is_contiguous():
+                raise ValueError("bodies must be a contiguous torch.bool / torch.uint8 tensor of %d elements on %s" % (n, dev))
+            return bodies.data_ptr(), bodies
+        host = np.asarray([bool(b) for b in bodies], dtype=np.bool_)
+        if host.size != n:
+            raise ValueError("bodies must name every one of the %d bodies" % n)
+        t = torch.from_numpy(host).to(dev)
+        torch.cuda.current_stream(dev).synchronize()   # (a pageable copy: the mask is complete whatever stream the call names)
+        return t.data_ptr(), t
+
+    def snapshot(self, stream=None):
+        """A Snapshot of the current state of every body, behind the substeps enqueued so far.  Allocates (may block).  `stream` is
+        accepted for symmetry with capture / restore: a fresh snapshot has nothing to order against the caller."""
+        s = C.c_void_p()
+        capi.check(self._L.tetsim_snapshot_create(self._h, C.byref(s)), self._h)
+        snap = Snapshot(self, s)
+        self._snapshots.append(snap)
+        return snap
+
+    def _snapshot_call(self, fn, snap, bodies, stream):
+        import torch
+        dev, s = self._torch_stream(torch, stream)
+        if not isinstance(snap, Snapshot) or snap._s is None:
+            raise ValueError("snap must be a live Snapshot")
+        ptr, keep = self._body_mask(torch, dev, bodies)
+        capi.check(fn(self._h, snap._s, ptr, s), self._h)
+        self._mask_keep = keep   # (a converted host sequence lives until the next call: the kernel may not have read it yet)
+
+    def capture(self, snap, bodies=None, stream=None):
+        """Overwrite the chosen bodies' part of `snap` with their current state.  bodies: None = all, a torch.bool / torch.uint8 tensor
+        [num_bodies] on the body's device (produced on `stream`; reusable on it right after the call), or a host sequence of truth values.
+        No host copy of the state and, with a tensor, no synchronisation; `stream` as in exportTensors."""
+        self._snapshot_call(self._L.tetsim_snapshot_capture, snap, bodies, stream)
+
+    def restore(self, snap, bodies=None, stream=None):
+        """Overwrite the chosen bodies' current state with their part of `snap`: with bodies=None what loadState(saveState() of the capture's
+        moment) leaves, bit for bit; with a mask the other bodies are not written.  Arguments as in capture."""
+        self._snapshot_call(self._L.tetsim_snapshot_restore, snap, bodies, stream)
 
     # -- embedded visual mesh (Softbody.js:259-277 / SoftbodyGPU.js:424-448), skinned on the device ---------------
     def setVisualMesh(self, visVerts, restNormals=None):
