@@ -576,6 +576,62 @@ int tetsim_snapshot_capture(tetsim_handle h, tetsim_snapshot s, const void *body
 int tetsim_snapshot_restore(tetsim_handle h, tetsim_snapshot s, const void *body_mask, void *caller_stream);
 void tetsim_snapshot_destroy(tetsim_snapshot s);
 
+/* --- per-body observations on the device: mass centre, bounds, volume, tet health -------- */
+
+/* What decides which bodies of a batch to reset: where each body is, how fast, whether it left the arena, whether a tet turned inside
+ * out -- one row of TETSIM_OBS_WIDTH doubles per body, in the caller's DEVICE memory, with no host synchronisation (or, through
+ * tetsim_read_body_observations, the same rows on the host).  An ADDITIVE extension of ABI version 5 (TETSIM_ABI_VERSION is unchanged;
+ * no existing struct changed): look the symbols up.
+ *
+ * DEFINITIONS.  All arithmetic is f64 on the stored f32 values (what tetsim_read_positions / _velocities return), every operation rounded
+ * on its own (no fused multiply-add).  dot(u,v) = (u.x*v.x + u.y*v.y) + u.z*v.z; cross(a,b) = (a.y*b.z - a.z*b.y, a.z*b.x - a.x*b.z,
+ * a.x*b.y - a.y*b.x).  Per tet with corners 0..3 in the caller's numbering (a batch: the concatenation), r_k the rest positions given at
+ * creation, x_k / v_k the current positions / velocities:
+ *   V0 = dot(r1-r0, cross(r2-r0, r3-r0)) / 6   computed once on the host; it KEEPS ITS SIGN, as the reference's initPhysics does
+ *   w  = (density * V0) / 4                    a quarter of the tet's mass for each corner.  This is the observation's own f64 definition of
+ *                                              the lumped mass: NOT the f32 invMass that Softbody.js:74-78 accumulates add by add
+ *                                              (tetsim_read_inv_mass), from which it differs in the last bits
+ *   V  = dot(x1-x0, cross(x2-x0, x3-x0)) / 6
+ * and per body, summed over its tets (S = sum):
+ *   MASS = S 4w      COM = (S w * (((x0+x1)+x2)+x3)) / MASS      VCOM = (S w * (((v0+v1)+v2)+v3)) / MASS      (3 doubles each)
+ *   VOLUME = S V     REST_VOLUME = S V0
+ *   MIN_VOLUME_RATIO = min V/V0 over the tets with V0 != 0 (+inf if there is none; a NaN ratio is left out, see NONFINITE)
+ *   INVERTED_TETS    = the number of those tets with V/V0 <= 0
+ *   a body with MASS == 0 (no tets) reports COM = VCOM = 0
+ * and over its particles:
+ *   AABB_MIN / AABB_MAX = the box of the positions (3 doubles each)      MAX_SPEED2 = max (vx*vx + vy*vy) + vz*vz
+ *   NONFINITE = the number of particles with a non-finite component in position or velocity.  Those particles are left out of the box
+ *   and of MAX_SPEED2; the tet sums are NOT filtered, so a NaN shows in COM.  A body without a finite particle reports +inf / -inf as
+ *   its box and 0 as MAX_SPEED2.
+ * Counts are reduced as integers and stored as doubles.  RESERVED is written as 0.
+ *
+ * REPRODUCIBLE AND POSITION INDEPENDENT.  A body's tets and particles are cut into chunks of 256 counted from the body's own first tet /
+ * particle, a chunk is reduced by a fixed tree, and the chunks' partial rows are reduced in index order by the same tree; there are no
+ * floating-point atomics.  So two calls on the same state give the same bits, and a body of a batch gives the bits the same body gives
+ * alone in the same state.  Nothing depends on a stepping path's internal particle or tet order.
+ *
+ * Row b of dst = body b of the handle (tetsim_get_batch_layout), at dst + b * row_stride; only the TETSIM_OBS_WIDTH doubles of a row
+ * are written -- not the padding of a wider row, not a byte outside the rows.  THE STREAM CONTRACT is that of tetsim_export_device:
+ * the handle's stream waits for caller_stream, two launches run behind every substep enqueued so far, caller_stream waits for them.
+ * Only the handle's first observation may block: it builds the constant per-tet table (ids and V0, 24 bytes per tet) on the host and
+ * uploads it with the scratch of the partial rows; all of it counts into TetSimInfo.device_bytes from then on.
+ * tetsim_read_body_observations writes the same rows to host memory, out[num_bodies * TETSIM_OBS_WIDTH], and synchronises.
+ *
+ * Every error is found before anything is enqueued and leaves `dst` as it was.  TETSIM_EINVAL: a NULL handle, dst or out; a dst that
+ * is not 8-byte aligned; a row_stride that is neither 0 (packed: 160) nor a multiple of 8 of at least 160; a dst that
+ * hipPointerGetAttributes does not report as device memory of the handle's device, or whose rows do not fit the allocation it points
+ * into.  TETSIM_ESTATE: a partitioned body.
+ * Out of scope: partitioned bodies; energies; per-tet output fields; a body mask; thresholds or "done" flags (the caller compares). */
+#define TETSIM_OBS_WIDTH 20          /* doubles per body row: 160 bytes */
+enum { TETSIM_OBS_MASS = 0, TETSIM_OBS_COM = 1 /*..3*/, TETSIM_OBS_VCOM = 4 /*..6*/, TETSIM_OBS_VOLUME = 7,
+       TETSIM_OBS_REST_VOLUME = 8, TETSIM_OBS_MIN_VOLUME_RATIO = 9, TETSIM_OBS_INVERTED_TETS = 10,
+       TETSIM_OBS_AABB_MIN = 11 /*..13*/, TETSIM_OBS_AABB_MAX = 14 /*..16*/, TETSIM_OBS_MAX_SPEED2 = 17,
+       TETSIM_OBS_NONFINITE = 18, TETSIM_OBS_RESERVED = 19 /* written as 0 */ };
+/* row b of dst (DEVICE memory, f64) = body b of the handle; ordered against caller_stream exactly as tetsim_export_device */
+int tetsim_observe_bodies_device(tetsim_handle h, void *dst, uint64_t row_stride, void *caller_stream);
+/* the same rows into host memory [num_bodies * TETSIM_OBS_WIDTH]; synchronises */
+int tetsim_read_body_observations(tetsim_handle h, double *out);
+
 /* --- measurement ----------------------------------------------------------------------------- */
 
 /* Run n substeps eagerly on the handle's own stream; every POLAR_JACOBI kernel carries its own begin/end HIP

@@ -21,6 +21,10 @@ COLLIDER_SPHERE, COLLIDER_CAPSULE, COLLIDER_BOX, COLLIDER_PLANE = 0, 1, 2, 3
 MAX_COLLIDERS = 8
 FIELD_POSITIONS, FIELD_VELOCITIES, FIELD_PREV_POSITIONS, FIELD_QUATS, FIELD_VISUAL_POSITIONS, FIELD_VISUAL_NORMALS, FIELD_VISUAL_VERTEX_NORMALS = range(7)
 MAX_EXPORT_FIELDS = 8
+# doubles of a body's row of tetsim_observe_bodies_device, and where each quantity starts in it
+OBS_WIDTH = 20
+(OBS_MASS, OBS_COM, OBS_VCOM, OBS_VOLUME, OBS_REST_VOLUME, OBS_MIN_VOLUME_RATIO, OBS_INVERTED_TETS, OBS_AABB_MIN, OBS_AABB_MAX, OBS_MAX_SPEED2,
+ OBS_NONFINITE, OBS_RESERVED) = 0, 1, 4, 7, 8, 9, 10, 11, 14, 17, 18, 19
 
 
 class TetSimParams(C.Structure):
@@ -129,13 +133,15 @@ SYMBOLS = [
     "tetsim_raycast_visual", "tetsim_start_grab_ray", "tetsim_read_visual_bounding_sphere", "tetsim_prep_boundary_surface",
     "tetsim_export_device", "tetsim_import_device",
     "tetsim_snapshot_create", "tetsim_snapshot_capture", "tetsim_snapshot_restore", "tetsim_snapshot_destroy",
+    "tetsim_observe_bodies_device", "tetsim_read_body_observations",
     "tetsim_mesh_write", "tetsim_mesh_open", "tetsim_mesh_arrays", "tetsim_mesh_close", "tetsim_create_from_file",
 ]
 
 # additive to ABI 5 (looked up by name: a library built before them lacks them and still loads; calling one then raises)
 OPTIONAL_SYMBOLS = ("tetsim_set_colliders", "tetsim_raycast_visual", "tetsim_start_grab_ray", "tetsim_read_visual_bounding_sphere", "tetsim_prep_boundary_surface",
                     "tetsim_export_device", "tetsim_import_device",
-                    "tetsim_snapshot_create", "tetsim_snapshot_capture", "tetsim_snapshot_restore", "tetsim_snapshot_destroy")
+                    "tetsim_snapshot_create", "tetsim_snapshot_capture", "tetsim_snapshot_restore", "tetsim_snapshot_destroy",
+                    "tetsim_observe_bodies_device", "tetsim_read_body_observations")
 
 _lib = None
 
@@ -216,6 +222,9 @@ def lib():
         L.tetsim_snapshot_restore.argtypes = [H, H, C.c_void_p, C.c_void_p]
         L.tetsim_snapshot_destroy.argtypes = [H]
         L.tetsim_snapshot_destroy.restype = None
+    if hasattr(L, "tetsim_observe_bodies_device"):   # (additive to ABI 5; dst and the stream travel as plain addresses)
+        L.tetsim_observe_bodies_device.argtypes = [H, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.tetsim_read_body_observations.argtypes = [H, dp]
     L.tetsim_profile.argtypes = [H, u32, dbl, PP, C.POINTER(TetSimProfile)]
     L.tetsim_time_kernels.argtypes = [H, u32, dbl, PP, C.POINTER(TetSimProfile)]
     L.tetsim_time_step_n.argtypes = [H, u32, dbl, PP, dp]

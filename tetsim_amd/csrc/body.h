@@ -8,6 +8,8 @@
 //                      index map, what must run first, which requests are errors), the one gather kernel and the staging buffer of the
 //                      host reads that use it; and export / import in device memory, ordered against a caller's stream
 //   snapshot.hip       the complete state kept in device memory: capture and restore of chosen bodies (tetsim_snapshot_*), one copy kernel
+//   observe.hip        per-body observations on the device (tetsim_observe_bodies_device): mass centre, volume, tet health, bounds -- two
+//                      launches over a constant per-tet table, a fixed reduction tree
 //   tetsim_measure.hip measurement: per-kernel profile, kernel timing loops, device copy bandwidth
 //   tetsim_create.hip  construction of the two solvers' device state (host preprocessing -> uploads)
 //   tetsim_halo.hip    multi-GPU: per-substep halo choreography (two queues, flag or event synchronised), in-process group stepping
@@ -136,6 +138,17 @@ struct NeighDev {
     int32_t* send_idx = nullptr;   // device, when not contiguous
     float4* send_buf = nullptr;    // device staging, when not contiguous
     std::vector<int32_t> send_global, recv_global, send_local;
+};
+
+// tetsim_observe_bodies_device (observe.hip): the constant tables and the scratch of a handle's observations, made by its first one
+struct ObsDev {
+    const void* tets = nullptr;        // [tets] int4: the four API particle ids
+    const double* v0 = nullptr;        // [tets] signed rest volume
+    const void *chunks = nullptr, *bodies = nullptr;   // per workgroup of the first launch its body and rows; per body its chunks
+    double* partial = nullptr;         // [n_chunks] partial rows
+    double* rows = nullptr;            // [bodies][TETSIM_OBS_WIDTH]: the device side of tetsim_read_body_observations
+    uint32_t n_chunks = 0;
+    bool ready = false;
 };
 
 }  // namespace tetsim
@@ -284,6 +297,7 @@ struct tetsim_body {
     // [bodies + 1] first particle / first tet in device numbering, and for a Neo-Hookean batch the body of every volError entry
     std::vector<tetsim_snapshot_s*> snapshots;
     uint32_t *d_snap_first_vert = nullptr, *d_snap_first_elem = nullptr, *d_snap_tet_body = nullptr;
+    ObsDev obs;                    // tetsim_observe_bodies_device / tetsim_read_body_observations (observe.hip)
     double* d_best = nullptr; uint32_t* d_best_id = nullptr;  // tetsim_start_grab candidates
     // tetsim_raycast_visual / tetsim_read_visual_bounding_sphere (query_kernels.hip): allocated by the first query, grown on demand
     uint32_t* d_sphere = nullptr;

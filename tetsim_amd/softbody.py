@@ -471,6 +471,31 @@ class SoftBodyHIP:
         moment) leaves, bit for bit; with a mask the other bodies are not written.  Arguments as in capture."""
         self._snapshot_call(self._L.tetsim_snapshot_restore, snap, bodies, stream)
 
+    # -- per-body observations (include/tetsim.h: tetsim_observe_bodies_device): one row of _capi.OBS_WIDTH doubles per body -------
+    def observeBodies(self, out=None, stream=None):
+        """torch.float64 [num_bodies, 20] on the handle's device: per body its mass, mass centre and velocity, volume, rest volume, worst
+        volume ratio, inverted tets, box, fastest particle and non-finite particles (columns: _capi.OBS_*; definitions: include/tetsim.h).
+        No host copy and no synchronisation; valid for work enqueued on `stream` (as in exportTensors) after this returns.  The tensor is
+        allocated once and reused by later calls unless `out` supplies it (rows may be strided: anything between them is left alone)."""
+        import torch
+        dev, s = self._torch_stream(torch, stream)
+        n, w = self.info.num_bodies, capi.OBS_WIDTH
+        if out is None:
+            out = self._export_cache.get("observations")
+            if out is None:
+                out = self._export_cache["observations"] = torch.empty((n, w), dtype=torch.float64, device=dev)
+        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or out.device != dev or tuple(out.shape) != (n, w)
+              or out.stride(1) != 1 or (n > 1 and out.stride(0) < w)):
+            raise ValueError("out must be a float64 tensor on %s of shape (%d, %d) with contiguous, non-overlapping rows" % (dev, n, w))
+        capi.check(self._L.tetsim_observe_bodies_device(self._h, out.data_ptr(), 8 * out.stride(0) if n > 1 else 0, s), self._h)
+        return out
+
+    def bodyObservations(self):
+        """observeBodies() on the host: a numpy float64 [num_bodies, 20] array.  Synchronises."""
+        out = np.empty((self.info.num_bodies, capi.OBS_WIDTH), dtype=np.float64)
+        capi.check(self._L.tetsim_read_body_observations(self._h, out.ctypes.data_as(C.POINTER(C.c_double))), self._h)
+        return out
+
     # -- embedded visual mesh (Softbody.js:259-277 / SoftbodyGPU.js:424-448), skinned on the device ---------------
     def setVisualMesh(self, visVerts, restNormals=None):
         vv = _f32(visVerts).reshape(-1)
