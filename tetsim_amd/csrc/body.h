@@ -2,11 +2,11 @@
 //
 //   tetsim_api.hip     lifecycle, stepping (streams / graphs)
 //   tetsim_state.hip   the state's host entry points: reads (copying: on the host; pinned: through the gather), tetsim_write_state,
-//                      checkpoint and resume, plan getters
+//                      checkpoint and resume, plan getters; state_sections(), the table of self-describing sections that IS the complete state
 //   tetsim_visual.hip  embedded visual mesh (its set-up and its host reads), grab (pin, nearest-particle query), picking
 //   device_io.hip      how rows leave and enter the device arrays, for all of the above: the table of TETSIM_FIELD_* (source, rows, width,
 //                      index map, what must run first, which requests are errors), the one gather kernel and the staging buffer of the
-//                      host reads that use it; and export / import in device memory, ordered against a caller's stream
+//                      host reads that use it; export / import in device memory; every device-side call's guard and ordering against a caller's stream
 //   snapshot.hip       the complete state kept in device memory: capture and restore of chosen bodies (tetsim_snapshot_*), one copy kernel
 //   observe.hip        per-body observations on the device (tetsim_observe_bodies_device): mass centre, volume, tet health, bounds -- two
 //                      launches over a constant per-tet table, a fixed reduction tree
@@ -333,6 +333,18 @@ struct tetsim_body {
 
 namespace tetsim {
 
+// ---- the bodies of a handle (here alone: batch_first_* are empty for a single body).  is_batch: made by tetsim_create_batch, of however many bodies
+inline bool is_batch(const tetsim_body* h) { return !h->batch_first_vert.empty(); }
+// [bodies + 1] first particle / first tet of every body in the caller's (API) numbering, for a batch and for a single body alike
+inline void body_ranges(const tetsim_body* h, std::vector<uint32_t>* first_vert, std::vector<uint32_t>* first_tet) {
+    *first_vert = h->batch_first_vert; *first_tet = h->batch_first_tet;
+    if (!is_batch(h)) { *first_vert = {0u, h->info.num_particles}; *first_tet = {0u, h->info.num_elems}; }
+}
+inline uint32_t body_of_tet(const tetsim_body* h, uint32_t t) {   // t: a tet in the caller's numbering
+    const std::vector<uint32_t>& first = h->batch_first_tet;
+    return first.empty() ? 0u : static_cast<uint32_t>(std::upper_bound(first.begin(), first.end(), t) - first.begin()) - 1u;
+}
+
 #define HIPCHK(h, call)                                                                                 \
     do {                                                                                                \
         hipError_t e_ = (call);                                                                         \
@@ -415,10 +427,22 @@ int ensure_prediction(tetsim_body* h, double dt);
 const float4* current_positions(tetsim_body* h);   // end-of-substep positions of either solver
 int ensure_quats(tetsim_body* h);                  // lean-state bodies: pj.quat brought up to date on h->stream (behind both queues' work); else nothing
 int ensure_index_map(tetsim_body* h);              // device copy of api2dev (gather / scatter / nearest kernels)
-// what the complete solver state is: the device arrays a checkpoint holds one after the other, and a snapshot one buffer each
-struct StateSection { void* ptr; size_t bytes; };
+// What the complete solver state is: the device arrays a checkpoint holds one after the other, and a snapshot one buffer each.  A
+// section says what it is, so that no reader needs the handle to interpret it; a new state array is added in state_sections() alone.
+enum class StateRows : uint8_t {
+    kParticles,    // particles in device numbering (a body's particles keep their range)
+    kTets,         // tets in the device's own order: blocked tile order, or caller order on the gather path (elem: one section per plane, the rows behind nt are nobody's)
+    kSolveOrder,   // tets by position in the Neo-Hookean solve sequence (vol_err[order[e]]): a coloured or clustered order interleaves the bodies
+};
+struct StateSection {
+    void* ptr;
+    size_t rows; uint32_t row_bytes;   // 16, 8 or 4
+    StateRows of;         // whose rows they are
+    bool stamped;         // the fourth float of a 16-byte row is a call's sequence number and leaves as 0 (tetsim_api.hip: next_epoch_block)
+    bool predictions;     // polar pos_pred: a peer-to-peer body on odd substep parity keeps its ghost tail in ghost_alt
+    size_t bytes() const { return rows * row_bytes; }
+};
 void state_sections(tetsim_body* h, std::vector<StateSection>& v);
-bool is_stamped_section(const tetsim_body* h, const void* ptr);   // its float4 rows carry a call's sequence number in w; a saved state holds 0 there
 // ---- rows out of and into the device arrays (device_io.hip)
 int drain(tetsim_body* h);                         // set the device, wait for h->stream, then for h->comm_stream if there is one
 struct FieldSrc {                                  // a TETSIM_FIELD_* on this body: row r = `width` floats of src[mapped ? d_api2dev[r] : r]
@@ -439,6 +463,15 @@ int read_rows(tetsim_body* h, const FieldSrc* f, float* const* out, uint32_t cou
 // the handle's (io_begin); the second recorded on the handle's stream and awaited by the caller's (io_end)
 int io_begin(tetsim_body* h, hipStream_t caller, hipEvent_t** ev);
 int io_end(tetsim_body* h, hipStream_t caller, hipEvent_t* ev);
+// ... and a call under that contract, behind its argument checks: io_begin, what `enqueue` puts on h->stream (non-zero ends the call), io_end
+template <class F> int on_caller_stream(tetsim_body* h, void* caller_stream, F&& enqueue) {
+    hipStream_t const cs = static_cast<hipStream_t>(caller_stream);
+    hipEvent_t* ev;
+    if (int rc = io_begin(h, cs, &ev)) return rc;
+    if (int rc = enqueue()) return rc;
+    return io_end(h, cs, ev);
+}
+int device_call_guard(tetsim_body* h);             // what every device-side call starts from: not a partitioned body (kPartitionedIo), the handle's device set
 int launched(tetsim_body* h);                      // hipGetLastError behind a kernel launch
 // `ptr` is device memory of the handle's device and `need` bytes from it fit the allocation it points into (`misfit`: the message if not)
 int check_device_span(tetsim_body* h, const void* ptr, uint64_t need, const std::string& what, const std::string& misfit);

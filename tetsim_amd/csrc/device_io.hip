@@ -82,6 +82,11 @@ int check_device_rows(tetsim_body* h, const void* ptr, uint64_t stride, uint32_t
 
 const char* const kPartitionedIo = "device export / import of a partitioned body is not supported (its halo stream and its ghosts need a contract of their own)";
 
+int device_call_guard(tetsim_body* h) {
+    if (h->partitioned) return fail(h, TETSIM_ESTATE, kPartitionedIo);
+    HIPCHK(h, hipSetDevice(h->opt.device));
+    return 0;
+}
 int launched(tetsim_body* h) {
     const hipError_t le = hipGetLastError();
     return le == hipSuccess ? 0 : fail(h, TETSIM_EHIP, std::string("kernel launch: ") + hipGetErrorString(le));
@@ -228,8 +233,7 @@ int tetsim_export_device(tetsim_handle h, const TetSimDeviceField* fields, uint3
     if (!h) return TETSIM_EINVAL;
     if (!fields) return fail(h, TETSIM_EINVAL, "fields is null");
     if (count == 0 || count > TETSIM_MAX_EXPORT_FIELDS) return fail(h, TETSIM_EINVAL, "count must be 1 .. TETSIM_MAX_EXPORT_FIELDS");
-    if (h->partitioned) return fail(h, TETSIM_ESTATE, kPartitionedIo);
-    HIPCHK(h, hipSetDevice(h->opt.device));
+    if (int rc = device_call_guard(h)) return rc;
     FieldSrc src[TETSIM_MAX_EXPORT_FIELDS];
     void* dst[TETSIM_MAX_EXPORT_FIELDS];
     uint64_t stride[TETSIM_MAX_EXPORT_FIELDS];
@@ -244,37 +248,34 @@ int tetsim_export_device(tetsim_handle h, const TetSimDeviceField* fields, uint3
         if (int rc = check_device_rows(h, dst[k] = in.dst, stride[k], src[k].rows, src[k].width, at + "dst")) return rc;
     }
     // ---- every argument is good: from here on only allocation and HIP itself can fail
-    hipStream_t const cs = static_cast<hipStream_t>(consumer_stream);
-    hipEvent_t* ev;
-    if (int rc = io_begin(h, cs, &ev)) return rc;
-    if (int rc = prepare_fields(h, src, count)) return rc;
-    if (int rc = gather(h, src, dst, stride, count)) return rc;
-    return io_end(h, cs, ev);
+    return on_caller_stream(h, consumer_stream, [&]() -> int {
+        if (int rc = prepare_fields(h, src, count)) return rc;
+        return gather(h, src, dst, stride, count);
+    });
 }
 
 int tetsim_import_device(tetsim_handle h, const void* pos, uint64_t pos_stride, const void* vel, uint64_t vel_stride, void* producer_stream) {
     if (!h) return TETSIM_EINVAL;
     if (!pos || !vel) return fail(h, TETSIM_EINVAL, "null argument");
-    if (h->partitioned) return fail(h, TETSIM_ESTATE, kPartitionedIo);
+    if (h->partitioned) return fail(h, TETSIM_ESTATE, kPartitionedIo);   // (device_call_guard's two steps, with the stride check between them as ever)
     if (!stride_ok(pos_stride, 3u) || !stride_ok(vel_stride, 3u)) return fail(h, TETSIM_EINVAL, "a stride must be 0 or a multiple of 4 of at least 12");
     HIPCHK(h, hipSetDevice(h->opt.device));
     const uint32_t n = h->info.owned_particles;
     const uint64_t ps = pos_stride ? pos_stride : 12u, vs = vel_stride ? vel_stride : 12u;
     if (int rc = check_device_rows(h, pos, ps, n, 3u, "pos")) return rc;
     if (int rc = check_device_rows(h, vel, vs, n, 3u, "vel")) return rc;
-    hipStream_t const prod = static_cast<hipStream_t>(producer_stream);
-    hipEvent_t* ev;
-    if (int rc = io_begin(h, prod, &ev)) return rc;
-    const bool pjs = h->opt.solver == TETSIM_SOLVER_POLAR_JACOBI, mapped = pjs && !h->api2dev.empty();
-    if (mapped) { if (int rc = ensure_index_map(h)) return rc; }
-    if (n) hipLaunchKernelGGL(import_kernel, dim3((n + 255u) / 256u), dim3(256), 0, h->stream, static_cast<const char*>(pos), ps, static_cast<const char*>(vel), vs,
-                              mapped ? h->d_api2dev : nullptr, n, pjs ? h->pj.pos_final : h->nh.pos, pjs ? h->pj.pos_pred : nullptr, pjs ? h->pj.vel : h->nh.vel);
-    if (int rc = launched(h)) return rc;
-    if (pjs) {
-        h->pred_any_dt = false;
-        h->dt_pred = std::nanf("");  // forces a re-prediction at the next step
-    }
-    return io_end(h, prod, ev);
+    return on_caller_stream(h, producer_stream, [&]() -> int {
+        const bool pjs = h->opt.solver == TETSIM_SOLVER_POLAR_JACOBI, mapped = pjs && !h->api2dev.empty();
+        if (mapped) { if (int rc = ensure_index_map(h)) return rc; }
+        if (n) hipLaunchKernelGGL(import_kernel, dim3((n + 255u) / 256u), dim3(256), 0, h->stream, static_cast<const char*>(pos), ps, static_cast<const char*>(vel), vs,
+                                  mapped ? h->d_api2dev : nullptr, n, pjs ? h->pj.pos_final : h->nh.pos, pjs ? h->pj.pos_pred : nullptr, pjs ? h->pj.vel : h->nh.vel);
+        if (int rc = launched(h)) return rc;
+        if (pjs) {
+            h->pred_any_dt = false;
+            h->dt_pred = std::nanf("");  // forces a re-prediction at the next step
+        }
+        return 0;
+    });
 }
 
 }  // extern "C"

@@ -2,7 +2,7 @@
 // TETSIM_OBS_WIDTH doubles per body of the handle -- mass, mass centre and its velocity, volume, rest volume, the worst tet's volume ratio,
 // the inverted tets, the box of the particles, the fastest particle, the non-finite particles -- computed on the device from the rows the
 // export hands out (device_io.hip: resolve_field / prepare_fields, gathered through d_api2dev), so no stepping path's tet order matters, and
-// ordered against the caller's stream as the export is (io_begin / io_end).  f64 arithmetic on the stored f32 values, every operation
+// ordered against the caller's stream as the export is (on_caller_stream).  f64 arithmetic on the stored f32 values, every operation
 // rounded on its own (this unit is built with -ffp-contract=off); a fixed reduction tree, no atomics: the same state gives the same bits,
 // and a body of a batch the bits it gives alone.  See body.h.
 #include "body.h"
@@ -207,9 +207,9 @@ double rest_volume(const float* v, const int32_t* t) {
 int ensure_tables(tetsim_body* h) {
     ObsDev& d = h->obs;
     if (d.ready) return 0;
-    const uint32_t nv = static_cast<uint32_t>(h->h_verts.size() / 3), nt = static_cast<uint32_t>(h->h_tets.size() / 4);
-    std::vector<uint32_t> fv = h->batch_first_vert, ft = h->batch_first_tet;
-    if (fv.empty()) { fv = {0u, nv}; ft = {0u, nt}; }
+    const uint32_t nt = h->info.num_elems;
+    std::vector<uint32_t> fv, ft;
+    body_ranges(h, &fv, &ft);
     const uint32_t nb = static_cast<uint32_t>(fv.size() - 1);
     std::vector<int4> ids(nt);
     std::vector<double> v0(nt);
@@ -278,25 +278,19 @@ int tetsim_observe_bodies_device(tetsim_handle h, void* dst, uint64_t row_stride
     if (reinterpret_cast<uintptr_t>(dst) % 8) return fail(h, TETSIM_EINVAL, "dst is not 8-byte aligned");
     constexpr uint64_t row = 8ull * TETSIM_OBS_WIDTH;
     if (row_stride != 0 && (row_stride < row || row_stride % 8)) return fail(h, TETSIM_EINVAL, "row_stride must be 0 or a multiple of 8 of at least 160");
-    if (h->partitioned) return fail(h, TETSIM_ESTATE, kPartitionedIo);
-    HIPCHK(h, hipSetDevice(h->opt.device));
+    if (int rc = device_call_guard(h)) return rc;
     const uint64_t stride = row_stride ? row_stride : row;
     const uint32_t nb = h->info.num_bodies;
     if (int rc = check_device_span(h, dst, static_cast<uint64_t>(nb - 1u) * stride + row, "dst", std::to_string(nb) + " rows do not fit the allocation it points into")) return rc;
     // ---- every argument is good: from here on only allocation and HIP itself can fail
     if (int rc = ensure_tables(h)) return rc;
-    hipStream_t const cs = static_cast<hipStream_t>(caller_stream);
-    hipEvent_t* ev;
-    if (int rc = io_begin(h, cs, &ev)) return rc;
-    if (int rc = enqueue_observation(h, dst, stride)) return rc;
-    return io_end(h, cs, ev);
+    return on_caller_stream(h, caller_stream, [&] { return enqueue_observation(h, dst, stride); });
 }
 
 int tetsim_read_body_observations(tetsim_handle h, double* out) {
     if (!h) return TETSIM_EINVAL;
     if (!out) return fail(h, TETSIM_EINVAL, "out is null");
-    if (h->partitioned) return fail(h, TETSIM_ESTATE, kPartitionedIo);
-    HIPCHK(h, hipSetDevice(h->opt.device));
+    if (int rc = device_call_guard(h)) return rc;
     if (int rc = ensure_tables(h)) return rc;
     if (int rc = enqueue_observation(h, h->obs.rows, 8ull * TETSIM_OBS_WIDTH)) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));

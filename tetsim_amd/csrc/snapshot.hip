@@ -1,7 +1,7 @@
 // snapshot.hip -- C ABI, part 6 (include/tetsim.h): tetsim_snapshot_*.  A snapshot is the handle's complete solver state in device memory -- one
 // buffer per entry of state_sections() (tetsim_state.hip), what a checkpoint keeps on the host -- captured and restored for CHOSEN bodies of a
-// batch by ONE copy kernel on the handle's stream, ordered against the caller's stream as the device export and import are (device_io.hip:
-// io_begin / io_end).  The mask of the chosen bodies is device memory that the host never reads.  See body.h.
+// batch by ONE copy kernel on the handle's stream, ordered against the caller's stream as the device export and import are (body.h:
+// on_caller_stream).  The mask of the chosen bodies is device memory that the host never reads.  See body.h.
 #include "body.h"
 
 using namespace tetsim;
@@ -133,18 +133,16 @@ void intersect_validity(bool* any_dt, float* dt, bool other_any, float other_dt)
 // the body tables of a masked call, uploaded once (the only blocking part of a capture or a restore, with the creation of the events)
 int ensure_body_tables(tetsim_body* h) {
     if (h->d_snap_first_vert) return 0;
-    const bool pjs = h->opt.solver == TETSIM_SOLVER_POLAR_JACOBI;
-    std::vector<uint32_t> fv = h->batch_first_vert, fe = h->batch_first_tet;
-    if (fv.empty()) { fv = {0u, pjs ? h->pj.nv_local : h->nh.nv}; fe = {0u, pjs ? h->pj.nt : h->nh.nt}; }
+    std::vector<uint32_t> fv, fe;
+    body_ranges(h, &fv, &fe);   // (the device's ranges too: no partitioned body gets here, so every particle and tet is local, and a body's particles keep their range)
     uint32_t* d_fe = nullptr;
-    if (pjs) {
+    if (h->opt.solver == TETSIM_SOLVER_POLAR_JACOBI) {
         if (int rc = dev_alloc(h, &d_fe, fe.size())) return rc;
         if (int rc = upload(h, d_fe, fe)) return rc;
         h->d_snap_first_elem = d_fe;
     } else {
         std::vector<uint32_t> body(h->nh.nt);
-        for (uint32_t i = 0; i < h->nh.nt; i++)   // volError entry i belongs to the caller's tet order[i]
-            body[i] = static_cast<uint32_t>(std::upper_bound(fe.begin(), fe.end(), static_cast<uint32_t>(h->order[i])) - fe.begin()) - 1u;
+        for (uint32_t i = 0; i < h->nh.nt; i++) body[i] = body_of_tet(h, static_cast<uint32_t>(h->order[i]));   // volError entry i belongs to the caller's tet order[i]
         if (int rc = dev_alloc(h, &d_fe, body.size())) return rc;
         if (int rc = upload(h, d_fe, body)) return rc;
         h->d_snap_tet_body = d_fe;
@@ -160,7 +158,6 @@ int ensure_body_tables(tetsim_body* h) {
 int launch_snapshot(tetsim_body* h, tetsim_snapshot_s* s, const void* mask, bool restore) {
     std::vector<StateSection> secs;
     state_sections(h, secs);
-    const bool pjs = h->opt.solver == TETSIM_SOLVER_POLAR_JACOBI;
     SnapTable t{};
     t.mask = static_cast<const uint8_t*>(mask);
     t.bodies = h->info.num_bodies;
@@ -175,24 +172,16 @@ int launch_snapshot(tetsim_body* h, tetsim_snapshot_s* s, const void* mask, bool
         blocks += static_cast<uint32_t>((units + kSnapChunk - 1u) / kSnapChunk);
     };
     for (size_t i = 0; i < secs.size(); i++) {
-        char* const live = static_cast<char*>(secs[i].ptr);
-        char* const kept = static_cast<char*>(s->buf[i]);
-        const bool stamped = is_stamped_section(h, secs[i].ptr);
-        if (pjs && secs[i].ptr == h->pj.elem) {   // [4][nt_pad]: four planes of tets in the caller's order, the rows behind nt padding
-            const uint64_t plane = static_cast<uint64_t>(h->pj.nt_pad) * sizeof(float4);
-            for (uint32_t c = 0; c < 4u; c++) add(live + c * plane, kept + c * plane, h->pj.nt_pad, 16u, kRowsByRange, h->d_snap_first_elem, false);
-        } else if (!pjs && secs[i].ptr == h->nh.vol_err) add(live, kept, h->nh.nt, 8u, kRowsByTable, h->d_snap_tet_body, false);
-        else if (pjs && h->blocked && secs[i].ptr == h->blk.rest_c1) add(live, kept, h->pj.nt, 4u, kRowsByRange, h->d_snap_first_elem, false);
-        else {
-            const bool particles = pjs ? (secs[i].ptr == h->pj.pos_final || secs[i].ptr == h->pj.vel || secs[i].ptr == h->pj.pos_pred) : true;
-            add(live, kept, static_cast<uint32_t>(secs[i].bytes / sizeof(float4)), 16u, kRowsByRange, particles ? h->d_snap_first_vert : h->d_snap_first_elem, stamped);
-        }
+        const StateSection& sec = secs[i];
+        const bool by_table = sec.of == StateRows::kSolveOrder;
+        add(static_cast<char*>(sec.ptr), static_cast<char*>(s->buf[i]), static_cast<uint32_t>(sec.rows), sec.row_bytes, by_table ? kRowsByTable : kRowsByRange,
+            by_table ? h->d_snap_tet_body : sec.of == StateRows::kParticles ? h->d_snap_first_vert : h->d_snap_first_elem, sec.stamped);
     }
     if (blocks) hipLaunchKernelGGL(snapshot_kernel, dim3(blocks), dim3(kSnapLanes), 0, h->stream, t);
     return launched(h);
 }
 
-// what capture and restore refuse, before anything is enqueued
+// what capture and restore refuse, before anything is enqueued (device_call_guard's two steps, with the owner's check between them as ever)
 int check_call(tetsim_body* h, tetsim_snapshot_s* s, const void* mask) {
     if (!s) return fail(h, TETSIM_EINVAL, "snapshot is null");
     if (h->partitioned) return fail(h, TETSIM_ESTATE, kPartitionedIo);
@@ -227,23 +216,22 @@ int tetsim_snapshot_create(tetsim_handle h, tetsim_snapshot* out) {
     if (!h) return TETSIM_EINVAL;
     if (!out) return fail(h, TETSIM_EINVAL, "out is null");
     *out = nullptr;
-    if (h->partitioned) return fail(h, TETSIM_ESTATE, kPartitionedIo);
-    HIPCHK(h, hipSetDevice(h->opt.device));
+    if (int rc = device_call_guard(h)) return rc;
     std::vector<StateSection> secs;
     state_sections(h, secs);
     tetsim_snapshot_s* s = new tetsim_snapshot_s;
     s->owner = h;
     for (const StateSection& sec : secs) {
         void* p = nullptr;
-        const size_t bytes = std::max<size_t>(sec.bytes, 16);
+        const size_t bytes = std::max<size_t>(sec.bytes(), 16);
         const hipError_t e = hipMalloc(&p, bytes);
         if (e != hipSuccess) {
             free_snapshot(s);
             return fail(h, TETSIM_ENOMEM, "hipMalloc(" + std::to_string(bytes) + "): " + hipGetErrorString(e));
         }
         s->buf.push_back(p);
-        s->bytes.push_back(sec.bytes);
-        h->info.device_bytes += sec.bytes;
+        s->bytes.push_back(sec.bytes());
+        h->info.device_bytes += sec.bytes();
     }
     int rc = ensure_quats(h);
     if (!rc) rc = launch_snapshot(h, s, nullptr, false);
@@ -259,14 +247,13 @@ int tetsim_snapshot_capture(tetsim_handle h, tetsim_snapshot s, const void* body
     if (int rc = check_call(h, s, body_mask)) return rc;
     // ---- every argument is good: from here on only allocation and HIP itself can fail
     if (body_mask) { if (int rc = ensure_body_tables(h)) return rc; }
-    hipStream_t const cs = static_cast<hipStream_t>(caller_stream);
-    hipEvent_t* ev;
-    if (int rc = io_begin(h, cs, &ev)) return rc;
-    if (int rc = ensure_quats(h)) return rc;   // (a lean-state body: the quaternion section is what its shape section says)
-    if (int rc = launch_snapshot(h, s, body_mask, false)) return rc;
-    if (body_mask) intersect_validity(&s->pred_any_dt, &s->dt_pred, h->pred_any_dt, h->dt_pred);
-    else { s->pred_any_dt = h->pred_any_dt; s->dt_pred = h->dt_pred; }
-    return io_end(h, cs, ev);
+    return on_caller_stream(h, caller_stream, [&]() -> int {
+        if (int rc = ensure_quats(h)) return rc;   // (a lean-state body: the quaternion section is what its shape section says)
+        if (int rc = launch_snapshot(h, s, body_mask, false)) return rc;
+        if (body_mask) intersect_validity(&s->pred_any_dt, &s->dt_pred, h->pred_any_dt, h->dt_pred);
+        else { s->pred_any_dt = h->pred_any_dt; s->dt_pred = h->dt_pred; }
+        return 0;
+    });
 }
 
 int tetsim_snapshot_restore(tetsim_handle h, tetsim_snapshot s, const void* body_mask, void* caller_stream) {
@@ -274,18 +261,17 @@ int tetsim_snapshot_restore(tetsim_handle h, tetsim_snapshot s, const void* body
     if (int rc = check_call(h, s, body_mask)) return rc;
     // ---- every argument is good: from here on only allocation and HIP itself can fail
     if (body_mask) { if (int rc = ensure_body_tables(h)) return rc; }
-    hipStream_t const cs = static_cast<hipStream_t>(caller_stream);
-    hipEvent_t* ev;
-    if (int rc = io_begin(h, cs, &ev)) return rc;
-    if (int rc = launch_snapshot(h, s, body_mask, true)) return rc;
-    if (body_mask) intersect_validity(&h->pred_any_dt, &h->dt_pred, s->pred_any_dt, s->dt_pred);
-    else {
-        // every body comes from the snapshot: what tetsim_load_state leaves for a blob of that moment.  (After a masked restore quat_stale stays
-        // as it was: pjb_recover_quat_kernel gives the same bits when it runs again on the same shape next to the quaternion it stored.)
-        h->pred_any_dt = s->pred_any_dt; h->dt_pred = s->dt_pred;
-        h->quat_stale = false;
-    }
-    return io_end(h, cs, ev);
+    return on_caller_stream(h, caller_stream, [&]() -> int {
+        if (int rc = launch_snapshot(h, s, body_mask, true)) return rc;
+        if (body_mask) intersect_validity(&h->pred_any_dt, &h->dt_pred, s->pred_any_dt, s->dt_pred);
+        else {
+            // every body comes from the snapshot: what tetsim_load_state leaves for a blob of that moment.  (After a masked restore quat_stale stays
+            // as it was: pjb_recover_quat_kernel gives the same bits when it runs again on the same shape next to the quaternion it stored.)
+            h->pred_any_dt = s->pred_any_dt; h->dt_pred = s->dt_pred;
+            h->quat_stale = false;
+        }
+        return 0;
+    });
 }
 
 void tetsim_snapshot_destroy(tetsim_snapshot s) {

@@ -112,7 +112,7 @@ void fill_params(const tetsim_body* h, double dt, const TetSimParams& p, DevPara
 //     earlier substep of the same call from the lane's own fold.  The other particle kernels copy the inverse mass there (`prev = pos`),
 //     which can have any stamp's bits: none of them runs between the call's prediction and its sweep.
 // Stamps restart at every body's creation, so none may travel in a checkpoint: tetsim_save_state and tetsim_load_state write 0 in
-// pos_pred.w, pos_final.w and Neo-Hookean prev.w (tetsim_state.hip: clear_stamps).
+// the sections that state_sections() marks `stamped` (tetsim_state.hip) -- pos_pred.w, pos_final.w and Neo-Hookean prev.w; a snapshot likewise.
 int next_epoch_block(tetsim_body* h) {
     if (h->frame_epoch >= 0xfffe0000u) {
         if (h->partial_b && h->partial_slots) {
@@ -613,13 +613,10 @@ int tetsim_create_batch(const float* const* verts, const uint32_t* nv, const int
 
 int tetsim_get_batch_layout(tetsim_handle h, uint32_t* first_particle, uint32_t* first_elem) {
     if (!h || !first_particle || !first_elem) return fail(h, TETSIM_EINVAL, "null argument");
-    if (h->batch_first_vert.empty()) {
-        first_particle[0] = 0; first_particle[1] = h->info.num_particles;
-        first_elem[0] = 0; first_elem[1] = h->info.num_elems;
-        return 0;
-    }
-    std::copy(h->batch_first_vert.begin(), h->batch_first_vert.end(), first_particle);
-    std::copy(h->batch_first_tet.begin(), h->batch_first_tet.end(), first_elem);
+    std::vector<uint32_t> fv, ft;
+    body_ranges(h, &fv, &ft);
+    std::copy(fv.begin(), fv.end(), first_particle);
+    std::copy(ft.begin(), ft.end(), first_elem);
     return 0;
 }
 

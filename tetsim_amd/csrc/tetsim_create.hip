@@ -48,7 +48,7 @@ int create_polar(tetsim_body* h, const float* verts, uint32_t nv, const int32_t*
     }
     // device numbering: Morton order inside the interior segment [nvb, nvo); boundary (halo sends stay contiguous
     // runs) and ghosts (receive ranges) keep the plan's order.  Batches: every body's segment on its own (as it would be alone).
-    const bool batch = !h->batch_first_vert.empty();
+    const bool batch = is_batch(h);
     const uint32_t bodies = batch ? static_cast<uint32_t>(h->batch_first_vert.size() - 1) : 1u;
     {
         std::vector<float> lv(3ull * nvl);
@@ -348,11 +348,7 @@ int create_polar(tetsim_body* h, const float* verts, uint32_t nv, const int32_t*
                 // group the tiles by body
                 std::vector<std::vector<uint32_t>> groups(bodies);
                 for (uint32_t b = 0; b < nbk; b++) {
-                    uint32_t body = 0;
-                    if (batch) {
-                        const uint32_t lt = static_cast<uint32_t>(B.tet_perm[B.blk_tet_off[b]]);
-                        body = static_cast<uint32_t>(std::upper_bound(h->batch_first_tet.begin(), h->batch_first_tet.end(), lt) - h->batch_first_tet.begin()) - 1u;
-                    }
+                    const uint32_t body = batch ? body_of_tet(h, static_cast<uint32_t>(B.tet_perm[B.blk_tet_off[b]])) : 0u;
                     groups[std::min(body, bodies - 1u)].push_back(b);
                 }
                 const uint32_t budget = per_cu * (cus / 8u) / 2u;   // workgroups of this body per XCD
@@ -520,10 +516,8 @@ int create_neohookean(tetsim_body* h, const float* verts, uint32_t nv, const int
         for (uint32_t i = 0; i < nt; i++) pos_in[i] = static_cast<int32_t>(i);
         // (a batch: inside a level the tets lie body by body -- any order inside a level gives the sequential result, and the
         // single-workgroup launch below walks ITS body's piece of every level)
-        body_of.assign(nt, 0);
-        if (!h->batch_first_tet.empty())
-            for (uint32_t i = 0; i < nt; i++)
-                body_of[i] = static_cast<uint32_t>(std::upper_bound(h->batch_first_tet.begin(), h->batch_first_tet.end(), static_cast<uint32_t>(pre[i])) - h->batch_first_tet.begin()) - 1u;
+        body_of.resize(nt);
+        for (uint32_t i = 0; i < nt; i++) body_of[i] = body_of_tet(h, static_cast<uint32_t>(pre[i]));
         std::stable_sort(pos_in.begin(), pos_in.end(), [&](int32_t a, int32_t b) { return level[a] != level[b] ? level[a] < level[b] : body_of[a] < body_of[b]; });
         h->level_off.assign(nl + 1, 0);
         for (uint32_t i = 0; i < nt; i++) h->level_off[level[i] + 1]++;
@@ -718,8 +712,8 @@ int create_neohookean(tetsim_body* h, const float* verts, uint32_t nv, const int
     // tets -- tools/nh_size_sweep.py)
     static const bool allow_nh_frame = [] { const char* e = lab_env("TETSIM_NH_FRAME"); return !(e && e[0] == '0'); }();
     if (allow_nh_frame && !clustered && nv > 0 && nt > 0 && nl > 0) {
-        std::vector<uint32_t> first_vert = h->batch_first_vert, first_tet = h->batch_first_tet;
-        if (first_vert.empty()) { first_vert = {0u, nv}; first_tet = {0u, nt}; }
+        std::vector<uint32_t> first_vert, first_tet;
+        body_ranges(h, &first_vert, &first_tet);
         const uint32_t bodies = static_cast<uint32_t>(first_vert.size() - 1);
         uint32_t most_v = 0, most_t = 0;
         for (uint32_t b = 0; b < bodies; b++) { most_v = std::max(most_v, first_vert[b + 1] - first_vert[b]); most_t = std::max(most_t, first_tet[b + 1] - first_tet[b]); }

@@ -27,36 +27,34 @@ int ensure_index_map(tetsim_body* h) {  // internal Morton numbering -> API numb
     if (rc) return rc;
     return upload(h, h->d_api2dev, h->api2dev);
 }
-// the complete solver state, section by section (a checkpoint: one after the other behind the header; a snapshot: one buffer each)
+// The complete solver state, section by section (a checkpoint: one after the other behind the header; a snapshot: one buffer each).  THE place
+// where an array joins the state: what it says here is all that save, load, capture and restore know about it (body.h).  `stamped`: the one-launch
+// call (pj_blocked.hip: pjb_call_kernel) leaves its last substep's sequence number in the fourth float of every prediction and end-of-substep position, and its
+// waves of substep s look for s's number there; the Neo-Hookean call (nh_kernels.inc: nh_call_kernel) leaves one in prev.w, where the other paths leave the inverse mass.
 void state_sections(tetsim_body* h, std::vector<StateSection>& v) {
+    constexpr bool kStamped = true, kPredictions = true;
+    auto particles = [&](float4* p, size_t n, bool stamped = false, bool predictions = false) { v.push_back({p, n, 16u, StateRows::kParticles, stamped, predictions}); };
+    auto tets = [&](void* p, size_t n, uint32_t row_bytes = 16u) { v.push_back({p, n, row_bytes, StateRows::kTets, false, false}); };
     if (h->opt.solver == TETSIM_SOLVER_POLAR_JACOBI) {
         const size_t nvl = h->pj.nv_local, nt = h->pj.nt;
-        v.push_back({h->pj.pos_final, nvl * sizeof(float4)});
-        v.push_back({h->pj.vel, nvl * sizeof(float4)});
-        v.push_back({h->pj.pos_pred, nvl * sizeof(float4)});
-        v.push_back({h->pj.quat, nt * sizeof(float4)});
+        particles(h->pj.pos_final, nvl, kStamped);
+        particles(h->pj.vel, nvl);
+        particles(h->pj.pos_pred, nvl, kStamped, kPredictions);
+        tets(h->pj.quat, nt);
         if (h->blocked) {
-            if (h->blk.lean_state) {  // three corners (the quaternion section above is brought up to date before a save: ensure_quats)
-                v.push_back({h->blk.rest_a, nt * sizeof(float4)});
-                v.push_back({h->blk.rest_b, nt * sizeof(float4)});
-                v.push_back({h->blk.rest_c1, nt * sizeof(float)});
-            } else if (!h->blk.lean) {  // constant-rest-shape bodies carry no shape state
-                v.push_back({h->blk.rest_a, nt * sizeof(float4)});
-                v.push_back({h->blk.rest_b, nt * sizeof(float4)});
-                v.push_back({h->blk.rest_c, nt * sizeof(float4)});
-            }
-        } else v.push_back({h->pj.elem, 4ull * h->pj.nt_pad * sizeof(float4)});
+            if (!h->blk.lean_state && h->blk.lean) return;  // constant-rest-shape bodies carry no shape state
+            tets(h->blk.rest_a, nt);
+            tets(h->blk.rest_b, nt);
+            // lean state: three corners (the quaternion section above is brought up to date before a save: ensure_quats)
+            if (h->blk.lean_state) tets(h->blk.rest_c1, nt, 4u); else tets(h->blk.rest_c, nt);
+        } else for (uint32_t c = 0; c < 4u; c++) tets(h->pj.elem + static_cast<size_t>(c) * h->pj.nt_pad, h->pj.nt_pad);   // [4][nt_pad], adjacent and in order
     } else {
         const size_t nv = h->nh.nv;
-        v.push_back({h->nh.pos, nv * sizeof(float4)});
-        v.push_back({h->nh.prev, nv * sizeof(float4)});
-        v.push_back({h->nh.vel, nv * sizeof(float4)});
-        v.push_back({h->nh.vol_err, h->nh.nt * sizeof(double)});
+        particles(h->nh.pos, nv);
+        particles(h->nh.prev, nv, kStamped);
+        particles(h->nh.vel, nv);
+        v.push_back({h->nh.vol_err, h->nh.nt, 8u, StateRows::kSolveOrder, false, false});
     }
-}
-bool is_stamped_section(const tetsim_body* h, const void* ptr) {
-    if (h->opt.solver == TETSIM_SOLVER_POLAR_JACOBI) return ptr == h->pj.pos_pred || ptr == h->pj.pos_final;
-    return ptr == h->nh.prev;
 }
 }  // namespace tetsim
 
@@ -148,7 +146,7 @@ StateHeader state_header(tetsim_body* h) {
     hd.pred_any_dt = h->pred_any_dt ? 1u : 0u; hd.dt_pred = h->dt_pred;
     std::vector<StateSection> secs;
     state_sections(h, secs);
-    for (const StateSection& sec : secs) hd.payload += sec.bytes;
+    for (const StateSection& sec : secs) hd.payload += sec.bytes();
     hd.mesh_digest = mesh_digest(h);
     return hd;
 }
@@ -206,12 +204,10 @@ int await_peer_deliveries(tetsim_body* h) {
         std::this_thread::sleep_for(std::chrono::microseconds(50));
     }
 }
-// The one-launch call (pj_blocked.hip: pjb_call_kernel) leaves its last substep's sequence number in the fourth float of every prediction
-// and end-of-substep position, and its waves of substep s look for s's number there; the Neo-Hookean call (nh_kernels.inc: nh_call_kernel)
-// leaves one in prev.w, where the other Neo-Hookean paths leave the inverse mass.  Numbers restart with every body (tetsim_api.hip:
-// next_epoch_block), so a restored stamp could pass for a fresh one in another body: a checkpoint holds 0 there -- no call looks for 0,
-// and the blob does not depend on the path that ran.  Cleared in the blob a save writes AND in what a load uploads (blobs of older
-// builds carry stamps).
+// The sections whose fourth float is a call's sequence number say so themselves (StateSection::stamped, set in state_sections above).
+// Numbers restart with every body (tetsim_api.hip: next_epoch_block), so a restored stamp could pass for a fresh one in another body: a
+// checkpoint holds 0 there -- no call looks for 0, and the blob does not depend on the path that ran.  Cleared in the blob a save writes
+// AND in what a load uploads (blobs of older builds carry stamps).
 void clear_stamps(char* section, size_t bytes) {
     for (size_t off = 0; off + sizeof(float4) <= bytes; off += sizeof(float4)) std::memset(section + off + 3 * sizeof(float), 0, sizeof(float));
 }
@@ -243,10 +239,10 @@ int tetsim_save_state(tetsim_handle h, void* blob, uint64_t bytes) {
     std::vector<StateSection> secs;
     state_sections(h, secs);
     for (const StateSection& sec : secs) {
-        if (sec.bytes) HIPCHK(h, hipMemcpy(out, sec.ptr, sec.bytes, hipMemcpyDeviceToHost));
-        if (sec.ptr == h->pj.pos_pred && h->opt.solver == TETSIM_SOLVER_POLAR_JACOBI) { if (int rc = patch_blob_ghosts(h, out)) return rc; }
-        if (is_stamped_section(h, sec.ptr)) clear_stamps(out, sec.bytes);
-        out += sec.bytes;
+        if (sec.bytes()) HIPCHK(h, hipMemcpy(out, sec.ptr, sec.bytes(), hipMemcpyDeviceToHost));
+        if (sec.predictions) { if (int rc = patch_blob_ghosts(h, out)) return rc; }
+        if (sec.stamped) clear_stamps(out, sec.bytes());
+        out += sec.bytes();
     }
     return 0;
 }
@@ -271,13 +267,13 @@ int tetsim_load_state(tetsim_handle h, const void* blob, uint64_t bytes) {
     std::vector<char> scrubbed;
     for (const StateSection& sec : secs) {
         const char* from = src;
-        if (sec.bytes && is_stamped_section(h, sec.ptr)) {
-            scrubbed.assign(src, src + sec.bytes);
-            clear_stamps(scrubbed.data(), sec.bytes);
+        if (sec.bytes() && sec.stamped) {
+            scrubbed.assign(src, src + sec.bytes());
+            clear_stamps(scrubbed.data(), sec.bytes());
             from = scrubbed.data();
         }
-        if (sec.bytes) HIPCHK(h, hipMemcpy(sec.ptr, from, sec.bytes, hipMemcpyHostToDevice));
-        src += sec.bytes;
+        if (sec.bytes()) HIPCHK(h, hipMemcpy(sec.ptr, from, sec.bytes(), hipMemcpyHostToDevice));
+        src += sec.bytes();
     }
     if (int rc = ghosts_from_tail(h)) return rc;
     h->pred_any_dt = in.pred_any_dt != 0;

@@ -68,8 +68,7 @@ int tetsim_set_visual_mesh(tetsim_handle h, const float* vis_verts, uint32_t nvi
         qidx.push_back(pjs ? tet_pos[el] : 0);
         if (rest_normals) n0.push_back(make_float4(rest_normals[3 * i], rest_normals[3 * i + 1], rest_normals[3 * i + 2], 0.0f));
         kept.push_back(static_cast<int32_t>(i));
-        if (!h->batch_first_tet.empty())   // (ray casts name the body of a hit: the body whose tets carry the row)
-            row_body.push_back(static_cast<int32_t>(std::upper_bound(h->batch_first_tet.begin(), h->batch_first_tet.end(), e) - h->batch_first_tet.begin()) - 1);
+        if (is_batch(h)) row_body.push_back(static_cast<int32_t>(body_of_tet(h, e)));   // (ray casts name the body of a hit: the body whose tets carry the row)
     }
     const uint32_t nk = static_cast<uint32_t>(kept.size());
     SkinDev& k = h->skin;
