@@ -632,6 +632,62 @@ int tetsim_observe_bodies_device(tetsim_handle h, void *dst, uint64_t row_stride
 /* the same rows into host memory [num_bodies * TETSIM_OBS_WIDTH]; synchronises */
 int tetsim_read_body_observations(tetsim_handle h, double *out);
 
+/* --- range sensors on the device: per-body ray casts from device memory ------------------------- */
+
+/* What a depth or touch sensor attached to ONE body of a batch needs: rays, the body each ray belongs to and the hits live in the
+ * caller's DEVICE memory, nothing synchronises the host, and a ray is cast against ITS OWN body -- the bodies of a batch usually
+ * occupy the same region of space, where tetsim_raycast_visual would answer "body 0" for every ray.  An ADDITIVE extension of ABI
+ * version 5 (TETSIM_ABI_VERSION is unchanged; no existing struct changed): look the symbols up.
+ *
+ * DEFINITIONS.  rays: count TetSimRay records, record i at rays + i * ray_stride; hits: count TetSimRayHit records at
+ * hits + i * hit_stride; ray_body: count int32, packed, or NULL.  The arithmetic is that of tetsim_raycast_visual (above), bit for bit.
+ *   ray_body == NULL: record i is exactly what tetsim_raycast_visual returns for ray i, in every field, `body` included.
+ *   ray_body != NULL: ray i is cast against body b = ray_body[i] alone: it sees the triangles whose rows belong to b, in the order of the
+ *     caller's list, and is culled by the bounding sphere of b's visual rows.  The record is what tetsim_raycast_visual returns for body
+ *     b created ALONE in the same state, bit for bit, except that `triangle` is the position in THIS handle's list and body = b.  A
+ *     single body accepts ray_body values of 0.  A body without visual rows or without triangles gives a miss.
+ *   An invalid ray cannot be refused by the host, which never sees it: the device gives it hit = TETSIM_RAY_INVALID, body = triangle =
+ *     -1 and zeros elsewhere, and it disturbs no other ray.  Invalid is what tetsim_raycast_visual refuses -- a non-finite origin or
+ *     direction, a zero direction, a NaN near or far, near < 0, far < near -- and a ray_body value outside [0, num_bodies).
+ * tetsim_visual_bounding_spheres_device: row b of dst = (centre x, y, z, radius) of body b's visual rows, 4 doubles at
+ * dst + b * row_stride: what tetsim_read_visual_bounding_sphere returns for body b alone, bit for bit (the same order-free reduction
+ * on integer keys, one set per body; "bit for bit" holds for finite positions: a NaN component is left out of the box, and which other
+ * rows that takes with it depends, here as in tetsim_read_visual_bounding_sphere, on how the rows fall into waves).  A body without rows
+ * gives (0, 0, 0, 0), as three.js does for an empty Box3.
+ * Only the 48 bytes of a hit record and the 32 bytes of a sphere row are written: not the padding of a wider row, not a byte outside.
+ *
+ * THE KERNEL.  One lane per ray, 256 rays per workgroup; a body's triangles pass through the workgroup's LDS in tiles of 256, each
+ * prepared once (gathered, converted to f64, edges and normal) and then read by every ray of that body.  RAYS GROUPED BY BODY ARE THE
+ * FAST CASE: a workgroup whose rays name several bodies goes through those bodies one after the other (the answers do not depend on
+ * the grouping).  Few rays split the triangle range over more workgroups; the winner is the smallest (distance, triangle) in
+ * lexicographic order at every level, so it depends on no grid shape.  Any count works.
+ *
+ * THE STREAM CONTRACT is that of tetsim_export_device: the handle's stream waits for an event on caller_stream (rays and bodies are
+ * then complete, hits / dst free), the work -- skinning first, as every query, so the answer belongs to the last substep enqueued
+ * before the call -- runs behind every substep enqueued so far, caller_stream waits for it.  No host synchronisation, and no solver
+ * state changes.  Only a handle's first such call may block: it builds the per-body tables on the host (per row its body, the triangle
+ * ids stably sorted by body with the bodies' offsets, per triangle its body) and uploads them with a scratch buffer whose size does
+ * not depend on count; all of it counts into TetSimInfo.device_bytes from then on.
+ *
+ * Every error is found before anything is enqueued and leaves hits / dst as they were.  TETSIM_EINVAL: a NULL handle; NULL rays or
+ * hits with count > 0; a NULL dst; a stride that is neither 0 (packed: 64 / 48 / 32) nor a multiple of 8 of at least that; a pointer
+ * that is not 8-byte aligned (ray_body: 4-byte), that hipPointerGetAttributes does not report as device memory of the handle's
+ * device, or whose rows do not fit the allocation it points into.  TETSIM_ESTATE: no visual mesh; no triangles (the ray call only); a
+ * partitioned body; with ray_body != NULL a triangle whose three rows belong to different bodies (found once on the host; such a
+ * mesh still casts with ray_body == NULL).  count == 0 succeeds and enqueues nothing.
+ * Out of scope: partitioned bodies; an acceleration structure; all hits along a ray; back-side or double-side materials; f32 rays or
+ * hits; rays attached to a moving frame (the caller transforms them, on the device, before the call); gradients; device-resident grab
+ * targets or collider lists; a Node binding (Node has no device tensors). */
+#define TETSIM_RAY_INVALID (-1)   /* TetSimRayHit.hit of a ray the device refused */
+int tetsim_raycast_visual_device(tetsim_handle h,
+        const void *rays,     uint64_t ray_stride,   /* DEVICE: count TetSimRay records (64 B); stride 0 = packed, else a multiple of 8, >= 64 */
+        const void *ray_body,                        /* DEVICE: count int32, or NULL */
+        uint32_t count,
+        void *hits,           uint64_t hit_stride,   /* DEVICE: count TetSimRayHit records (48 B); stride 0 = packed, else a multiple of 8, >= 48 */
+        void *caller_stream);
+/* one row of 4 doubles per body (centre xyz, radius) into DEVICE memory; stride 0 = packed 32, else a multiple of 8, >= 32 */
+int tetsim_visual_bounding_spheres_device(tetsim_handle h, void *dst, uint64_t row_stride, void *caller_stream);
+
 /* --- measurement ----------------------------------------------------------------------------- */
 
 /* Run n substeps eagerly on the handle's own stream; every POLAR_JACOBI kernel carries its own begin/end HIP

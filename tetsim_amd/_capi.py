@@ -10,6 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TETSIM_HIP_LIB") or os.path.join(_HERE, "libtetsim_hip.so")   # same override as the N-API shim
 
 OK, EINVAL, ENODEVICE, EHIP, ENOMEM, ECOMM, ESTATE = range(7)
+RAY_INVALID = -1   # TetSimRayHit.hit of a ray tetsim_raycast_visual_device refused
 SOLVER_POLAR_JACOBI, SOLVER_NEOHOOKEAN_GS = 0, 1
 PRECISE, FAST = 0, 1
 ORDER_ORIGINAL, ORDER_COLOURED, ORDER_CLUSTERED = 0, 1, 2
@@ -134,6 +135,7 @@ SYMBOLS = [
     "tetsim_export_device", "tetsim_import_device",
     "tetsim_snapshot_create", "tetsim_snapshot_capture", "tetsim_snapshot_restore", "tetsim_snapshot_destroy",
     "tetsim_observe_bodies_device", "tetsim_read_body_observations",
+    "tetsim_raycast_visual_device", "tetsim_visual_bounding_spheres_device",
     "tetsim_mesh_write", "tetsim_mesh_open", "tetsim_mesh_arrays", "tetsim_mesh_close", "tetsim_create_from_file",
 ]
 
@@ -141,7 +143,8 @@ SYMBOLS = [
 OPTIONAL_SYMBOLS = ("tetsim_set_colliders", "tetsim_raycast_visual", "tetsim_start_grab_ray", "tetsim_read_visual_bounding_sphere", "tetsim_prep_boundary_surface",
                     "tetsim_export_device", "tetsim_import_device",
                     "tetsim_snapshot_create", "tetsim_snapshot_capture", "tetsim_snapshot_restore", "tetsim_snapshot_destroy",
-                    "tetsim_observe_bodies_device", "tetsim_read_body_observations")
+                    "tetsim_observe_bodies_device", "tetsim_read_body_observations",
+                    "tetsim_raycast_visual_device", "tetsim_visual_bounding_spheres_device")
 
 _lib = None
 
@@ -225,6 +228,9 @@ def lib():
     if hasattr(L, "tetsim_observe_bodies_device"):   # (additive to ABI 5; dst and the stream travel as plain addresses)
         L.tetsim_observe_bodies_device.argtypes = [H, C.c_void_p, C.c_uint64, C.c_void_p]
         L.tetsim_read_body_observations.argtypes = [H, dp]
+    if hasattr(L, "tetsim_raycast_visual_device"):   # (additive to ABI 5; rays, bodies, hits and the stream travel as plain addresses)
+        L.tetsim_raycast_visual_device.argtypes = [H, C.c_void_p, C.c_uint64, C.c_void_p, u32, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.tetsim_visual_bounding_spheres_device.argtypes = [H, C.c_void_p, C.c_uint64, C.c_void_p]
     L.tetsim_profile.argtypes = [H, u32, dbl, PP, C.POINTER(TetSimProfile)]
     L.tetsim_time_kernels.argtypes = [H, u32, dbl, PP, C.POINTER(TetSimProfile)]
     L.tetsim_time_step_n.argtypes = [H, u32, dbl, PP, dp]

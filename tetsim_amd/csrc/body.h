@@ -38,6 +38,7 @@
 #include "../../include/tetsim.h"
 #include "dev_common.h"
 #include "dev_store.h"
+#include "query_device.h"
 #include "host_prep.h"
 #include "mesh_file.h"
 
@@ -304,6 +305,12 @@ struct tetsim_body {
     RayIn* d_rays = nullptr; RayPrep* d_ray_prep = nullptr; RayOut* d_ray_hits = nullptr; RayCand* d_ray_cand = nullptr;
     size_t ray_cap = 0, ray_prep_cap = 0, ray_hits_cap = 0, ray_cand_cap = 0;   // elements in d_rays / d_ray_prep / d_ray_hits / d_ray_cand
     std::vector<int32_t> vis_row_body, tri_body;   // batches: the body behind every visual row / behind every triangle's first vertex
+    // tetsim_raycast_visual_device / tetsim_visual_bounding_spheres_device (query_device.h): the per-body tables of the visual mesh, uploaded
+    // by the first such call (rows: either call; triangles: the ray call), and the candidates of the few-ray launches
+    QueryBodiesDev qbodies;
+    bool qrows_ready = false, qtris_ready = false;
+    bool tri_spans_bodies = false;     // some triangle's three rows belong to different bodies: no per-body cast
+    RayCand* d_cast_cand = nullptr;    // [kCastCandCap]
 
     // NEOHOOKEAN_GS
     NHDev nh;
@@ -475,6 +482,10 @@ int device_call_guard(tetsim_body* h);             // what every device-side cal
 int launched(tetsim_body* h);                      // hipGetLastError behind a kernel launch
 // `ptr` is device memory of the handle's device and `need` bytes from it fit the allocation it points into (`misfit`: the message if not)
 int check_device_span(tetsim_body* h, const void* ptr, uint64_t need, const std::string& what, const std::string& misfit);
+// records of `row_bytes` in the caller's device memory: a stride is 0 (packed) or a multiple of `align` of at least the record; `ptr` is not
+// null, aligned to `align`, device memory of the handle's device, and `rows` records `stride` bytes apart (the resolved stride) fit its allocation
+bool record_stride_ok(uint64_t stride, uint64_t row_bytes, uint32_t align);
+int check_device_records(tetsim_body* h, const void* ptr, uint64_t stride, uint32_t rows, uint64_t row_bytes, uint32_t align, const std::string& what);
 extern const char* const kPartitionedIo;           // the refusal of a partitioned body, one text for every device-side call
 void release_snapshots(tetsim_body* h);            // tetsim_destroy: the snapshots that are left (snapshot.hip)
 

@@ -67,18 +67,21 @@ int gather(tetsim_body* h, const FieldSrc* s, void* const* dst, const uint64_t* 
     return launched(h);
 }
 
-// 0 = packed; else at least the row and a multiple of 4
-bool stride_ok(uint64_t stride, uint32_t width) { return stride == 0 || (stride >= 4ull * width && stride % 4 == 0); }
-
-// `ptr` is device memory of the handle's device, 4-byte aligned, and `rows` rows of `width` floats `stride` bytes apart fit the allocation
+// rows of `width` floats: the general checks below with 4-byte units
+bool stride_ok(uint64_t stride, uint32_t width) { return record_stride_ok(stride, 4ull * width, 4u); }
 int check_device_rows(tetsim_body* h, const void* ptr, uint64_t stride, uint32_t rows, uint32_t width, const std::string& what) {
-    if (!ptr) return fail(h, TETSIM_EINVAL, what + " is null");
-    if (reinterpret_cast<uintptr_t>(ptr) % 4) return fail(h, TETSIM_EINVAL, what + " is not 4-byte aligned");
-    return check_device_span(h, ptr, rows ? static_cast<uint64_t>(rows - 1u) * stride + 4ull * width : 0u, what,
-                             std::to_string(rows) + " rows do not fit the allocation it points into");
+    return check_device_records(h, ptr, stride, rows, 4ull * width, 4u, what);
 }
 
 }  // namespace
+
+bool record_stride_ok(uint64_t stride, uint64_t row_bytes, uint32_t align) { return stride == 0 || (stride >= row_bytes && stride % align == 0); }
+int check_device_records(tetsim_body* h, const void* ptr, uint64_t stride, uint32_t rows, uint64_t row_bytes, uint32_t align, const std::string& what) {
+    if (!ptr) return fail(h, TETSIM_EINVAL, what + " is null");
+    if (reinterpret_cast<uintptr_t>(ptr) % align) return fail(h, TETSIM_EINVAL, what + " is not " + std::to_string(align) + "-byte aligned");
+    return check_device_span(h, ptr, rows ? static_cast<uint64_t>(rows - 1u) * stride + row_bytes : 0u, what,
+                             std::to_string(rows) + " rows do not fit the allocation it points into");
+}
 
 const char* const kPartitionedIo = "device export / import of a partitioned body is not supported (its halo stream and its ghosts need a contract of their own)";
 

@@ -9,6 +9,7 @@
 //   * the sphere: min / max of f32 values and the max of non-negative f64 values are order-free, so integer atomicMax on
 //     order-preserving keys gives the same bits whatever the order.
 #include "dev_common.h"
+#include "query_device.h"
 
 #include <algorithm>
 #include <cmath>
@@ -77,10 +78,7 @@ __device__ inline double dot3(const double* u, const double* v) { return u[0] * 
 
 // Mesh.raycast up to the triangles: the bounding-sphere cull (ray recast by `near`, direction as given), then the ray in the
 // mesh's local space -- the identity leaves the origin alone and Vector3.transformDirection normalises the direction.
-__global__ __launch_bounds__(256) void ray_prep_kernel(const RayIn* __restrict__ rays, uint32_t count, const uint32_t* __restrict__ words, RayPrep* __restrict__ prep) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= count) return;
-    const RayIn r = rays[i];
+__device__ inline RayPrep ray_prepare(const RayIn& r, const uint32_t* __restrict__ words) {
     double c[3];
     sphere_centre(words, c);
     const double radius = sqrt(__longlong_as_double(static_cast<long long>(*reinterpret_cast<const unsigned long long*>(words + 6))));
@@ -113,15 +111,26 @@ __global__ __launch_bounds__(256) void ray_prep_kernel(const RayIn* __restrict__
     RayPrep p;
     for (int k = 0; k < 3; k++) { p.o[k] = r.o[k]; p.d[k] = r.d[k] * s; }
     p.near = r.near; p.far = r.far; p.culled = culled ? 1u : 0u; p.pad = 0u;
-    prep[i] = p;
+    return p;
+}
+
+__global__ __launch_bounds__(256) void ray_prep_kernel(const RayIn* __restrict__ rays, uint32_t count, const uint32_t* __restrict__ words, RayPrep* __restrict__ prep) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= count) return;
+    prep[i] = ray_prepare(rays[i], words);
 }
 
 // Ray.intersectTriangle(a, b, c, backfaceCulling = true) + checkIntersection's distance window.  true: dist / pt are the hit.
-__device__ inline bool tri_hit(const RayPrep& r, const float4 A, const float4 B, const float4 C, double& dist, double pt[3]) {
-    const double a[3] = {static_cast<double>(A.x), static_cast<double>(A.y), static_cast<double>(A.z)};
-    const double e1[3] = {static_cast<double>(B.x) - a[0], static_cast<double>(B.y) - a[1], static_cast<double>(B.z) - a[2]};
-    const double e2[3] = {static_cast<double>(C.x) - a[0], static_cast<double>(C.y) - a[1], static_cast<double>(C.z) - a[2]};
-    const double n[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
+// The triangle's own part (a, e1 = b - a, e2 = c - a, n = e1 x e2) is the same for every ray: TriRec holds it, so that a kernel whose
+// rays share a triangle prepares it once.
+struct TriRec { double a[3], e1[3], e2[3], n[3]; };
+__device__ inline void tri_prepare(const float4 A, const float4 B, const float4 C, TriRec& t) {
+    t.a[0] = static_cast<double>(A.x); t.a[1] = static_cast<double>(A.y); t.a[2] = static_cast<double>(A.z);
+    t.e1[0] = static_cast<double>(B.x) - t.a[0]; t.e1[1] = static_cast<double>(B.y) - t.a[1]; t.e1[2] = static_cast<double>(B.z) - t.a[2];
+    t.e2[0] = static_cast<double>(C.x) - t.a[0]; t.e2[1] = static_cast<double>(C.y) - t.a[1]; t.e2[2] = static_cast<double>(C.z) - t.a[2];
+    t.n[0] = t.e1[1] * t.e2[2] - t.e1[2] * t.e2[1]; t.n[1] = t.e1[2] * t.e2[0] - t.e1[0] * t.e2[2]; t.n[2] = t.e1[0] * t.e2[1] - t.e1[1] * t.e2[0];
+}
+__device__ inline bool tri_test(const RayPrep& r, const double a[3], const double e1[3], const double e2[3], const double n[3], double& dist, double pt[3]) {
     double DdN = dot3(r.d, n);
     if (!(DdN < 0.0)) return false;          // > 0: a back face, culled (front-side material); == 0 (or NaN): no intersection
     DdN = -DdN;                              // sign = -1
@@ -140,6 +149,11 @@ __device__ inline bool tri_hit(const RayPrep& r, const float4 A, const float4 B,
     for (int k = 0; k < 3; k++) { pt[k] = r.o[k] + r.d[k] * t; w[k] = r.o[k] - pt[k]; }   // Ray.at; origin.distanceTo(point)
     dist = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
     return !(dist < r.near || dist > r.far);
+}
+__device__ inline bool tri_hit(const RayPrep& r, const float4 A, const float4 B, const float4 C, double& dist, double pt[3]) {
+    TriRec t;
+    tri_prepare(A, B, C, t);
+    return tri_test(r, t.a, t.e1, t.e2, t.n, dist, pt);
 }
 
 __device__ inline bool better(double d, uint32_t t, double bd, uint32_t bt) { return t != kRayNone && (bt == kRayNone || d < bd || (d == bd && t < bt)); }
@@ -205,6 +219,193 @@ __global__ __launch_bounds__(256) void ray_pick_kernel(QueryDev q, const RayPrep
     hits[ray] = o;
 }
 
+// ---- range sensors (query_device.h): rays, their bodies and the hits in the caller's device memory -----------------------------------
+
+// The two sphere reductions keyed by the row's body: a lane = one row.  Rows of one body usually follow each other, so a wave whose
+// rows share a body reduces first and issues one set of atomics; a mixed wave issues them per lane.  Order-free either way.
+__global__ __launch_bounds__(256) void body_sphere_minmax_kernel(const float4* __restrict__ pos, const uint32_t* __restrict__ row_body, uint32_t n,
+                                                                 uint32_t* __restrict__ words) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x, row = i < n ? i : n - 1u;   // (n > 0; a lane behind the end keeps the last row's body and says nothing)
+    const uint32_t b = row_body[row];
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    if (i < n) {
+        const float4 p = pos[i];
+        const float v[3] = {p.x, p.y, p.z};
+        for (int k = 0; k < 3; k++) { lo[k] = v[k] < lo[k] ? v[k] : lo[k]; hi[k] = v[k] > hi[k] ? v[k] : hi[k]; }
+    }
+    const bool uniform = __all(b == __shfl(b, 0, 64));
+    if (uniform)
+        for (int k = 0; k < 3; k++)
+            for (int m = 32; m > 0; m >>= 1) {
+                const float a = __shfl_xor(lo[k], m, 64), c = __shfl_xor(hi[k], m, 64);
+                lo[k] = a < lo[k] ? a : lo[k];
+                hi[k] = c > hi[k] ? c : hi[k];
+            }
+    // (a wave of one body speaks as a wave of sphere_minmax_kernel does; in a mixed wave every live lane speaks for its row, and a NaN
+    // component's infinities change no key.  With non-finite positions the existing reduction already depends on which rows share a wave.)
+    if (uniform ? ((threadIdx.x & 63u) == 0u && hi[0] >= lo[0]) : i < n) {
+        uint32_t* const w = words + static_cast<size_t>(b) * kSphereWords;
+        for (int k = 0; k < 3; k++) {
+            atomicMax(&w[k], ~key_of(__float_as_uint(lo[k])));
+            atomicMax(&w[3 + k], key_of(__float_as_uint(hi[k])));
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void body_sphere_radius_kernel(const float4* __restrict__ pos, const uint32_t* __restrict__ row_body, uint32_t n,
+                                                                 uint32_t* __restrict__ words) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x, row = i < n ? i : n - 1u;
+    const uint32_t b = row_body[row];
+    uint32_t* const w = words + static_cast<size_t>(b) * kSphereWords;
+    double best = 0.0;
+    if (i < n) {
+        double c[3];
+        sphere_centre(w, c);
+        const float4 p = pos[i];
+        const double dx = c[0] - static_cast<double>(p.x), dy = c[1] - static_cast<double>(p.y), dz = c[2] - static_cast<double>(p.z);
+        const double d2 = dx * dx + dy * dy + dz * dz;
+        best = d2 > best ? d2 : best;
+    }
+    const bool uniform = __all(b == __shfl(b, 0, 64));
+    if (uniform)
+        for (int m = 32; m > 0; m >>= 1) {
+            const double o = __shfl_xor(best, m, 64);
+            best = o > best ? o : best;
+        }
+    if (!uniform || (threadIdx.x & 63u) == 0u)
+        atomicMax(reinterpret_cast<unsigned long long*>(w + 6), static_cast<unsigned long long>(__double_as_longlong(best)));
+}
+
+// a lane = one body: its keys decoded as query_decode_sphere does; only the 32 bytes of the row are written
+__global__ __launch_bounds__(256) void body_spheres_out_kernel(const uint32_t* __restrict__ words, const uint32_t* __restrict__ body_rows, uint32_t bodies,
+                                                               char* __restrict__ dst, uint64_t stride) {
+    const uint32_t b = blockIdx.x * 256u + threadIdx.x;
+    if (b >= bodies) return;
+    double* const o = reinterpret_cast<double*>(dst + static_cast<uint64_t>(b) * stride);
+    if (body_rows[b] == 0u) { o[0] = o[1] = o[2] = o[3] = 0.0; return; }   // three's empty Box3: centre 0, radius 0
+    const uint32_t* const w = words + static_cast<size_t>(b) * kSphereWords;
+    double c[3];
+    sphere_centre(w, c);
+    o[0] = c[0]; o[1] = c[1]; o[2] = c[2];
+    o[3] = sqrt(__longlong_as_double(static_cast<long long>(*reinterpret_cast<const unsigned long long*>(w + 6))));
+}
+
+// A caller's ray: its record, what is wrong with it (ray_defect; a body outside the handle), its body and that body's sphere keys.
+struct CastRay { RayIn r; uint32_t body; bool bad; const uint32_t* words; };
+__device__ inline CastRay cast_load(const QueryDev& q, const QueryBodiesDev& t, const CastIo& io, uint32_t i) {
+    CastRay c;
+    const double* const src = reinterpret_cast<const double*>(io.rays + static_cast<uint64_t>(i) * io.ray_stride);
+    for (int k = 0; k < 3; k++) { c.r.o[k] = src[k]; c.r.d[k] = src[3 + k]; }
+    c.r.near = src[6]; c.r.far = src[7];
+    c.bad = ray_defect(c.r.o, c.r.d, c.r.near, c.r.far) != kRayGood;
+    c.body = 0u;
+    c.words = q.sphere;
+    if (io.ray_body) {
+        const int32_t b = io.ray_body[i];
+        if (b < 0 || static_cast<uint32_t>(b) >= t.bodies) c.bad = true;
+        else { c.body = static_cast<uint32_t>(b); c.words = t.spheres + static_cast<size_t>(b) * kSphereWords; }
+    }
+    return c;
+}
+// the 48 bytes of a hit record as six 8-byte stores (the record is 8-byte aligned, no more)
+__device__ inline void cast_store(const CastIo& io, uint32_t i, int32_t hit, int32_t body, int32_t triangle, double distance, const double pt[3]) {
+    unsigned long long* const o = reinterpret_cast<unsigned long long*>(io.hits + static_cast<uint64_t>(i) * io.hit_stride);
+    o[0] = static_cast<unsigned long long>(static_cast<uint32_t>(hit)) | (static_cast<unsigned long long>(static_cast<uint32_t>(body)) << 32);
+    o[1] = static_cast<unsigned long long>(static_cast<uint32_t>(triangle));
+    o[2] = static_cast<unsigned long long>(__double_as_longlong(distance));
+    for (int k = 0; k < 3; k++) o[3 + k] = static_cast<unsigned long long>(__double_as_longlong(pt[k]));
+}
+__device__ inline void cast_store_result(const QueryBodiesDev& t, const CastIo& io, uint32_t i, const CastRay& c, uint32_t bt, double bd, const double bp[3]) {
+    const double zero[3] = {0.0, 0.0, 0.0};
+    if (c.bad) cast_store(io, i, -1, -1, -1, 0.0, zero);                  // TETSIM_RAY_INVALID
+    else if (bt == kRayNone) cast_store(io, i, 0, -1, -1, 0.0, zero);
+    else cast_store(io, i, 1, io.ray_body ? static_cast<int32_t>(c.body) : t.tri_body ? t.tri_body[bt] : 0, static_cast<int32_t>(bt), bd, bp);
+}
+
+// A lane = one ray, a workgroup = kCastTile rays; grid = (workgroups of rays, parts of the triangle range).  The workgroup goes through
+// the bodies its rays name, lowest first (one body when the rays are grouped by body, the fast case; the whole mesh without ray_body):
+// every lane prepares one triangle of the tile into LDS (tri_prepare: the gathers and the f64 conversions happen once per triangle and
+// workgroup, not once per ray), then the lanes whose ray belongs to that body read the same prepared record one after the other -- an
+// LDS broadcast -- and keep their best by the lexicographic rule.  kSplit: part y takes tiles y, y + gridDim.y, ..; its best goes to
+// cand[y * count + ray] and cast_finish_kernel picks; otherwise the record is written here.
+template <bool kSplit>
+__global__ __launch_bounds__(256) void cast_device_kernel(QueryDev q, QueryBodiesDev t, CastIo io, uint32_t first, RayCand* __restrict__ cand) {
+    __shared__ TriRec s_tri[kCastTile];
+    __shared__ uint32_t s_id[kCastTile];
+    __shared__ uint32_t s_next;
+    const uint32_t i = first + blockIdx.x * kCastTile + threadIdx.x;
+    const bool live = i < io.count && i >= first;   // (i >= first: the last chunk's index may wrap)
+    CastRay c;
+    RayPrep r;
+    bool todo = false;
+    if (live) {
+        c = cast_load(q, t, io, i);
+        if (!c.bad) { r = ray_prepare(c.r, c.words); todo = !r.culled; }
+    }
+    double bd = 0.0, bp[3] = {0.0, 0.0, 0.0};
+    uint32_t bt = kRayNone;
+    for (;;) {
+        if (threadIdx.x == 0u) s_next = kRayNone;
+        __syncthreads();
+        if (todo) atomicMin(&s_next, c.body);
+        __syncthreads();
+        const uint32_t cur = s_next;      // the same for the whole workgroup: every barrier below is reached by all of it
+        if (cur == kRayNone) break;
+        const bool mine = todo && c.body == cur;
+        const uint64_t lo = io.ray_body ? t.tri_first[cur] : 0u, hi = io.ray_body ? t.tri_first[cur + 1u] : q.ntri;
+        for (uint64_t base = lo + static_cast<uint64_t>(blockIdx.y) * kCastTile; base < hi; base += static_cast<uint64_t>(gridDim.y) * kCastTile) {
+            __syncthreads();              // (the tile before this one has been read)
+            const uint64_t k = base + threadIdx.x;
+            if (k < hi) {
+                const uint32_t id = io.ray_body ? t.tri_sorted[k] : static_cast<uint32_t>(k);
+                const int4 v = q.tri[id];
+                tri_prepare(q.pos[v.x], q.pos[v.y], q.pos[v.z], s_tri[threadIdx.x]);
+                s_id[threadIdx.x] = id;
+            }
+            __syncthreads();
+            if (mine) {
+                const uint32_t n = hi - base < kCastTile ? static_cast<uint32_t>(hi - base) : kCastTile;
+                for (uint32_t j = 0; j < n; j++) {
+                    double d, pt[3];
+                    if (tri_test(r, s_tri[j].a, s_tri[j].e1, s_tri[j].e2, s_tri[j].n, d, pt) && better(d, s_id[j], bd, bt)) {
+                        bd = d; bt = s_id[j];
+                        bp[0] = pt[0]; bp[1] = pt[1]; bp[2] = pt[2];
+                    }
+                }
+            }
+        }
+        if (mine) todo = false;
+        __syncthreads();                  // (everybody has read s_next)
+    }
+    if (!live) return;
+    if (kSplit) {
+        RayCand k;
+        k.distance = bd; k.triangle = bt; k.pad = 0u;
+        cand[static_cast<size_t>(blockIdx.y) * io.count + i] = k;
+    } else {
+        cast_store_result(t, io, i, c, bt, bd, bp);
+    }
+}
+
+// split launches: a lane = one ray; the smallest of its parts' candidates, then the record (the winner's point is computed again, by the same code)
+__global__ __launch_bounds__(256) void cast_finish_kernel(QueryDev q, QueryBodiesDev t, CastIo io, const RayCand* __restrict__ cand, uint32_t parts) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= io.count) return;
+    const CastRay c = cast_load(q, t, io, i);
+    double bd = 0.0, bp[3] = {0.0, 0.0, 0.0};
+    uint32_t bt = kRayNone;
+    for (uint32_t p = 0; p < parts; p++) {
+        const RayCand k = cand[static_cast<size_t>(p) * io.count + i];
+        if (better(k.distance, k.triangle, bd, bt)) { bd = k.distance; bt = k.triangle; }
+    }
+    if (!c.bad && bt != kRayNone) {
+        const RayPrep r = ray_prepare(c.r, c.words);
+        const int4 v = q.tri[bt];
+        if (!tri_hit(r, q.pos[v.x], q.pos[v.y], q.pos[v.z], bd, bp)) bt = kRayNone;
+    }
+    cast_store_result(t, io, i, c, bt, bd, bp);
+}
+
 }  // namespace
 
 void query_decode_sphere(const uint32_t words[kSphereWords], double centre[3], double* radius) {
@@ -236,6 +437,42 @@ void query_launch_rays(hipStream_t s, const QueryDev& q, const RayIn* rays, RayP
         hipLaunchKernelGGL(ray_prep_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, rays + first, n, q.sphere, prep + first);
         hipLaunchKernelGGL(ray_triangles_kernel, dim3(per_ray, n), dim3(256), 0, s, q, prep + first, cand + static_cast<size_t>(first) * per_ray);
         hipLaunchKernelGGL(ray_pick_kernel, dim3((n + 3u) / 4u), dim3(256), 0, s, q, prep + first, cand + static_cast<size_t>(first) * per_ray, per_ray, n, hits + first);
+    }
+}
+
+void query_launch_body_spheres(hipStream_t s, const QueryDev& q, const QueryBodiesDev& b) {
+    (void)hipMemsetAsync(b.spheres, 0, static_cast<size_t>(b.bodies) * kSphereWords * sizeof(uint32_t), s);
+    if (q.nvis == 0) return;
+    const uint32_t blocks = (q.nvis + 255u) / 256u;   // (<= 2^24: within a dispatch's 2^32 - 1 work-items)
+    hipLaunchKernelGGL(body_sphere_minmax_kernel, dim3(blocks), dim3(256), 0, s, q.pos, b.row_body, q.nvis, b.spheres);
+    hipLaunchKernelGGL(body_sphere_radius_kernel, dim3(blocks), dim3(256), 0, s, q.pos, b.row_body, q.nvis, b.spheres);
+}
+
+void query_launch_spheres_out(hipStream_t s, const QueryBodiesDev& b, char* dst, uint64_t stride) {
+    hipLaunchKernelGGL(body_spheres_out_kernel, dim3((b.bodies + 255u) / 256u), dim3(256), 0, s, b.spheres, b.body_rows, b.bodies, dst, stride);
+}
+
+// Many rays: the rays themselves fill the chip (one part, the record written by the cast).  Few rays: about four workgroups per compute
+// unit's worth of parts, as far as the largest body has tiles and the candidates fit their buffer.
+uint32_t query_cast_splits(uint32_t tiles, uint32_t count) {
+    const uint32_t groups = (count + kCastTile - 1u) / kCastTile;
+    const uint32_t want = std::max(1024u / std::max(groups, 1u), 1u), fit = std::max(kCastCandCap / std::max(count, 1u), 1u);
+    return std::min(std::min(std::max(tiles, 1u), std::min(want, fit)), 65535u);
+}
+
+void query_launch_cast_device(hipStream_t s, const QueryDev& q, const QueryBodiesDev& b, const CastIo& io, RayCand* cand) {
+    const uint32_t tiles = io.ray_body ? b.max_tiles : (q.ntri + kCastTile - 1u) / kCastTile;
+    const uint32_t parts = query_cast_splits(tiles, io.count);
+    if (parts > 1u) {   // (parts * count <= kCastCandCap: one launch holds every ray)
+        hipLaunchKernelGGL(cast_device_kernel<true>, dim3((io.count + kCastTile - 1u) / kCastTile, parts), dim3(256), 0, s, q, b, io, 0u, cand);
+        hipLaunchKernelGGL(cast_finish_kernel, dim3((io.count + 255u) / 256u), dim3(256), 0, s, q, b, io, cand, parts);
+        return;
+    }
+    // a dispatch holds at most 2^32 - 1 work-items (max_grid_blocks)
+    const uint64_t chunk = static_cast<uint64_t>(max_grid_blocks(256u)) * kCastTile;
+    for (uint64_t first = 0; first < io.count; first += chunk) {
+        const uint64_t n = std::min<uint64_t>(chunk, io.count - first);
+        hipLaunchKernelGGL(cast_device_kernel<false>, dim3(static_cast<uint32_t>((n + kCastTile - 1u) / kCastTile)), dim3(256), 0, s, q, b, io, static_cast<uint32_t>(first), cand);
     }
 }
 

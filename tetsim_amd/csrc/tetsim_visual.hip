@@ -161,7 +161,11 @@ int tetsim_set_visual_triangles(tetsim_handle h, const int32_t* tri_ids, uint32_
     k.ntri = ntri; k.tri = dt; k.vt_tri = dent;
     if (!h->vis_row_body.empty() && !part) {
         h->tri_body.resize(ntri);
-        for (uint32_t t = 0; t < ntri; t++) h->tri_body[t] = h->vis_row_body[tri_ids[3 * t]];
+        for (uint32_t t = 0; t < ntri; t++) {
+            h->tri_body[t] = h->vis_row_body[tri_ids[3 * t]];
+            // (a per-body ray cast sees a body's own triangles: one that spans two bodies belongs to neither, tetsim_raycast_visual_device)
+            if (h->vis_row_body[tri_ids[3 * t + 1]] != h->tri_body[t] || h->vis_row_body[tri_ids[3 * t + 2]] != h->tri_body[t]) h->tri_spans_bodies = true;
+        }
     }
     k.vt_off = doff;
     return 0;
@@ -357,13 +361,10 @@ const char* const kPartitionedQuery = "a partition skins only its own rows, and 
                                       "of a partitioned body are not supported (put the ranks' skins together with tetsim_read_visual_mesh + tetsim_get_visual_ids)";
 
 // the visual positions of the last completed substep in skin.out_pos and their bounding sphere in d_sphere, on h->stream
+int skin_for_query(tetsim_body* h, QueryDev* q);
 int skin_and_sphere(tetsim_body* h, QueryDev* q) {
     HIPCHK(h, hipSetDevice(h->opt.device));
-    const bool pjs = h->opt.solver == TETSIM_SOLVER_POLAR_JACOBI;
-    if (pjs) { if (int rc = ensure_quats(h)) return rc; }
-    if (!h->d_sphere) { if (int rc = dev_alloc(h, &h->d_sphere, kSphereWords)) return rc; }
-    skin_launch(h->stream, h->skin, pjs ? h->pj.pos_final : h->nh.pos, pjs ? h->pj.quat : nullptr, !pjs);
-    q->nvis = h->skin.nvis; q->ntri = h->skin.ntri; q->pos = h->skin.out_pos; q->tri = h->skin.tri; q->sphere = h->d_sphere;
+    if (int rc = skin_for_query(h, q)) return rc;
     query_launch_sphere(h->stream, *q);
     return 0;
 }
@@ -378,16 +379,73 @@ int check_query_state(tetsim_body* h, bool need_triangles) {
 
 int check_rays(tetsim_body* h, const TetSimRay* rays, uint32_t count) {
     for (uint32_t i = 0; i < count; i++) {
+        // (ray_defect, query_device.h: the one definition of an invalid ray; the device's cast reads it too)
+        static const char* const why[] = {"", "non-finite origin or direction", "zero direction", "near or far is NaN", "near < 0", "far < near"};
         const TetSimRay& r = rays[i];
-        const std::string at = "ray " + std::to_string(i) + ": ";
-        bool finite = true;
-        for (int k = 0; k < 3; k++) finite = finite && std::isfinite(r.origin[k]) && std::isfinite(r.direction[k]);
-        if (!finite) return fail(h, TETSIM_EINVAL, at + "non-finite origin or direction");
-        if (r.direction[0] == 0.0 && r.direction[1] == 0.0 && r.direction[2] == 0.0) return fail(h, TETSIM_EINVAL, at + "zero direction");
-        if (r.near != r.near || r.far != r.far) return fail(h, TETSIM_EINVAL, at + "near or far is NaN");
-        if (r.near < 0.0) return fail(h, TETSIM_EINVAL, at + "near < 0");
-        if (r.far < r.near) return fail(h, TETSIM_EINVAL, at + "far < near");
+        if (const int defect = ray_defect(r.origin, r.direction, r.near, r.far)) return fail(h, TETSIM_EINVAL, "ray " + std::to_string(i) + ": " + why[defect]);
     }
+    return 0;
+}
+
+// the per-body tables of the visual rows (query_device.h), built and uploaded once: the body of every row, the rows of every body, the sphere keys
+int ensure_row_tables(tetsim_body* h) {
+    if (h->qrows_ready) return 0;
+    QueryBodiesDev& b = h->qbodies;
+    const uint32_t nb = h->info.num_bodies, nvis = h->skin.nvis;
+    std::vector<uint32_t> row_body(nvis, 0u), body_rows(nb, 0u);
+    for (uint32_t i = 0; i < nvis; i++) {
+        if (!h->vis_row_body.empty()) row_body[i] = static_cast<uint32_t>(h->vis_row_body[i]);
+        body_rows[row_body[i]]++;
+    }
+    uint32_t *d_row_body = nullptr, *d_body_rows = nullptr;
+    if (int rc = dev_alloc(h, &d_row_body, row_body.size())) return rc;
+    if (int rc = dev_alloc(h, &d_body_rows, body_rows.size())) return rc;
+    if (int rc = dev_alloc(h, &b.spheres, static_cast<size_t>(nb) * kSphereWords)) return rc;
+    if (int rc = upload(h, d_row_body, row_body)) return rc;
+    if (int rc = upload(h, d_body_rows, body_rows)) return rc;
+    b.bodies = nb; b.row_body = d_row_body; b.body_rows = d_body_rows;
+    h->qrows_ready = true;
+    return 0;
+}
+
+// ... and of the triangle list: the ids stably sorted by body with the bodies' offsets, the body of every triangle (batches), the candidates
+// of the few-ray launches.  (A triangle whose rows belong to different bodies was found by tetsim_set_visual_triangles: tri_spans_bodies.)
+int ensure_triangle_tables(tetsim_body* h) {
+    if (h->qtris_ready) return 0;
+    if (int rc = ensure_row_tables(h)) return rc;
+    QueryBodiesDev& b = h->qbodies;
+    const uint32_t nb = b.bodies, ntri = h->skin.ntri;
+    auto body_of = [&](uint32_t t) { return h->tri_body.empty() ? 0u : static_cast<uint32_t>(h->tri_body[t]); };
+    std::vector<uint32_t> first(nb + 1u, 0u), sorted(ntri);
+    for (uint32_t t = 0; t < ntri; t++) first[body_of(t) + 1u]++;
+    uint32_t most = 0;
+    for (uint32_t k = 0; k < nb; k++) { most = std::max(most, first[k + 1u]); first[k + 1u] += first[k]; }
+    std::vector<uint32_t> fill(first.begin(), first.end() - 1);
+    for (uint32_t t = 0; t < ntri; t++) sorted[fill[body_of(t)]++] = t;   // (in list order: stable)
+    uint32_t *d_sorted = nullptr, *d_first = nullptr;
+    int32_t* d_tri_body = nullptr;
+    if (int rc = dev_alloc(h, &d_sorted, sorted.size())) return rc;
+    if (int rc = dev_alloc(h, &d_first, first.size())) return rc;
+    if (int rc = dev_alloc(h, &h->d_cast_cand, kCastCandCap)) return rc;
+    if (int rc = upload(h, d_sorted, sorted)) return rc;
+    if (int rc = upload(h, d_first, first)) return rc;
+    if (!h->tri_body.empty()) {
+        if (int rc = dev_alloc(h, &d_tri_body, h->tri_body.size())) return rc;
+        if (int rc = upload(h, d_tri_body, h->tri_body)) return rc;
+    }
+    b.tri_sorted = d_sorted; b.tri_first = d_first; b.tri_body = d_tri_body;
+    b.max_tiles = std::max((most + kCastTile - 1u) / kCastTile, 1u);
+    h->qtris_ready = true;
+    return 0;
+}
+
+// skinning alone: the visual positions of the last enqueued substep in skin.out_pos, on h->stream
+int skin_for_query(tetsim_body* h, QueryDev* q) {
+    const bool pjs = h->opt.solver == TETSIM_SOLVER_POLAR_JACOBI;
+    if (pjs) { if (int rc = ensure_quats(h)) return rc; }
+    if (!h->d_sphere) { if (int rc = dev_alloc(h, &h->d_sphere, kSphereWords)) return rc; }
+    skin_launch(h->stream, h->skin, pjs ? h->pj.pos_final : h->nh.pos, pjs ? h->pj.quat : nullptr, !pjs);
+    q->nvis = h->skin.nvis; q->ntri = h->skin.ntri; q->pos = h->skin.out_pos; q->tri = h->skin.tri; q->sphere = h->d_sphere;
     return 0;
 }
 
@@ -434,6 +492,58 @@ int tetsim_start_grab_ray(tetsim_handle h, const TetSimRay* ray, TetSimRayHit* h
     float xyz[3];
     for (int k = 0; k < 3; k++) xyz[k] = static_cast<float>(ray->origin[k] + ray->direction[k] * hit.distance);
     return tetsim_start_grab(h, xyz, id_out);
+}
+
+// ---- range sensors: the same casts and spheres per body, from and into the caller's device memory (query_device.h) -------------------
+int tetsim_raycast_visual_device(tetsim_handle h, const void* rays, uint64_t ray_stride, const void* ray_body, uint32_t count, void* hits, uint64_t hit_stride,
+                                 void* caller_stream) {
+    if (!h) return TETSIM_EINVAL;
+    if (count && (!rays || !hits)) return fail(h, TETSIM_EINVAL, "null argument");
+    constexpr uint64_t ray_row = sizeof(TetSimRay), hit_row = sizeof(TetSimRayHit);
+    if (!record_stride_ok(ray_stride, ray_row, 8u)) return fail(h, TETSIM_EINVAL, "ray_stride must be 0 or a multiple of 8 of at least 64");
+    if (!record_stride_ok(hit_stride, hit_row, 8u)) return fail(h, TETSIM_EINVAL, "hit_stride must be 0 or a multiple of 8 of at least 48");
+    if (int rc = check_query_state(h, true)) return rc;
+    if (ray_body && h->tri_spans_bodies)
+        return fail(h, TETSIM_ESTATE, "a triangle of the visual mesh has rows of different bodies: it belongs to no body's own surface (cast without ray_body)");
+    if (count == 0) return 0;
+    if (int rc = device_call_guard(h)) return rc;
+    CastIo io;
+    io.rays = static_cast<const char*>(rays); io.ray_stride = ray_stride ? ray_stride : ray_row;
+    io.ray_body = static_cast<const int32_t*>(ray_body);
+    io.hits = static_cast<char*>(hits); io.hit_stride = hit_stride ? hit_stride : hit_row;
+    io.count = count;
+    if (int rc = check_device_records(h, rays, io.ray_stride, count, ray_row, 8u, "rays")) return rc;
+    if (int rc = check_device_records(h, hits, io.hit_stride, count, hit_row, 8u, "hits")) return rc;
+    if (ray_body) { if (int rc = check_device_records(h, ray_body, 4u, count, 4u, 4u, "ray_body")) return rc; }
+    // ---- every argument is good: from here on only allocation and HIP itself can fail
+    if (int rc = ensure_triangle_tables(h)) return rc;
+    return on_caller_stream(h, caller_stream, [&]() -> int {
+        QueryDev q;
+        if (int rc = skin_for_query(h, &q)) return rc;
+        if (ray_body) query_launch_body_spheres(h->stream, q, h->qbodies);
+        else query_launch_sphere(h->stream, q);
+        query_launch_cast_device(h->stream, q, h->qbodies, io, h->d_cast_cand);
+        return launched(h);
+    });
+}
+
+int tetsim_visual_bounding_spheres_device(tetsim_handle h, void* dst, uint64_t row_stride, void* caller_stream) {
+    if (!h) return TETSIM_EINVAL;
+    constexpr uint64_t row = 4ull * sizeof(double);
+    if (!record_stride_ok(row_stride, row, 8u)) return fail(h, TETSIM_EINVAL, "row_stride must be 0 or a multiple of 8 of at least 32");
+    if (!dst) return fail(h, TETSIM_EINVAL, "dst is null");
+    if (int rc = check_query_state(h, false)) return rc;
+    if (int rc = device_call_guard(h)) return rc;
+    const uint64_t stride = row_stride ? row_stride : row;
+    if (int rc = check_device_records(h, dst, stride, h->info.num_bodies, row, 8u, "dst")) return rc;
+    if (int rc = ensure_row_tables(h)) return rc;
+    return on_caller_stream(h, caller_stream, [&]() -> int {
+        QueryDev q;
+        if (int rc = skin_for_query(h, &q)) return rc;
+        query_launch_body_spheres(h->stream, q, h->qbodies);
+        query_launch_spheres_out(h->stream, h->qbodies, static_cast<char*>(dst), stride);
+        return launched(h);
+    });
 }
 
 int tetsim_read_visual_bounding_sphere(tetsim_handle h, double centre[3], double* radius) {

@@ -76,6 +76,14 @@ def make_rays(origins, directions, near=0.0, far=np.inf):
     return rays
 
 
+def rays_tensor(origins, directions, near=0.0, far=np.inf, device="cuda"):
+    """make_rays on a torch device: the float64 [count, 8] tensor raycastVisualDevice reads (columns: origin xyz, direction xyz,
+    near, far -- a TetSimRay per row)."""
+    import torch
+    rays = make_rays(origins, directions, near, far)
+    return torch.from_numpy(rays.view(np.float64).reshape(-1, 8).copy()).to(device)
+
+
 def boundary_surface(tets, nv, verts=None):
     """(visVerts [rows, 4], visTriIds [triangles, 3]) of the tet mesh's boundary, oriented outward, in the reference's visual-mesh
     format -- for bodies without an artist's mesh (include/tetsim.h: tetsim_prep_boundary_surface).  Host only, no GPU needed.
@@ -602,6 +610,54 @@ class SoftBodyHIP:
         c, r = np.empty(3, dtype=np.float64), C.c_double()
         capi.check(self._L.tetsim_read_visual_bounding_sphere(self._h, c.ctypes.data_as(C.POINTER(C.c_double)), C.byref(r)), self._h)
         return c, float(r.value)
+
+    # -- range sensors (include/tetsim.h: tetsim_raycast_visual_device / tetsim_visual_bounding_spheres_device) -----
+    def raycastVisualDevice(self, rays, bodies=None, out=None, stream=None):
+        """raycastVisual from and into device memory, with no host copy and no synchronisation.  rays: torch.float64 [count, 8] on the
+        handle's device (rays_tensor; the rows may be strided); bodies: torch.int32 [count] -- ray i is cast against body bodies[i]
+        ALONE and gets what that body would give on its own, `triangle` counted in this handle's list -- or None: every ray against the
+        whole mesh, exactly raycastVisual.  Returns views onto one torch.uint8 [count, 48] buffer of TetSimRayHit records (`raw`: cached
+        like the export tensors, or `out`, whose rows may be strided): hit, body, triangle (int32 [count]), distance (float64 [count]),
+        point (float64 [count, 3]).  An invalid ray or body gets hit = _capi.RAY_INVALID instead of an exception.  Rays grouped by body
+        are the fast case.  Valid for work enqueued on `stream` (as in exportTensors) after this returns."""
+        import torch
+        dev, s = self._torch_stream(torch, stream)
+        if (not isinstance(rays, torch.Tensor) or rays.dtype != torch.float64 or rays.device != dev or rays.dim() != 2 or rays.shape[1] != 8
+                or (rays.shape[0] and rays.stride(1) != 1) or (rays.shape[0] > 1 and rays.stride(0) < 8)):
+            raise ValueError("rays must be a float64 tensor on %s of shape (count, 8) with contiguous, non-overlapping rows" % (dev,))
+        n = int(rays.shape[0])
+        if bodies is not None and (not isinstance(bodies, torch.Tensor) or bodies.dtype != torch.int32 or bodies.device != dev
+                                   or tuple(bodies.shape) != (n,) or not bodies.is_contiguous()):
+            raise ValueError("bodies must be a contiguous int32 tensor on %s of shape (%d,)" % (dev, n))
+        if out is None:
+            out = self._export_cache.get("rayHits")
+            if out is None or out.shape[0] != n:
+                out = self._export_cache["rayHits"] = torch.empty((n, 48), dtype=torch.uint8, device=dev)
+        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != dev or tuple(out.shape) != (n, 48)
+              or (n and out.stride(1) != 1) or (n > 1 and (out.stride(0) < 48 or out.stride(0) % 8)) or (n and out.data_ptr() % 8)):
+            raise ValueError("out must be a uint8 tensor on %s of shape (%d, 48) with contiguous, non-overlapping, 8-byte aligned rows" % (dev, n))
+        capi.check(self._L.tetsim_raycast_visual_device(self._h, rays.data_ptr() if n else None, 8 * rays.stride(0) if n > 1 else 0,
+                                                        bodies.data_ptr() if bodies is not None and n else None, n,
+                                                        out.data_ptr() if n else None, out.stride(0) if n > 1 else 0, s), self._h)
+        i32, f64 = out.view(torch.int32), out.view(torch.float64)   # (rows of 12 / 6 of them; a strided `out` keeps its row stride)
+        return {"hit": i32[:, 0], "body": i32[:, 1], "triangle": i32[:, 2], "distance": f64[:, 2], "point": f64[:, 3:6], "raw": out}
+
+    def visualBoundingSpheresDevice(self, out=None, stream=None):
+        """torch.float64 [num_bodies, 4] on the handle's device: (centre x, y, z, radius) of every body's visual rows -- what
+        visualBoundingSphere() returns for that body alone, bit for bit; a body without rows: zeros.  No host copy and no synchronisation;
+        `out` and `stream` as in observeBodies."""
+        import torch
+        dev, s = self._torch_stream(torch, stream)
+        n = self.info.num_bodies
+        if out is None:
+            out = self._export_cache.get("visualSpheres")
+            if out is None:
+                out = self._export_cache["visualSpheres"] = torch.empty((n, 4), dtype=torch.float64, device=dev)
+        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or out.device != dev or tuple(out.shape) != (n, 4)
+              or out.stride(1) != 1 or (n > 1 and out.stride(0) < 4)):
+            raise ValueError("out must be a float64 tensor on %s of shape (%d, 4) with contiguous, non-overlapping rows" % (dev, n))
+        capi.check(self._L.tetsim_visual_bounding_spheres_device(self._h, out.data_ptr(), 8 * out.stride(0) if n > 1 else 0, s), self._h)
+        return out
 
     def nearestParticle(self, pos):
         """(global id, squared distance) of the owned particle nearest to pos -- the building block of startGrab for partitioned
