@@ -820,6 +820,28 @@ int tetsim_prep_tiles(const float *verts, uint32_t nv, const int32_t *tets, uint
  * ref_quirk != 0 reproduces the `<= 0.0` test.  Returns the number of dropped contributions. */
 int tetsim_prep_slot_table(const int32_t *tets, uint32_t nt, uint32_t nv, int32_t ref_quirk,
                            int32_t *slots /*[nv*36]*/, uint32_t *dropped);
+/* The dispatch schedule of the one-launch polar call (large unpartitioned bodies, fused_particle_pass 5).  Host only.
+ * tetsim_prep_call_tiles: what the schedule is built from, for a mesh tiled as tetsim_create tiles an unpartitioned body (particles in
+ * the device's numbering): sizes = {tiles, tile slots, vp_cols, nv_pad}; blk_vert_off [tiles + 1] and blk_verts [slots]: the particles
+ * each tile stages; vp_ell [vp_cols * nv_pad]: per particle v the tile slots on its lists, vp_ell[j * nv_pad + v], 0xffffffff = none.
+ * Pass NULL arrays to query the sizes first.
+ * tetsim_prep_call_schedule: one periodic table of *period entries (a multiple of 8); block g of a call of n substeps runs entry
+ * g % period for substep g / period (one less for a WRAPPED entry; a substep outside [0, n) does nothing), n * period + *tail blocks in
+ * all.  An entry is kind << 30 | wrapped << 29 | index: kind 0 = a tile, index = its block r in the plain order (tile
+ * (r % 8) * ceil(tiles / 8) + r / 8, always at a position = r mod 8); 1 = particles [256 * index, 256 * index + 256); 2 = nothing.
+ * lag 0 = the plain order, every tile and then every particle block; lag L = a particle block 8 * L positions behind the last tile on
+ * its particles' lists.  A lag that cannot be laid out gives the plain order: *fell_back = 1, the reason in tetsim_last_error(NULL).
+ * entry == NULL queries *period (capacity: the entries `entry` has room for).
+ * tetsim_prep_check_call_schedule: 0 if whatever a block of the table waits for has a smaller grid index and every tile and particle
+ * block appears exactly once, tiles on their XCD in order; else TETSIM_EINVAL and what is wrong in tetsim_last_error(NULL). */
+int tetsim_prep_call_tiles(const float *verts, uint32_t nv, const int32_t *tets, uint32_t nt, uint32_t sizes[4],
+                           uint32_t *blk_vert_off, int32_t *blk_verts, uint32_t *vp_ell);
+int tetsim_prep_call_schedule(const int32_t *blk_verts, const uint32_t *blk_vert_off, uint32_t nb, const uint32_t *vp_ell,
+                              uint32_t vp_cols, uint32_t nv_pad, uint32_t nv_owned, uint32_t lag, uint32_t *entry,
+                              uint32_t capacity, uint32_t *period, uint32_t *tail, int32_t *fell_back);
+int tetsim_prep_check_call_schedule(const int32_t *blk_verts, const uint32_t *blk_vert_off, uint32_t nb, const uint32_t *vp_ell,
+                                    uint32_t vp_cols, uint32_t nv_pad, uint32_t nv_owned, const uint32_t *entry, uint32_t period,
+                                    uint32_t tail);
 /* The particle(s) SoftbodyGPU.js:335-338,345 pins for `grab_id` on a mesh with num_elems tets (texture side
  * ceil(sqrt(num_elems))): out[0..1], -1 = none.  What TETSIM_FLAG_REF_GRAB_TEXEL uses. */
 int tetsim_prep_ref_grab_texels(int32_t grab_id, uint32_t num_elems, uint32_t num_particles, int32_t out[2]);
@@ -907,8 +929,9 @@ int tetsim_abi_version(void);
  * {TETSIM_DEBUG_LOOPBACK_HALO, TETSIM_DEBUG_LOOPBACK_COPY, TETSIM_DEBUG_ONE_STREAM, TETSIM_DEBUG_GROUP_SYNC,
  * TETSIM_DEBUG_HOSTPROF, TETSIM_DEBUG_TRACE*, TETSIM_HALO_SYNC, TETSIM_HALO_GRAPH, TETSIM_DEBUG_LOOPBACK_DELAY_US, TETSIM_NH_QUADS*,
  * TETSIM_FUSED_PARTICLE_PASS, TETSIM_FRAME_KERNEL, TETSIM_FRAME_LOCAL*, TETSIM_NH_FOLD*, TETSIM_HALO_ALIGNED_TILES*, TETSIM_HALO_FOLD_WAIT, TETSIM_QUAD,
- * TETSIM_QUAD_POLL_DELAY*, TETSIM_NH_FRAME*} is set in the environment and READ by this build -- the names marked * are A/B switches
- * of choices settled by measurement, which only the development build looks at (the product library reads the 12 others and
+ * TETSIM_QUAD_POLL_DELAY*, TETSIM_NH_FRAME*, TETSIM_NH_ONE_LAUNCH, TETSIM_PJ_ONE_LAUNCH, TETSIM_PJ_CALL_LAG} is set in the environment and
+ * READ by this build -- the names marked * are A/B switches
+ * of choices settled by measurement, which only the development build looks at (the product library reads the 15 others and
  * TETSIM_RCCL_LIB, TETSIM_HALO_TIMEOUT_MS, TETSIM_DEBUG_STREAM_PROBE: INTEGRATION.md 4).  bench.py records all of it in its JSON line. */
 typedef struct TetSimLibraryInfo {
     int32_t abi;

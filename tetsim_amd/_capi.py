@@ -69,7 +69,7 @@ class TetSimLibraryInfo(C.Structure):
 DEBUG_ENV_NAMES = ["TETSIM_DEBUG_LOOPBACK_HALO", "TETSIM_DEBUG_LOOPBACK_COPY", "TETSIM_DEBUG_ONE_STREAM", "TETSIM_DEBUG_GROUP_SYNC",
                    "TETSIM_DEBUG_HOSTPROF", "TETSIM_DEBUG_TRACE", "TETSIM_HALO_SYNC", "TETSIM_HALO_GRAPH", "TETSIM_DEBUG_LOOPBACK_DELAY_US", "TETSIM_NH_QUADS", "TETSIM_FUSED_PARTICLE_PASS",
                    "TETSIM_FRAME_KERNEL", "TETSIM_FRAME_LOCAL", "TETSIM_NH_FOLD", "TETSIM_HALO_ALIGNED_TILES", "TETSIM_HALO_FOLD_WAIT", "TETSIM_QUAD", "TETSIM_QUAD_POLL_DELAY", "TETSIM_NH_FRAME",
-                   "TETSIM_NH_ONE_LAUNCH", "TETSIM_PJ_ONE_LAUNCH"]
+                   "TETSIM_NH_ONE_LAUNCH", "TETSIM_PJ_ONE_LAUNCH", "TETSIM_PJ_CALL_LAG"]
 
 
 # A/B switches of settled choices: read (and reported) by the development build only (csrc/body.h: lab_env, build_info.cpp)
@@ -128,7 +128,7 @@ SYMBOLS = [
     "tetsim_comm_unique_id", "tetsim_comm_init", "tetsim_comm_info", "tetsim_comm_selftest", "tetsim_comm_probe", "tetsim_group_step_n", "tetsim_halo_exchange_local", "tetsim_get_halo_plan",
     "tetsim_halo_p2p_export", "tetsim_halo_p2p_connect",
     "tetsim_halo_export", "tetsim_halo_import", "tetsim_prep_levels", "tetsim_prep_colours", "tetsim_prep_clusters",
-    "tetsim_prep_tiles", "tetsim_prep_slot_table", "tetsim_prep_ref_grab_texels", "tetsim_prep_rest", "tetsim_prep_partition", "tetsim_prep_partition_quality", "tetsim_plan_create", "tetsim_plan_destroy", "tetsim_plan_sizes",
+    "tetsim_prep_tiles", "tetsim_prep_slot_table", "tetsim_prep_call_tiles", "tetsim_prep_call_schedule", "tetsim_prep_check_call_schedule", "tetsim_prep_ref_grab_texels", "tetsim_prep_rest", "tetsim_prep_partition", "tetsim_prep_partition_quality", "tetsim_plan_create", "tetsim_plan_destroy", "tetsim_plan_sizes",
     "tetsim_plan_arrays", "tetsim_plan_neighbour", "tetsim_plan_neighbour_ids",
     "tetsim_plan_create_deep", "tetsim_plan_layers", "tetsim_plan_neighbour_layer2", "tetsim_plan_neighbour_layer2_ids",
     "tetsim_raycast_visual", "tetsim_start_grab_ray", "tetsim_read_visual_bounding_sphere", "tetsim_prep_boundary_surface",
@@ -252,6 +252,10 @@ def lib():
     L.tetsim_prep_clusters.argtypes = [ip, u32, u32, ip, ip, ip, ip, C.POINTER(u32), C.POINTER(u32)]
     L.tetsim_prep_tiles.argtypes = [fp, u32, ip, u32, C.POINTER(u32), C.POINTER(u32), u32, ip, C.POINTER(u32), C.POINTER(C.c_uint8), C.POINTER(u32)]
     L.tetsim_prep_slot_table.argtypes = [ip, u32, u32, i32, ip, C.POINTER(u32)]
+    up = C.POINTER(u32)
+    L.tetsim_prep_call_tiles.argtypes = [fp, u32, ip, u32, up, up, ip, up]
+    L.tetsim_prep_call_schedule.argtypes = [ip, up, u32, up, u32, u32, u32, u32, up, u32, up, up, ip]
+    L.tetsim_prep_check_call_schedule.argtypes = [ip, up, u32, up, u32, u32, u32, up, u32, u32]
     L.tetsim_prep_ref_grab_texels.argtypes = [i32, u32, u32, ip]
     L.tetsim_prep_rest.argtypes = [fp, u32, ip, u32, dbl, fp, fp, fp]
     L.tetsim_prep_partition.argtypes = [fp, u32, ip, u32, i32, ip]

@@ -212,6 +212,8 @@ struct tetsim_body {
     // two kernels per substep (A/B); tetsim_step and tetsim_profile keep the two kernels (same arithmetic, same bits)
     bool pj_one_launch = false;
     uint32_t* d_substep_err = nullptr;
+    // ... in the order of a host-built dispatch table (host_prep.h: CallSchedule; TETSIM_PJ_CALL_LAG at creation, 0 = every tile, then every particle block)
+    PJCallSched call_sched;
     // TETSIM_FLAG_LEAN_STATE (pj_blocked.hip: kModeLeanState): the substep neither reads nor writes pj.quat; it is recovered from the carried
     // shape and this constant centred rest shape when somebody asks for it (ensure_quats)
     float4 *rest0_a = nullptr, *rest0_b = nullptr, *rest0_c = nullptr;

@@ -3,6 +3,8 @@
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
+#include "host_prep.h"
+
 #include <cstddef>
 #include <cstdint>
 
@@ -147,10 +149,14 @@ struct NHDev {
 // ---- grids of the one-launch calls (pjb_call_kernel, nh_call_kernel): n substeps x the workgroups of one substep ----------------
 // A dispatch holds at most 2^32 - 1 WORK-ITEMS (the AQL packet's grid size is a 32-bit count of work-items), not workgroups.
 constexpr uint32_t max_grid_blocks(uint32_t threads) { return 0xffffffffu / threads; }
-// pjb_call_kernel: the tiles rounded up to whole rows of 8 (one per XCD), then the owned particles' workgroups, the sum rounded up to 8
-// again (block r of every substep lands on the XCD of block r of the first).  The launch and tetsim_step_n's chunking both use this.
-constexpr uint32_t pjb_call_blocks_per_sub(uint32_t nb, uint32_t nv_owned, uint32_t threads) {
-    return (((nb + 7u) & ~7u) + (nv_owned + threads - 1u) / threads + 7u) & ~7u;
+// pjb_call_kernel: the period of the plain dispatch table is pjb_call_blocks_per_sub (host_prep.h, where the table is built); a table with
+// a lag (host_prep.h: CallSchedule) may be longer and has a tail, and a call of n substeps is n * period + tail blocks
+struct PJCallSched { const uint32_t* entry = nullptr; uint32_t period = 0, tail = 0; };
+// the most substeps one launch of that table may hold (call_chunk below, less the tail's share of the dispatch limit)
+constexpr uint32_t pjb_call_chunk(uint32_t period, uint32_t tail, uint32_t threads, uint32_t cap) {
+    const uint32_t room = max_grid_blocks(threads) > tail ? max_grid_blocks(threads) - tail : 0u;
+    const uint32_t fit = period ? room / period : cap;
+    return fit < 1u ? 1u : fit < cap ? fit : cap;
 }
 // nh_call_kernel: the clusters' blocks of all colours, rounded up to 8
 constexpr uint32_t nh_call_blocks_per_sub(uint32_t blocks) { return (blocks + 7u) & ~7u; }
@@ -159,7 +165,8 @@ constexpr uint32_t call_chunk(uint32_t per_sub, uint32_t threads, uint32_t cap) 
     const uint32_t fit = per_sub ? max_grid_blocks(threads) / per_sub : cap;
     return fit < 1u ? 1u : fit < cap ? fit : cap;
 }
-static_assert(call_chunk(pjb_call_blocks_per_sub(2282u, 103823u, 256u), 256u, 8192u) == 6223u, "46-cell lattice: 2,696 blocks per substep");
+static_assert(pjb_call_chunk(pjb_call_blocks_per_sub(2282u, 103823u, 256u), 0u, 256u, 8192u) == 6223u, "46-cell lattice: 2,696 blocks per substep");
+static_assert(pjb_call_chunk(pjb_call_blocks_per_sub(2282u, 103823u, 256u), 2696u, 256u, 8192u) == 6222u, "... and a tail of a whole period takes one substep's room");
 static_assert(call_chunk(nh_call_blocks_per_sub(2601u), 256u, 65000u / 8u) == 6432u, "55-cell lattice, clustered: 2,608 blocks per substep");
 
 // One launch of the clustered Gauss-Seidel schedule (host_prep.h ClusterPlan): lane = cluster, step j = tets first[j] + lane
@@ -246,8 +253,9 @@ void pjb_launch_tet(hipStream_t s, const PJBlk& d, uint32_t tile_first, uint32_t
                     hipEvent_t e1 = nullptr, uint32_t* raise_word = nullptr, uint32_t* clear_word = nullptr);
 // n substeps -- per substep every tile, then every owned particle -- as ONE launch (pj_blocked.hip: pjb_call_kernel): partial sums and
 // predictions carry the sequence number (d.epoch or DevParams::epoch) + substep + 1, their readers look for it; err: raised by a wave that
-// waited in vain.  n * blocks per substep must fit a grid (tetsim_step_n chunks long calls).
-void pjb_launch_call(hipStream_t s, const PJBlk& d, uint32_t n, uint32_t* err, uint32_t timeout_ms, const DevParams& params, DevParams* params_dev);
+// waited in vain.  sched: the dispatch table (device memory) every block reads its work from; n * period + tail blocks must fit a grid
+// (tetsim_step_n chunks long calls: pjb_call_chunk).
+void pjb_launch_call(hipStream_t s, const PJBlk& d, const PJCallSched& sched, uint32_t n, uint32_t* err, uint32_t timeout_ms, const DevParams& params, DevParams* params_dev);
 // the same tiles with the previous substep's particle update fused into the staging (d.partial_prev / fin_in / fin_out set)
 void pjb_launch_tet_fused(hipStream_t s, const PJBlk& d, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 void pjb_launch_vertex(hipStream_t s, const PJBlk& d, uint32_t first, uint32_t count, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr,

@@ -531,6 +531,171 @@ void build_blocks(const float* verts, const int32_t* tets, uint32_t nt, uint32_t
         }
 }
 
+// ---- dispatch schedule of the one-launch polar call ---------------------------------------------------------------------------------
+namespace {
+// who waits for whom: per particle block the tiles on its particles' lists, per tile the particle blocks that own what it stages
+struct SchedDeps {
+    uint32_t per_xcd = 0, tet_blocks = 0, npb = 0, plain_period = 0;
+    std::vector<std::vector<uint32_t>> tiles_of_pb, pbs_of_tile;
+};
+SchedDeps sched_deps(const int32_t* blk_verts, const uint32_t* blk_vert_off, uint32_t nb, const uint32_t* vp_ell, uint32_t vp_cols, uint32_t nv_pad,
+                     uint32_t nv_owned, uint32_t tile) {
+    SchedDeps D;
+    D.per_xcd = (nb + 7u) / 8u; D.tet_blocks = D.per_xcd * 8u; D.npb = (nv_owned + tile - 1u) / tile;
+    D.plain_period = pjb_call_blocks_per_sub(nb, nv_owned, tile);
+    D.tiles_of_pb.resize(D.npb); D.pbs_of_tile.resize(nb);
+    for (uint32_t v = 0; v < nv_owned; v++)
+        for (uint32_t j = 0; j < vp_cols; j++) {
+            const uint32_t idx = vp_ell[static_cast<size_t>(j) * nv_pad + v];
+            if (idx == 0xffffffffu) continue;
+            const uint32_t b = static_cast<uint32_t>(std::upper_bound(blk_vert_off, blk_vert_off + nb + 1, idx) - blk_vert_off) - 1u;
+            if (b < nb) D.tiles_of_pb[v / tile].push_back(b);
+        }
+    for (uint32_t b = 0; b < nb; b++)
+        for (uint32_t g = blk_vert_off[b]; g < blk_vert_off[b + 1]; g++)
+            if (static_cast<uint32_t>(blk_verts[g]) < nv_owned) D.pbs_of_tile[b].push_back(static_cast<uint32_t>(blk_verts[g]) / tile);
+    auto uniq = [](std::vector<uint32_t>& v) { std::sort(v.begin(), v.end()); v.erase(std::unique(v.begin(), v.end()), v.end()); };
+    for (auto& v : D.tiles_of_pb) uniq(v);
+    for (auto& v : D.pbs_of_tile) uniq(v);
+    return D;
+}
+inline uint32_t sched_tile_of(uint32_t r, uint32_t per_xcd) { return (r & 7u) * per_xcd + (r >> 3); }
+void sched_plain(const SchedDeps& D, uint32_t nb, CallSchedule* out) {
+    out->period = D.plain_period;
+    out->tail = 0; out->lag = 0;
+    out->entry.assign(out->period, sched_entry(kSchedEmpty, 0));
+    for (uint32_t r = 0; r < D.tet_blocks; r++)
+        if (sched_tile_of(r, D.per_xcd) < nb) out->entry[r] = sched_entry(kSchedTile, r);
+    for (uint32_t k = 0; k < D.npb; k++) out->entry[D.tet_blocks + k] = sched_entry(kSchedParticles, k);
+}
+// One pass of the greedy layout.  head_at[k] != none: particle block k is WRAPPED -- it sits in the head of the period at the first free
+// position >= head_at[k] and belongs to the substep before.  ready[k]: where block k may sit at the earliest (last tile on its lists +
+// 8 * lag), in positions of this period; left: the unwrapped blocks that found no place before the period's end.
+struct SchedPass { std::vector<uint32_t> entry, ready, left; uint32_t head_end = 0; bool stuck = false; };
+SchedPass sched_pass(const SchedDeps& D, uint32_t nb, uint32_t lag, const std::vector<uint32_t>& head_at) {
+    constexpr uint32_t none = 0xffffffffu;
+    SchedPass R;
+    R.ready.assign(D.npb, none);
+    std::vector<uint32_t> need(D.npb), head, queue;   // head: wrapped blocks by head_at; queue: blocks whose tiles are all placed, by ready
+    std::vector<uint8_t> head_placed(D.npb, 0);
+    for (uint32_t k = 0; k < D.npb; k++) {
+        need[k] = static_cast<uint32_t>(D.tiles_of_pb[k].size());
+        if (head_at[k] != none) head.push_back(k);
+        if (need[k] == 0) { R.ready[k] = 0; if (head_at[k] == none) queue.push_back(k); }
+    }
+    std::stable_sort(head.begin(), head.end(), [&](uint32_t a, uint32_t b) { return head_at[a] < head_at[b]; });
+    std::vector<std::vector<uint32_t>> pbs_by_tile(nb);
+    for (uint32_t k = 0; k < D.npb; k++) for (uint32_t b : D.tiles_of_pb[k]) pbs_by_tile[b].push_back(k);
+    size_t hi = 0, qi = 0;   // (ready positions only grow along the walk: the queue stays sorted)
+    uint32_t col_next[8] = {}, tiles_left = D.tet_blocks;
+    const uint64_t limit = 4ull * (D.tet_blocks + D.npb) + 64ull * (static_cast<uint64_t>(lag) + 1ull) + 64ull;   // (a period far longer than its entries: give up)
+    for (uint32_t p = 0;; p++) {
+        if (tiles_left == 0 && hi == head.size() && (p & 7u) == 0u) break;
+        if (p >= limit) { R.stuck = true; break; }
+        const uint32_t x = p & 7u;
+        if (hi < head.size() && head_at[head[hi]] <= p) {
+            const uint32_t k = head[hi++];
+            R.entry.push_back(sched_entry(kSchedParticles, k, true));
+            head_placed[k] = 1; R.head_end = p + 1u;
+            continue;
+        }
+        if (qi < queue.size() && R.ready[queue[qi]] <= p) { R.entry.push_back(sched_entry(kSchedParticles, queue[qi++])); continue; }
+        if (col_next[x] < D.per_xcd) {
+            const uint32_t r = 8u * col_next[x] + x, b = sched_tile_of(r, D.per_xcd);
+            bool held = false;   // a tile that stages particles of a wrapped block waits for it
+            if (b < nb) for (uint32_t k : D.pbs_of_tile[b]) held = held || (head_at[k] != none && !head_placed[k]);
+            if (!held) {
+                col_next[x]++; tiles_left--;
+                R.entry.push_back(b < nb ? sched_entry(kSchedTile, r) : sched_entry(kSchedEmpty, 0));
+                if (b < nb) for (uint32_t k : pbs_by_tile[b])
+                    if (--need[k] == 0) { R.ready[k] = p + 8u * lag; if (head_at[k] == none) queue.push_back(k); }
+                continue;
+            }
+        }
+        R.entry.push_back(sched_entry(kSchedEmpty, 0));
+    }
+    R.left.assign(queue.begin() + static_cast<std::ptrdiff_t>(qi), queue.end());
+    return R;
+}
+}  // namespace
+
+std::string check_call_schedule(const int32_t* blk_verts, const uint32_t* blk_vert_off, uint32_t nb, const uint32_t* vp_ell, uint32_t vp_cols,
+                                uint32_t nv_pad, uint32_t nv_owned, const uint32_t* entry, uint32_t period, uint32_t tail, uint32_t tile) {
+    constexpr uint32_t none = 0xffffffffu;
+    const SchedDeps D = sched_deps(blk_verts, blk_vert_off, nb, vp_ell, vp_cols, nv_pad, nv_owned, tile);
+    if (period == 0 || period % 8u != 0u) return "the period is not a positive multiple of 8";
+    if (period < D.plain_period) return "the period is shorter than a substep's blocks";
+    // where everything of substep 0 sits in the grid: position, plus a period for a wrapped entry
+    std::vector<uint64_t> at_tile(nb, none), at_pb(D.npb, none);
+    uint32_t col_seen[8] = {}, wrapped_end = 0;
+    for (uint32_t p = 0; p < period; p++) {
+        const uint32_t kind = entry[p] >> 30, index = entry[p] & kSchedIndexMask;
+        const bool wrapped = (entry[p] & kSchedWrapped) != 0u;
+        if (kind == kSchedEmpty) continue;
+        if (kind == kSchedTile) {
+            const uint32_t b = sched_tile_of(index, D.per_xcd);
+            if (index >= D.tet_blocks || b >= nb) return "entry " + std::to_string(p) + " names a tile that does not exist";
+            if ((index & 7u) != (p & 7u)) return "tile block " + std::to_string(index) + " is not on its XCD";
+            if (wrapped) return "tile block " + std::to_string(index) + " is wrapped";
+            if ((index >> 3) < col_seen[p & 7u]) return "tile block " + std::to_string(index) + " is out of its XCD's order";
+            col_seen[p & 7u] = (index >> 3) + 1u;
+            if (at_tile[b] != none) return "tile " + std::to_string(b) + " appears twice";
+            at_tile[b] = p;
+        } else if (kind == kSchedParticles) {
+            if (index >= D.npb) return "entry " + std::to_string(p) + " names a particle block that does not exist";
+            if (at_pb[index] != none) return "particle block " + std::to_string(index) + " appears twice";
+            at_pb[index] = static_cast<uint64_t>(p) + (wrapped ? period : 0u);
+            if (wrapped) wrapped_end = p + 1u;
+        } else return "entry " + std::to_string(p) + " has no kind";
+    }
+    for (uint32_t b = 0; b < nb; b++) if (at_tile[b] == none) return "tile " + std::to_string(b) + " is missing";
+    for (uint32_t k = 0; k < D.npb; k++) if (at_pb[k] == none) return "particle block " + std::to_string(k) + " is missing";
+    if (tail < wrapped_end || tail > period) return "the tail does not cover the wrapped entries";
+    // (Block k of s in front of block k of s + 1, tile b of s in front of tile b of s + 1: these two orderings hold by construction -- every
+    // block has exactly ONE entry per period, checked above, so its entries of consecutive substeps are a period apart -- and need no test.)
+    for (uint32_t k = 0; k < D.npb; k++)
+        for (uint32_t b : D.tiles_of_pb[k])
+            if (!(at_tile[b] < at_pb[k])) return "particle block " + std::to_string(k) + " does not follow tile " + std::to_string(b) + " of its lists";
+    for (uint32_t b = 0; b < nb; b++)
+        for (uint32_t k : D.pbs_of_tile[b])
+            if (!(at_pb[k] < at_tile[b] + period)) return "tile " + std::to_string(b) + " of the next substep does not follow particle block " + std::to_string(k);
+    return "";
+}
+
+void build_call_schedule(const int32_t* blk_verts, const uint32_t* blk_vert_off, uint32_t nb, const uint32_t* vp_ell, uint32_t vp_cols,
+                         uint32_t nv_pad, uint32_t nv_owned, uint32_t lag, CallSchedule* out, uint32_t tile) {
+    constexpr uint32_t none = 0xffffffffu;
+    const SchedDeps D = sched_deps(blk_verts, blk_vert_off, nb, vp_ell, vp_cols, nv_pad, nv_owned, tile);
+    *out = CallSchedule();
+    auto plain = [&](const std::string& why) {
+        sched_plain(D, nb, out);
+        out->fell_back = !why.empty(); out->why = why;
+    };
+    if (lag == 0 || nb == 0) return plain("");
+    if (static_cast<uint64_t>(lag) * 8u >= D.plain_period) return plain("lag " + std::to_string(lag) + ": a whole substep or more");
+    // The wrapped set only grows from pass to pass (a block that once found no place before the period's end stays wrapped), so the
+    // passes end; each pass places the wrapped blocks where the pass before saw them become ready.
+    std::vector<uint32_t> head_at(D.npb, none);
+    SchedPass R;
+    bool settled = false;
+    for (int pass = 0; pass < 64 && !settled; pass++) {
+        R = sched_pass(D, nb, lag, head_at);
+        if (R.stuck) return plain("lag " + std::to_string(lag) + ": the layout does not close");
+        const uint32_t period = static_cast<uint32_t>(R.entry.size());
+        settled = R.left.empty();
+        for (uint32_t k : R.left) head_at[k] = 0;
+        for (uint32_t k = 0; k < D.npb; k++)
+            if (head_at[k] != none && !settled) head_at[k] = R.ready[k] != none && R.ready[k] > period ? R.ready[k] - period : 0u;
+    }
+    if (!settled) return plain("lag " + std::to_string(lag) + ": the wrapped blocks do not settle");
+    out->entry = R.entry;
+    out->period = static_cast<uint32_t>(R.entry.size());
+    out->tail = R.head_end;
+    out->lag = lag;
+    const std::string bad = check_call_schedule(blk_verts, blk_vert_off, nb, vp_ell, vp_cols, nv_pad, nv_owned, out->entry.data(), out->period, out->tail, tile);
+    if (!bad.empty()) return plain("lag " + std::to_string(lag) + ": " + bad);
+}
+
 std::string validate_mesh(const float* verts, uint32_t nv, const int32_t* tets, uint32_t nt, bool forbid_repeats) {
     if ((nv && !verts) || (nt && !tets)) return "null mesh pointer";
     if (nv == 0) return "mesh has no vertices";

@@ -159,6 +159,40 @@ void build_blocks(const float* verts, const int32_t* tets, uint32_t nt, uint32_t
                   const uint32_t* body_first_vert = nullptr, uint32_t bodies = 1, uint32_t nv_boundary = 0,
                   const uint8_t* tet_class = nullptr, uint32_t nv_owned = 0xffffffffu, uint32_t tile = kBlockTile);
 
+// ---- dispatch schedule of the one-launch polar call (pj_blocked.hip: pjb_call_kernel) ----------------------------------------------
+// One periodic table says what every workgroup of the call's grid does: block g runs entry g % period for substep g / period (+ the
+// entry's offset, 0 or -1; a substep outside [0, n) returns at once), and a call of n substeps has n * period + tail blocks.
+// An entry: kind << 30 | wrapped << 29 | index.  Tile entries carry the tile's BLOCK index r of today's order (the tile is
+// (r & 7) * tiles_per_xcd + (r >> 3), and r & 7 == position & 7: a tile stays on its XCD and every XCD walks its eighth in order);
+// particle entries the index of 256 consecutive owned particles; wrapped = the entry belongs to the substep one period back.
+constexpr uint32_t kSchedTile = 0u, kSchedParticles = 1u, kSchedEmpty = 2u, kSchedWrapped = 1u << 29, kSchedIndexMask = (1u << 29) - 1u;
+constexpr uint32_t sched_entry(uint32_t kind, uint32_t index, bool wrapped = false) { return kind << 30 | (wrapped ? kSchedWrapped : 0u) | index; }
+// the period of the plain table: the tiles rounded up to whole rows of 8 (one per XCD), then the owned particles' workgroups, the sum rounded
+// up to 8 again (block r of every substep lands on the XCD of block r of the first)
+constexpr uint32_t pjb_call_blocks_per_sub(uint32_t nb, uint32_t nv_owned, uint32_t threads) {
+    return (((nb + 7u) & ~7u) + (nv_owned + threads - 1u) / threads + 7u) & ~7u;
+}
+constexpr uint32_t kPJCallLagDefault = 0;   // TETSIM_PJ_CALL_LAG when the environment has none (what the sweep on the 1 M-tet lattice showed)
+struct CallSchedule {
+    std::vector<uint32_t> entry;   // [period]
+    uint32_t period = 0, tail = 0;
+    uint32_t lag = 0;              // the lag the table was built with: 0 = every particle block behind every tile (the plain order)
+    bool fell_back = false;        // the requested lag could not be laid out: `entry` is the plain order, `why` says what failed
+    std::string why;
+};
+// The plain order [tiles | particle blocks] when lag == 0; else every particle block at the first free position >= 8 * lag behind the
+// last tile on its particles' lists (blocks whose place passes the end of the period sit, wrapped, near the head of the next; a tile
+// that stages a wrapped block's particles is held back behind it with empty entries).  The result is checked with check_call_schedule;
+// a lag that cannot be laid out falls back to the plain order.  tile = particles per particle block = kBlockTile.
+void build_call_schedule(const int32_t* blk_verts, const uint32_t* blk_vert_off, uint32_t nb, const uint32_t* vp_ell, uint32_t vp_cols,
+                         uint32_t nv_pad, uint32_t nv_owned, uint32_t lag, CallSchedule* out, uint32_t tile = kBlockTile);
+// The progress invariant of a table -- whatever a block waits for has a smaller grid index -- and its completeness: every tile and every
+// particle block exactly once, tiles on their XCD and in order, and for substeps s and s + 1: every tile on a particle block's lists in
+// front of that block, every particle block that owns a particle a tile stages in front of that tile's entry of s + 1, block k of s in
+// front of block k of s + 1, tile b of s in front of tile b of s + 1.  "" or what is wrong.
+std::string check_call_schedule(const int32_t* blk_verts, const uint32_t* blk_vert_off, uint32_t nb, const uint32_t* vp_ell, uint32_t vp_cols,
+                                uint32_t nv_pad, uint32_t nv_owned, const uint32_t* entry, uint32_t period, uint32_t tail, uint32_t tile = kBlockTile);
+
 std::string validate_mesh(const float* verts, uint32_t nv, const int32_t* tets, uint32_t nt, bool forbid_repeats);
 
 }  // namespace tetsim

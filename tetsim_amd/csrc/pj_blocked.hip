@@ -151,6 +151,7 @@ __device__ __forceinline__ void pjb_tet_body(const PJBlk& d, uint32_t tile_first
     const uint32_t b = tile_first + rel;
     const uint32_t tid = threadIdx.x;
     TETSIM_LAB_TILE_BEGIN();
+    TETSIM_POLL_TILE(0);
     const uint32_t t0 = d.blk_tet_off[b], ntb = d.blk_tet_off[b + 1] - t0;
     const uint32_t v0 = d.blk_vert_off[b], nu = d.blk_vert_off[b + 1] - v0;
 
@@ -255,6 +256,8 @@ __device__ __forceinline__ void pjb_tet_body(const PJBlk& d, uint32_t tile_first
         const float4* src = vid >= d.nv_owned ? (g < d.n_ghost1 ? d.ghost_alt + g : d.ghost2 + (g - d.n_ghost1)) : d.pos_pred + vid;
         pos_stage = *src;
     } else if constexpr (kPoll) {
+        TETSIM_POLL_BEGIN();
+        TETSIM_POLL_TILE(1);
         pos_stage = load_coherent(d.pos_pred, vid);
         if (poll->want != 0u) {
             bool pend = has_slot && __float_as_uint(pos_stage.w) != poll->want;
@@ -262,14 +265,18 @@ __device__ __forceinline__ void pjb_tet_body(const PJBlk& d, uint32_t tile_first
                 const long long t0 = wall_clock64(), limit = 100000ll * poll->timeout_ms;   // 100 MHz ticks; 0 = unbounded
                 do {
                     __builtin_amdgcn_s_sleep(TETSIM_POLL_SLEEP);
+                    TETSIM_POLL_LOOK();
                     asm volatile("" ::: "memory");   // (every look is a fresh load)
                     if (pend) { pos_stage = load_coherent(d.pos_pred, vid); pend = __float_as_uint(pos_stage.w) != poll->want; }
                     if (limit && pend && wall_clock64() - t0 > limit) { __hip_atomic_store(poll->error, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); pend = false; }
                 } while (__builtin_amdgcn_ballot_w64(pend) != 0ull);
             }
+            TETSIM_POLL_TILE(2);
             __syncthreads();   // (every wave's looks have succeeded: every particle of the tile is stamped, i.e. every neighbouring tile's record too)
+            TETSIM_POLL_TILE(3);
             load_record();
         }
+        TETSIM_POLL_TILE_SAVE();
     } else {
         pos_stage = d.pos_pred[vid];
     }
@@ -352,6 +359,7 @@ __device__ __forceinline__ void pjb_tet_body(const PJBlk& d, uint32_t tile_first
         store_wt(d.partial, v0 + tid, acc);
     }
     TETSIM_STAMP(6);
+    TETSIM_POLL_TILE(4);
 }
 
 __global__ __launch_bounds__(kTile, 2) void pjb_tet_kernel(PJBlk d, uint32_t tile_first, uint32_t tile_count,
@@ -752,19 +760,29 @@ __global__ __launch_bounds__(64) void pjb_vertex_kernel(PJBlk d, uint32_t first,
 //   The call's parameters arrive BY VALUE, with the launch: the 176-byte upload in front of every call (a copy, its event, the switch between
 // the copy engine and the compute queue) was most of the ~18 us the device idled between two calls (tools/call_gap.py).  The first workgroup
 // leaves them in DevParams for the kernels behind this one (tetsim_step's pair, the read-outs).
+//   WHICH workgroup does what is a table the host built (host_prep.cpp: build_call_schedule): block g runs entry g % period for substep
+// g / period, or the substep before for a wrapped entry.  The plain table is every tile, then every particle block; with a lag a particle
+// block sits a chosen distance behind the last tile on its particles' lists instead of behind the whole substep, so its first look
+// succeeds.  Progress rests on "whatever a block waits for has a smaller grid index", which the table's builder checks on the host.
 template <int kMode>
-__global__ __launch_bounds__(kTile, 2) void pjb_call_kernel(PJBlk d, uint32_t n_sub, uint32_t tile_count, uint32_t tiles_per_xcd, uint32_t tet_blocks, uint32_t blocks_per_sub,
+__global__ __launch_bounds__(kTile, 2) void pjb_call_kernel(PJBlk d, uint32_t n_sub, uint32_t tile_count, uint32_t tiles_per_xcd, const uint32_t* __restrict__ sched, uint32_t period,
                                                            uint32_t* err, uint32_t timeout_ms, DevParams pv, DevParams* pdev TETSIM_DBG_PARAM) {
-    const uint32_t sub = blockIdx.x / blocks_per_sub, r = blockIdx.x - sub * blocks_per_sub;   // (blocks_per_sub is a multiple of 8: r and blockIdx.x land on the same XCD)
-    const uint32_t stamp = (d.epoch ? d.epoch : pv.epoch) + sub + 1u;
+    const uint32_t turn = blockIdx.x / period, entry = sched[blockIdx.x - turn * period];   // (the period is a multiple of 8: an entry's position and blockIdx.x land on the same XCD)
     if (blockIdx.x == 0u && threadIdx.x == 0u) store_params(pdev, pv);
-    if (r < tet_blocks) {
+    const uint32_t back = (entry & kSchedWrapped) ? 1u : 0u, kind = entry >> 30, r = entry & kSchedIndexMask;
+    if (kind == kSchedEmpty || turn < back || turn - back >= n_sub) return;   // (nothing here, or a substep outside the call: the head of the first period, the tail)
+    const uint32_t sub = turn - back;
+    const uint32_t stamp = (d.epoch ? d.epoch : pv.epoch) + sub + 1u;
+    TETSIM_LAB_CALL_MARK(sub, n_sub);
+    if (kind == kSchedTile) {
         const PJPoll poll = {r, sub ? stamp - 1u : 0u, err, timeout_ms};
         pjb_tet_body<kMode, false, false, false, true>(d, 0u, tile_count, tiles_per_xcd TETSIM_DBG_ARG, nullptr, stamp, &poll);
         return;
     }
-    const uint32_t v = (r - tet_blocks) * kTile + threadIdx.x;
+    const uint32_t v = r * kTile + threadIdx.x;
     if (v >= d.nv_owned) return;
+    TETSIM_POLL_BEGIN();
+    TETSIM_POLL_PB(0);
     float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     const uint32_t* col = d.vp_ell + v;
     const long long limit = 100000ll * timeout_ms;   // 100 MHz ticks; 0 = unbounded
@@ -778,6 +796,7 @@ __global__ __launch_bounds__(kTile, 2) void pjb_call_kernel(PJBlk d, uint32_t n_
 #pragma unroll
         for (uint32_t j = 0; j < 8u; j++) idx[j] = (j0 + j < d.vp_cols) ? col[static_cast<size_t>(j0 + j) * d.nv_pad] : 0xffffffffu;
         uint32_t pend = 0;
+        TETSIM_POLL_PB_FIRST(j0);
 #pragma unroll
         for (uint32_t j = 0; j < 8u; j++) {
             const float4 t = load_coherent(d.partial, idx[j] != 0xffffffffu ? idx[j] : 0u);
@@ -788,6 +807,7 @@ __global__ __launch_bounds__(kTile, 2) void pjb_call_kernel(PJBlk d, uint32_t n_
             const long long t0 = wall_clock64();
             do {
                 __builtin_amdgcn_s_sleep(TETSIM_POLL_SLEEP);
+                TETSIM_POLL_LOOK();
                 asm volatile("" ::: "memory");   // (every look is a fresh load)
 #pragma unroll
                 for (uint32_t j = 0; j < 8u; j++)
@@ -805,19 +825,24 @@ __global__ __launch_bounds__(kTile, 2) void pjb_call_kernel(PJBlk d, uint32_t n_
         for (uint32_t j = 0; j < 8u; j++) { acc.x += g[j].x; acc.y += g[j].y; acc.z += g[j].z; }
         if (__all(idx[7] == 0xffffffffu)) break;
     }
+    TETSIM_POLL_PB(2);
     if (sub) {
         const long long t0 = wall_clock64();
         while (__float_as_uint(prev.w) != stamp - 1u) {
             __builtin_amdgcn_s_sleep(4);
+            TETSIM_POLL_LOOK();
             asm volatile("" ::: "memory");
             prev = load_coherent(d.fin_in, v);
             if (limit && wall_clock64() - t0 > limit) { __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); break; }
         }
     }
+    TETSIM_POLL_PB(3);
     const VertexOut o = pjb_vertex_update(xyz(acc), wsum, xyz(prev), pv, v);
     store_wt(d.fin_out, v, make_float4(o.p.x, o.p.y, o.p.z, __uint_as_float(stamp)));
     if (d.vel && sub + 1u == n_sub) store_wt(d.vel, v, make_float4(o.vel.x, o.vel.y, o.vel.z, 0.0f));   // (the velocity array: behind a call's last substep only)
     store_wt(d.pos_pred, v, make_float4(o.pred.x, o.pred.y, o.pred.z, __uint_as_float(stamp)));
+    TETSIM_POLL_PB(4);
+    TETSIM_POLL_PB_SAVE();
 }
 __global__ __launch_bounds__(64) void pjb_vertex_kernel_raise(PJBlk d, uint32_t first, uint32_t count, uint32_t* sig, uint32_t* clear) {
     clear_then_raise(clear, sig);
@@ -946,12 +971,12 @@ void pjb_launch_tet(hipStream_t s, const PJBlk& d, uint32_t tile_first, uint32_t
     if (e0) hipExtLaunchKernelGGL(kernel, dim3(per_xcd * 8u), dim3(kTile), 0, s, e0, e1, 0, d, tile_first, tile_count, per_xcd TETSIM_DBG_LAUNCH);
     else hipLaunchKernelGGL(kernel, dim3(per_xcd * 8u), dim3(kTile), 0, s, d, tile_first, tile_count, per_xcd TETSIM_DBG_LAUNCH);
 }
-void pjb_launch_call(hipStream_t s, const PJBlk& d, uint32_t n, uint32_t* err, uint32_t timeout_ms, const DevParams& params, DevParams* params_dev) {
-    if (d.nb == 0 || n == 0) return;
-    const uint32_t per_xcd = (d.nb + 7u) / 8u, tet_blocks = per_xcd * 8u, per_sub = pjb_call_blocks_per_sub(d.nb, d.nv_owned, kTile);
+void pjb_launch_call(hipStream_t s, const PJBlk& d, const PJCallSched& sched, uint32_t n, uint32_t* err, uint32_t timeout_ms, const DevParams& params, DevParams* params_dev) {
+    if (d.nb == 0 || n == 0 || sched.period == 0) return;
+    const uint32_t per_xcd = (d.nb + 7u) / 8u;
     const int mode = blk_mode(d);
     auto* kernel = mode == kModeConstantRest ? pjb_call_kernel<kModeConstantRest> : mode == kModeLeanState ? pjb_call_kernel<kModeLeanState> : pjb_call_kernel<kModeCarried>;
-    hipLaunchKernelGGL(kernel, dim3(per_sub * n), dim3(kTile), 0, s, d, n, d.nb, per_xcd, tet_blocks, per_sub, err, timeout_ms, params, params_dev TETSIM_DBG_LAUNCH);
+    hipLaunchKernelGGL(kernel, dim3(sched.period * n + sched.tail), dim3(kTile), 0, s, d, n, d.nb, per_xcd, sched.entry, sched.period, err, timeout_ms, params, params_dev TETSIM_DBG_LAUNCH);
 }
 void pjb_launch_tet_fused(hipStream_t s, const PJBlk& d, hipEvent_t e0, hipEvent_t e1) { launch_tet_x(s, d, 0u, d.nb, TetFused{0u}, e0, e1); }
 void pjb_launch_frame(hipStream_t s, const PJBlk& d, uint32_t n, const int32_t* block_tile, uint32_t blocks, bool local, float4* pbuf0, float4* pbuf1,

@@ -40,8 +40,9 @@ static uint32_t tet_mode() {
         const char* np = getenv("TETSIM_DEBUG_NO_PEEL");
         const char* sg = getenv("TETSIM_DEBUG_STAGGER");
         const char* sm = getenv("TETSIM_DEBUG_STAGGER_MAP");
+        const char* pt = getenv("TETSIM_DEBUG_POLL_TRACE");   // (tetsim_create.hip sizes the trace for the rows of the looks)
         dbg = (it ? (atoi(it) & 15) : 9) | ((sk && sk[0] == '1') ? 16 : 0) | ((np && np[0] == '1') ? 64 : 0) | (sg ? ((atoi(sg) & 255) << 8) : 0) |
-              ((sm && sm[0] == '1') ? 0x10000 : 0);
+              ((sm && sm[0] == '1') ? 0x10000 : 0) | (pt ? 0x20000 : 0);
         fprintf(stderr, "[tetsim] WARNING: ABLATION build of libtetsim_hip (mode 0x%x): timing experiments only, the results are NOT the solver's\n", dbg);
     }
     return static_cast<uint32_t>(dbg);

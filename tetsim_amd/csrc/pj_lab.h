@@ -24,6 +24,14 @@
 #define TETSIM_STAMP(i) do { } while (0)
 #define TETSIM_LAB_SOLVE_TET(cur, rest, q_old, q_new, goal, cc) \
     pj_solve_tet(cur, rest, q_old, q_new, goal, TETSIM_ROTATION_ITERATIONS, true, kLean, !kLean, &cc, d.rot_exit_w2)
+#define TETSIM_LAB_CALL_MARK(sub, n_sub) do { } while (0)
+#define TETSIM_POLL_BEGIN() do { } while (0)
+#define TETSIM_POLL_LOOK() do { } while (0)
+#define TETSIM_POLL_TILE(i) do { } while (0)
+#define TETSIM_POLL_TILE_SAVE() do { } while (0)
+#define TETSIM_POLL_PB(i) do { } while (0)
+#define TETSIM_POLL_PB_FIRST(j0) do { } while (0)
+#define TETSIM_POLL_PB_SAVE() do { } while (0)
 #define TETSIM_LAB_FRAME_BEGIN() do { } while (0)
 #define FRAME_STAMP(i) do { } while (0)
 #define FRAME_POLL() do { } while (0)
@@ -56,6 +64,30 @@
         pj_solve_tet(cur, rest, q_old, q_new, goal, static_cast<int>(dbg & 15u), !(dbg & 64u), kLean, !kLean, &cc, d.rot_exit_w2,   \
                      d.iter_hist ? w2log_ : nullptr);                                                                              \
         if (d.iter_hist) pjb_log_iterations(d.iter_hist, w2log_);                                                                  \
+    } while (0)
+// the looks of the one-launch call (TETSIM_DEBUG_POLL_TRACE = a file, bit 17 of the mode word; tools/call_poll_share.py), for the substep
+// in the MIDDLE of a call, first wave of every workgroup, behind the nb rows of the phase stamps:
+//   one row per tile            {start, first look at the predictions issued, this wave's last look succeeded, every wave's had (barrier),
+//                                partial sums stored, looks of this wave, blockIdx.x, XCC_ID}
+//   one row per particle block  {start, first look at the partial sums issued (their indices are there), every sum carried the stamp,
+//                                the previous position did, results stored, looks of this wave, blockIdx.x, XCC_ID}
+#define TETSIM_LAB_CALL_MARK(sub, n_sub) do { if (!(d.trace && (sub) == (n_sub) / 2u)) dbg &= ~0x20000u; } while (0)
+#define TETSIM_POLL_BEGIN() [[maybe_unused]] unsigned long long pl_looks_ = 1ull
+#define TETSIM_POLL_LOOK() do { pl_looks_++; } while (0)
+#define TETSIM_POLL_TILE(i) do { if (kPoll && (dbg & 0x20000u) && tid == 0) d.trace[8ull * (d.nb + b) + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
+#define TETSIM_POLL_TILE_SAVE() do {                                                                                               \
+        if (kPoll && (dbg & 0x20000u) && tid == 0) {                                                                               \
+            unsigned long long* const row_ = d.trace + 8ull * (d.nb + b);                                                          \
+            row_[5] = pl_looks_; row_[6] = blockIdx.x; row_[7] = __builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11));             \
+        }                                                                                                                          \
+    } while (0)
+#define TETSIM_POLL_PB(i) do { if ((dbg & 0x20000u) && threadIdx.x == 0u) d.trace[8ull * (2ull * d.nb + r) + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
+#define TETSIM_POLL_PB_FIRST(j0) do { if ((j0) == 0u && (dbg & 0x20000u) && threadIdx.x == 0u) { __builtin_amdgcn_s_waitcnt(0x0F70); TETSIM_POLL_PB(1); } } while (0)
+#define TETSIM_POLL_PB_SAVE() do {                                                                                                 \
+        if ((dbg & 0x20000u) && threadIdx.x == 0u) {                                                                               \
+            unsigned long long* const row_ = d.trace + 8ull * (2ull * d.nb + r);                                                   \
+            row_[5] = pl_looks_; row_[6] = blockIdx.x; row_[7] = __builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11));             \
+        }                                                                                                                          \
     } while (0)
 // the frame kernel: thread 0 adds up the cycles of each phase over the call (tools/attic/frame_trace.py)
 #define TETSIM_LAB_FRAME_BEGIN() unsigned long long fr_acc[5] = {0, 0, 0, 0, 0}, fr_last = 0, fr_polls = 0

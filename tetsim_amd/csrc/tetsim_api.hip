@@ -640,6 +640,11 @@ void tetsim_destroy(tetsim_handle h) {
         if (hipMemcpy(tr.data(), h->blk.trace, tr.size() * sizeof(tr[0]), hipMemcpyDeviceToHost) == hipSuccess)
             if (FILE* f = fopen(lab_env("TETSIM_DEBUG_TRACE"), "wb")) { fwrite(tr.data(), sizeof(tr[0]), tr.size(), f); fclose(f); }
     }
+    if (h->blk.trace && lab_env("TETSIM_DEBUG_POLL_TRACE")) {   // (the phase rows, then the rows of the looks: pj_lab.h)
+        std::vector<unsigned long long> tr(8ull * (2ull * h->blk.nb + (h->blk.nv_owned + kBlockTile - 1u) / kBlockTile));
+        if (hipMemcpy(tr.data(), h->blk.trace, tr.size() * sizeof(tr[0]), hipMemcpyDeviceToHost) == hipSuccess)
+            if (FILE* f = fopen(lab_env("TETSIM_DEBUG_POLL_TRACE"), "wb")) { fwrite(tr.data(), sizeof(tr[0]), tr.size(), f); fclose(f); }
+    }
 #ifdef TETSIM_ABLATION
     if (h->blk.iter_hist && lab_env("TETSIM_DEBUG_ITER_HIST")) {   // one text line per body, appended: "<tets> <particles> <278 counters>"
         std::vector<unsigned long long> hs(278);
@@ -716,8 +721,8 @@ int tetsim_step_n(tetsim_handle h, uint32_t n, double dt, const TetSimParams* pa
         if (int rc = tetsim_step_n(h, 32768u, dt, params)) return rc;
         n -= 32768u;
     }
-    if (h->pj_one_launch) {   // (the one-launch call of large polar bodies: n x (tiles + particle workgroups) in one grid of at most 2^32 - 1 work-items, stamps inside one block)
-        const uint32_t most = call_chunk(pjb_call_blocks_per_sub(h->blk.nb, h->blk.nv_owned, kBlockTile), kBlockTile, 8192u);
+    if (h->pj_one_launch) {   // (the one-launch call of large polar bodies: n periods of its dispatch table and the table's tail in one grid of at most 2^32 - 1 work-items, stamps inside one block; every chunk drains)
+        const uint32_t most = pjb_call_chunk(h->call_sched.period, h->call_sched.tail, kBlockTile, 8192u);
         while (n > most) {
             if (int rc = tetsim_step_n(h, most, dt, params)) return rc;
             n -= most;
@@ -755,7 +760,7 @@ int tetsim_step_n(tetsim_handle h, uint32_t n, double dt, const TetSimParams* pa
         // (in turn with an exclusive frame-kernel body, if one lives on this device: see the graph launch below)
         return launch_in_turn(h, [&]() -> int {
             if (h->frame) return launch_frame_kernel(h, n, 0u);
-            pjb_launch_call(h->stream, h->blk, n, h->d_substep_err, halo_timeout_ms(h), h->params_on_device, h->d_params);
+            pjb_launch_call(h->stream, h->blk, h->call_sched, n, h->d_substep_err, halo_timeout_ms(h), h->params_on_device, h->d_params);
             return launched_with_params(h);
         });
     }

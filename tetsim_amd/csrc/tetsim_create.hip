@@ -300,6 +300,18 @@ int create_polar(tetsim_body* h, const float* verts, uint32_t nv, const int32_t*
                 h->info.fused_particle_pass = 5u;
                 if ((rc = dev_alloc(h, &h->d_substep_err, 1))) return rc;
                 HIPCHK(h, hipMemset(h->d_substep_err, 0, sizeof(uint32_t)));
+                // the order of the call's workgroups: TETSIM_PJ_CALL_LAG (read at every creation, like the switch above) = how many tile blocks per XCD
+                // a particle block sits behind the last tile it waits for; 0 = behind every tile of the substep.  A lag that cannot be laid out
+                // gives the plain order (host_prep.cpp: build_call_schedule).
+                const char* lag_env = getenv("TETSIM_PJ_CALL_LAG");
+                const uint32_t lag = lag_env ? static_cast<uint32_t>(std::min<unsigned long>(strtoul(lag_env, nullptr, 10), 1ul << 24)) : kPJCallLagDefault;
+                CallSchedule S;
+                build_call_schedule(B.blk_verts.data(), B.blk_vert_off.data(), B.num_blocks, B.vp_ell.data(), B.vp_cols, B.nv_pad, nvo, lag, &S);
+                if (S.fell_back) fprintf(stderr, "[tetsim] TETSIM_PJ_CALL_LAG=%u ignored (%s): the call runs in the plain order\n", lag, S.why.c_str());
+                uint32_t* dsched;
+                if ((rc = dev_alloc(h, &dsched, S.entry.size()))) return rc;
+                if ((rc = upload(h, dsched, S.entry))) return rc;
+                h->call_sched.entry = dsched; h->call_sched.period = S.period; h->call_sched.tail = S.tail;
             }
         }
         if (h->fused || h->quad) {
@@ -415,9 +427,11 @@ int create_polar(tetsim_body* h, const float* verts, uint32_t nv, const int32_t*
             HIPCHK(h, hipMemset(k.iter_hist, 0, 278 * sizeof(unsigned long long)));
         }
 #endif
-        if (lab_env("TETSIM_DEBUG_TRACE")) {  // development: per-tile phase timestamps of the LAST tet-kernel launch
-            if ((rc = dev_alloc(h, &k.trace, 8ull * B.num_blocks))) return rc;
-            HIPCHK(h, hipMemset(k.trace, 0, 8ull * B.num_blocks * sizeof(unsigned long long)));
+        if (lab_env("TETSIM_DEBUG_TRACE") || lab_env("TETSIM_DEBUG_POLL_TRACE")) {  // development: per-tile phase timestamps of the LAST tet-kernel launch
+            // (TETSIM_DEBUG_POLL_TRACE: behind them one row per tile and one per particle block for the looks of the one-launch call, pj_lab.h)
+            const size_t rows = lab_env("TETSIM_DEBUG_POLL_TRACE") ? 2ull * B.num_blocks + (nvo + kBlockTile - 1u) / kBlockTile : B.num_blocks;
+            if ((rc = dev_alloc(h, &k.trace, 8ull * rows))) return rc;
+            HIPCHK(h, hipMemset(k.trace, 0, 8ull * rows * sizeof(unsigned long long)));
         }
     } else {
         if ((rc = dev_alloc(h, &d.tet_idx, ntl))) return rc;

@@ -102,6 +102,51 @@ int tetsim_prep_slot_table(const int32_t* tets, uint32_t nt, uint32_t nv, int32_
     if (dropped) *dropped = d;
     return 0;
 }
+int tetsim_prep_call_tiles(const float* verts, uint32_t nv, const int32_t* tets, uint32_t nt, uint32_t sizes[4], uint32_t* blk_vert_off,
+                           int32_t* blk_verts, uint32_t* vp_ell) {
+    if (!sizes) return TETSIM_EINVAL;
+    std::string e = validate_mesh(verts, nv, tets, nt, false);
+    if (!e.empty()) return fail(nullptr, TETSIM_EINVAL, e);
+    // particles in the device's numbering (tetsim_create: along a Morton curve), tiles as an unpartitioned body gets them
+    const std::vector<uint32_t> order = morton_vertex_order(verts, nv, 0, nv);
+    std::vector<int32_t> to_dev(nv), ltets(4ull * nt);
+    std::vector<float> lverts(3ull * nv);
+    for (uint32_t i = 0; i < nv; i++) {
+        to_dev[order[i]] = static_cast<int32_t>(i);
+        for (int c = 0; c < 3; c++) lverts[3ull * i + c] = verts[3ull * order[i] + c];
+    }
+    for (uint64_t i = 0; i < 4ull * nt; i++) ltets[i] = to_dev[tets[i]];
+    const Incidence inc = build_incidence(ltets.data(), nt, nv, false, false);
+    BlockPlan B;
+    build_blocks(lverts.data(), ltets.data(), nt, nv, nv, inc, &B);
+    sizes[0] = B.num_blocks; sizes[1] = static_cast<uint32_t>(B.blk_verts.size()); sizes[2] = B.vp_cols; sizes[3] = B.nv_pad;
+    if (blk_vert_off) std::copy(B.blk_vert_off.begin(), B.blk_vert_off.end(), blk_vert_off);
+    if (blk_verts) std::copy(B.blk_verts.begin(), B.blk_verts.end(), blk_verts);
+    if (vp_ell) std::copy(B.vp_ell.begin(), B.vp_ell.begin() + static_cast<std::ptrdiff_t>(static_cast<size_t>(B.vp_cols) * B.nv_pad), vp_ell);
+    return 0;
+}
+int tetsim_prep_call_schedule(const int32_t* blk_verts, const uint32_t* blk_vert_off, uint32_t nb, const uint32_t* vp_ell, uint32_t vp_cols,
+                              uint32_t nv_pad, uint32_t nv_owned, uint32_t lag, uint32_t* entry, uint32_t capacity, uint32_t* period,
+                              uint32_t* tail, int32_t* fell_back) {
+    if (!blk_vert_off || (nb && !blk_verts) || (vp_cols && !vp_ell) || !period || !tail) return TETSIM_EINVAL;
+    if (nv_owned > nv_pad && vp_cols) return fail(nullptr, TETSIM_EINVAL, "tetsim_prep_call_schedule: nv_owned exceeds the column stride of vp_ell");
+    CallSchedule S;
+    build_call_schedule(blk_verts, blk_vert_off, nb, vp_ell, vp_cols, nv_pad, nv_owned, lag, &S);
+    *period = S.period; *tail = S.tail;
+    if (fell_back) *fell_back = S.fell_back ? 1 : 0;
+    if (S.fell_back) fail(nullptr, TETSIM_OK, "tetsim_prep_call_schedule: " + S.why + " -- the plain order instead");   // (reported, not an error: tetsim_last_error)
+    if (entry) {
+        if (capacity < S.period) return fail(nullptr, TETSIM_EINVAL, "tetsim_prep_call_schedule: the table needs " + std::to_string(S.period) + " entries");
+        std::copy(S.entry.begin(), S.entry.end(), entry);
+    }
+    return 0;
+}
+int tetsim_prep_check_call_schedule(const int32_t* blk_verts, const uint32_t* blk_vert_off, uint32_t nb, const uint32_t* vp_ell, uint32_t vp_cols,
+                                    uint32_t nv_pad, uint32_t nv_owned, const uint32_t* entry, uint32_t period, uint32_t tail) {
+    if (!blk_vert_off || (nb && !blk_verts) || (vp_cols && !vp_ell) || !entry) return TETSIM_EINVAL;
+    const std::string bad = check_call_schedule(blk_verts, blk_vert_off, nb, vp_ell, vp_cols, nv_pad, nv_owned, entry, period, tail);
+    return bad.empty() ? 0 : fail(nullptr, TETSIM_EINVAL, "call schedule: " + bad);
+}
 int tetsim_prep_ref_grab_texels(int32_t grab_id, uint32_t num_elems, uint32_t num_particles, int32_t out[2]) {
     if (!out) return TETSIM_EINVAL;
     ref_grab_texels(grab_id, num_elems, num_particles, out);
