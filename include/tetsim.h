@@ -688,6 +688,89 @@ int tetsim_raycast_visual_device(tetsim_handle h,
 /* one row of 4 doubles per body (centre xyz, radius) into DEVICE memory; stride 0 = packed 32, else a multiple of 8, >= 32 */
 int tetsim_visual_bounding_spheres_device(tetsim_handle h, void *dst, uint64_t row_stride, void *caller_stream);
 
+/* --- per-tet strain on the device: deformation gradient, volume ratio, principal stretches ------ */
+
+/* How deformed the material is: per tet the deformation gradient the reference's solveElem computes and throws away (Softbody.js:103-109,
+ * 159), its determinant, the principal stretches and a scalar strain to colour a mesh by; per body how far it is stretched and whether it
+ * has been crushed; per visual vertex one of those values.  All of it in the caller's DEVICE memory, with no host synchronisation, from the
+ * library's own invRestPose.  An ADDITIVE extension of ABI version 5 (TETSIM_ABI_VERSION is unchanged; no existing struct changed): look
+ * the symbols up.
+ *
+ * DEFINITIONS.  All arithmetic is f64 on the stored f32 values -- the positions tetsim_read_positions returns and the f32 invRestPose B
+ * tetsim_prep_rest returns (column-major: B_ij = inv_rest_pose[9 * tet + 3 * j + i]) --, every operation rounded on its own (no fused
+ * multiply-add), sums left to right as written, and only + - * / sqrt, so that tests/strain_ref.py gives the same bits in numpy.  Per tet
+ * with corners 0..3 in the caller's numbering (a batch: the concatenation), x_k the current positions:
+ *   P       column k = x_(k+1) - x_0:  P_ik = x_(k+1)[i] - x_0[i]
+ *   F       = P * B:  F_ij = (P_i0*B_0j + P_i1*B_1j) + P_i2*B_2j                             (9 floats, column-major: F_ij at F + 3 * j + i)
+ *   J       = (F00*(F11*F22 - F12*F21) - F01*(F10*F22 - F12*F20)) + F02*(F10*F21 - F11*F20)
+ *   C       = F^T F, each pair once:  C_ij = (F0i*F0j + F1i*F1j) + F2i*F2j   (i <= j)
+ *   DEV     = sqrt((C00 + C11) + C22)                                                          the reference's r_s; sqrt 3 at rest
+ *   GREEN   = the Frobenius norm of E = (C - I) / 2:  E_ii = (C_ii - 1) / 2, E_ij = C_ij / 2, and
+ *             GREEN = sqrt(((((E00*E00 + E11*E11) + E22*E22) + 2*(E01*E01)) + 2*(E02*E02)) + 2*(E12*E12))      0 for any rigid motion
+ *   STRETCH = sqrt(e < 0 ? 0 : e) of the three diagonal entries e of C after the Jacobi procedure below, then put in DESCENDING order by
+ *             three compare-and-swaps (0,1), (0,2), (1,2) that swap where the earlier value is smaller (3 floats)
+ * Values are rounded to f32 once, at the store.  RESERVED is written as 0.
+ * A DEGENERATE tet -- its rest volume (the observation's V0, above) is 0, or its invRestPose holds a non-finite value; found once on the
+ * host -- gives NaN in 0..14.
+ *
+ * THE JACOBI PROCEDURE.  TETSIM_STRAIN_SWEEPS cyclic sweeps over the pairs (0,1), (0,2), (1,2), no convergence test: a NaN terminates
+ * and every lane does the same work.  For a pair (p,q), r the third index:  nothing if C_pq == 0;  otherwise
+ *   theta = (C_qq - C_pp) / (2*C_pq)      t = sgn(theta) / (|theta| + sqrt(theta*theta + 1)), sgn(0) = +1
+ *   c = 1 / sqrt(t*t + 1)                 s = t*c
+ *   C_pp -= t*C_pq     C_qq += t*C_pq     (C_rp, C_rq) <- (c*C_rp - s*C_rq, s*C_rp + c*C_rq)     C_pq = 0
+ * WHY 4 SWEEPS.  It is the smallest count at which tests/strain_ref.py agrees with numpy.linalg.svd on the inputs of
+ * tests/test_strain_cpu.py (4,000 seeded F with condition numbers up to 1e6, near-equal pairs, rank 1 and 2, J < 0; the stepped Dragon
+ * states of tests/golden) within that test's margin: with d = (24 * sweeps + 8) * 2^-53 * trace(C) for the eigenvalues, a stretch is
+ * within min(d / sigma, sqrt(d)) + 4 * 2^-53 * sigma_max of LAPACK's sigma.  Observed at 4 sweeps: 0.11 of that margin at worst (3 sweeps:
+ * 22 times the margin on the seeded set, 1,000 times on a Dragon state), the off-diagonal entries left behind below 3e-7 * 2^-53 *
+ * trace(C), and the largest |stretch - sigma| / sigma_max = 1.2e-8, on a rank-2 F, where a square root of a rounding error is all any
+ * method through C can give.
+ *
+ * THE BODY ROW (tetsim_body_strain_device): TETSIM_STRAIN_BODY_WIDTH doubles per body of the handle, reduced from the f64 values before
+ * they are rounded to f32:  [0] the largest stretch, [1] the smallest stretch, [2] min J, [3] max J, [4] max GREEN,
+ * [5] the sum of |V0| * (GREEN*GREEN), [6] the sum of |V0|, [7] the number of tets LEFT OUT of all of these: the degenerate ones and
+ * those with a non-finite value in 0..14 of their f32 row (a count, reduced as an integer and stored as a double).  A body without usable
+ * tets reports -inf, +inf, +inf, -inf, -inf, 0, 0, n.  The reduction is the observation's: chunks of 256 tets counted from the body's own
+ * first tet, a fixed tree inside a chunk, the chunks' partial rows in index order by the same tree, no floating-point atomics -- a body of
+ * a batch gives the bits it gives alone, and two calls give the same bits.  The per-tet rows are not materialised.
+ *
+ * VISUAL STRAIN (tetsim_visual_strain_device): one float per attached visual row at dst + row * row_stride: channel `channel` (0..14) of
+ * the tet visVerts[row].tetNr, bit for bit the value of that tet's row.
+ *
+ * Row t of dst = tet t in the caller's numbering at dst + t * row_stride (row b = body b for the body row); only the payload of a row is
+ * written -- not the padding of a wider row, not a byte outside the rows.  THE STREAM CONTRACT is that of tetsim_export_device: the
+ * handle's stream waits for caller_stream, the work runs behind every substep enqueued so far, caller_stream waits for it; no host
+ * synchronisation.  Only a handle's first strain call may block: it builds the constant per-tet table on the host (64 bytes per tet: the
+ * four particle ids, the nine f32 of invRestPose, the degenerate mark, |V0|) and uploads it with the scratch of the partial rows and the
+ * rows of the host read (the first visual call: the rows' tets); all of it counts into TetSimInfo.device_bytes from then on.
+ * tetsim_read_tet_strain writes the tet rows to host memory, out[num_elems * TETSIM_STRAIN_WIDTH], and synchronises.
+ * THE KERNEL.  One lane per tet, 256 per workgroup; a lane reads its record as four 16-byte loads and gathers four corners.  Packed rows
+ * (row_stride 64) at a 16-byte aligned dst pass through LDS and leave as 16-byte stores that cover contiguous memory wave by wave;
+ * anything else leaves as dword stores per row.  The same bits either way.
+ *
+ * Every error is found before anything is enqueued and leaves `dst` as it was.  TETSIM_EINVAL: a NULL handle, dst or out; a dst that is
+ * not 4-byte aligned (body row: 8-byte); a row_stride that is neither 0 (packed: 64; visual: 4) nor a multiple of 4 (body row: 8) of at
+ * least the row's bytes; a dst that hipPointerGetAttributes does not report as device memory of the handle's device, or whose rows do not
+ * fit the allocation it points into; a channel outside 0..14.  TETSIM_ESTATE: a partitioned body; tetsim_visual_strain_device without a
+ * visual mesh.  A handle with 0 tets succeeds: no tet rows are written (the body row reports "no usable tets").
+ * Out of scope: partitioned bodies; a Node binding; energies that need compliances; stress; gradients; a body mask. */
+#define TETSIM_STRAIN_WIDTH 16        /* floats per tet row: 64 bytes */
+#define TETSIM_STRAIN_BODY_WIDTH 8    /* doubles per body row: 64 bytes */
+#define TETSIM_STRAIN_SWEEPS 4        /* cyclic Jacobi sweeps behind STRETCH */
+enum { TETSIM_STRAIN_F = 0 /*..8, column-major*/, TETSIM_STRAIN_J = 9, TETSIM_STRAIN_DEV = 10,
+       TETSIM_STRAIN_STRETCH = 11 /*..13, descending*/, TETSIM_STRAIN_GREEN = 14, TETSIM_STRAIN_RESERVED = 15 /* written as 0 */ };
+/* row t of dst (DEVICE memory, f32) = tet t in the caller's numbering; ordered against caller_stream exactly as tetsim_export_device */
+int tetsim_tet_strain_device(tetsim_handle h, void *dst, uint64_t row_stride, void *caller_stream);
+/* the same rows into host memory [num_elems * TETSIM_STRAIN_WIDTH]; synchronises */
+int tetsim_read_tet_strain(tetsim_handle h, float *out);
+/* row b of dst (DEVICE memory, f64) = body b of the handle */
+int tetsim_body_strain_device(tetsim_handle h, void *dst, uint64_t row_stride, void *caller_stream);
+/* one float per attached visual row (DEVICE memory): channel `channel` of the row's tet */
+int tetsim_visual_strain_device(tetsim_handle h, int32_t channel, void *dst, uint64_t row_stride, void *caller_stream);
+/* Host only, no device: the constant per-tet table those calls build, records_out[nt * 64 bytes].  A record is { int32 ids[4]; float
+ * inv_rest_pose[9] (what tetsim_prep_rest returns for the tet); uint32 degenerate (0 / 1); double abs_v0 }. */
+int tetsim_prep_strain_table(const float *verts, uint32_t nv, const int32_t *tets, uint32_t nt, double density, void *records_out);
+
 /* --- measurement ----------------------------------------------------------------------------- */
 
 /* Run n substeps eagerly on the handle's own stream; every POLAR_JACOBI kernel carries its own begin/end HIP

@@ -26,6 +26,9 @@ MAX_EXPORT_FIELDS = 8
 OBS_WIDTH = 20
 (OBS_MASS, OBS_COM, OBS_VCOM, OBS_VOLUME, OBS_REST_VOLUME, OBS_MIN_VOLUME_RATIO, OBS_INVERTED_TETS, OBS_AABB_MIN, OBS_AABB_MAX, OBS_MAX_SPEED2,
  OBS_NONFINITE, OBS_RESERVED) = 0, 1, 4, 7, 8, 9, 10, 11, 14, 17, 18, 19
+# floats of a tet's row of tetsim_tet_strain_device (and where each quantity starts in it), doubles of a body's row of tetsim_body_strain_device
+STRAIN_WIDTH, STRAIN_BODY_WIDTH, STRAIN_SWEEPS = 16, 8, 4
+STRAIN_F, STRAIN_J, STRAIN_DEV, STRAIN_STRETCH, STRAIN_GREEN, STRAIN_RESERVED = 0, 9, 10, 11, 14, 15
 
 
 class TetSimParams(C.Structure):
@@ -136,6 +139,7 @@ SYMBOLS = [
     "tetsim_snapshot_create", "tetsim_snapshot_capture", "tetsim_snapshot_restore", "tetsim_snapshot_destroy",
     "tetsim_observe_bodies_device", "tetsim_read_body_observations",
     "tetsim_raycast_visual_device", "tetsim_visual_bounding_spheres_device",
+    "tetsim_tet_strain_device", "tetsim_read_tet_strain", "tetsim_body_strain_device", "tetsim_visual_strain_device", "tetsim_prep_strain_table",
     "tetsim_mesh_write", "tetsim_mesh_open", "tetsim_mesh_arrays", "tetsim_mesh_close", "tetsim_create_from_file",
 ]
 
@@ -144,7 +148,8 @@ OPTIONAL_SYMBOLS = ("tetsim_set_colliders", "tetsim_raycast_visual", "tetsim_sta
                     "tetsim_export_device", "tetsim_import_device",
                     "tetsim_snapshot_create", "tetsim_snapshot_capture", "tetsim_snapshot_restore", "tetsim_snapshot_destroy",
                     "tetsim_observe_bodies_device", "tetsim_read_body_observations",
-                    "tetsim_raycast_visual_device", "tetsim_visual_bounding_spheres_device")
+                    "tetsim_raycast_visual_device", "tetsim_visual_bounding_spheres_device",
+                    "tetsim_tet_strain_device", "tetsim_read_tet_strain", "tetsim_body_strain_device", "tetsim_visual_strain_device", "tetsim_prep_strain_table")
 
 _lib = None
 
@@ -231,6 +236,12 @@ def lib():
     if hasattr(L, "tetsim_raycast_visual_device"):   # (additive to ABI 5; rays, bodies, hits and the stream travel as plain addresses)
         L.tetsim_raycast_visual_device.argtypes = [H, C.c_void_p, C.c_uint64, C.c_void_p, u32, C.c_void_p, C.c_uint64, C.c_void_p]
         L.tetsim_visual_bounding_spheres_device.argtypes = [H, C.c_void_p, C.c_uint64, C.c_void_p]
+    if hasattr(L, "tetsim_tet_strain_device"):   # (additive to ABI 5; dst and the stream travel as plain addresses)
+        L.tetsim_tet_strain_device.argtypes = [H, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.tetsim_read_tet_strain.argtypes = [H, fp]
+        L.tetsim_body_strain_device.argtypes = [H, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.tetsim_visual_strain_device.argtypes = [H, i32, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.tetsim_prep_strain_table.argtypes = [fp, u32, ip, u32, dbl, C.c_void_p]
     L.tetsim_profile.argtypes = [H, u32, dbl, PP, C.POINTER(TetSimProfile)]
     L.tetsim_time_kernels.argtypes = [H, u32, dbl, PP, C.POINTER(TetSimProfile)]
     L.tetsim_time_step_n.argtypes = [H, u32, dbl, PP, dp]

@@ -39,6 +39,8 @@ UNITS = {
     "snapshot.hip": ["-ffp-contract=off"],
     # f64 sums of products whose error bound counts every rounding (tests/observe_ref.py), and min / max / squares that are compared bit for bit
     "observe.hip": ["-ffp-contract=off"],
+    # only + - * / sqrt in f64, each rounded on its own: tests/strain_ref.py reproduces the rows bit for bit in numpy
+    "strain.hip": ["-ffp-contract=off"],
     "tetsim_create.hip": ["-ffp-contract=off"],
     "tetsim_halo.hip": ["-ffp-contract=off"],
     "tetsim_comm.hip": ["-ffp-contract=off"],

@@ -10,6 +10,8 @@
 //   snapshot.hip       the complete state kept in device memory: capture and restore of chosen bodies (tetsim_snapshot_*), one copy kernel
 //   observe.hip        per-body observations on the device (tetsim_observe_bodies_device): mass centre, volume, tet health, bounds -- two
 //                      launches over a constant per-tet table, a fixed reduction tree
+//   strain.hip         per-tet strain on the device (tetsim_tet_strain_device / _body_strain_device / _visual_strain_device): deformation
+//                      gradient, stretches, Green strain -- one lane per tet over a constant 64-byte record, the observation's reduction tree
 //   tetsim_measure.hip measurement: per-kernel profile, kernel timing loops, device copy bandwidth
 //   tetsim_create.hip  construction of the two solvers' device state (host preprocessing -> uploads)
 //   tetsim_halo.hip    multi-GPU: per-substep halo choreography (two queues, flag or event synchronised), in-process group stepping
@@ -152,6 +154,26 @@ struct ObsDev {
     bool ready = false;
 };
 
+// tetsim_tet_strain_device / tetsim_body_strain_device / tetsim_visual_strain_device (strain.hip): the constant tables and the scratch of a
+// handle's strain calls, made by its first one
+// The constant record of a tet (tetsim_prep_strain_table, built once on the host): 64 bytes, read by a lane as four 16-byte loads.
+struct StrainRec {
+    int32_t id[4];        // the four API particle ids
+    float b[9];           // invRestPose, column-major, as tetsim_prep_rest returns it
+    uint32_t degenerate;  // rest volume 0, or a non-finite invRestPose entry
+    double v0_abs;        // |V0|, V0 the observation's
+};
+static_assert(sizeof(StrainRec) == 64 && alignof(StrainRec) == 8, "four dwordx4 loads per record");
+struct StrainDev {
+    const void* table = nullptr;       // [tets] 64-byte records: the four API particle ids, invRestPose, the degenerate mark, |V0|
+    const void *chunks = nullptr, *bodies = nullptr;   // per workgroup its rows; per body its chunks
+    const uint32_t* vis_tet = nullptr; // [num_vis_verts] the tet of every attached visual row (the first visual call)
+    double* partial = nullptr;         // [n_chunks][TETSIM_STRAIN_BODY_WIDTH] partial body rows
+    float* rows = nullptr;             // [tets][TETSIM_STRAIN_WIDTH]: the device side of tetsim_read_tet_strain
+    uint32_t n_chunks = 0;
+    bool ready = false;
+};
+
 }  // namespace tetsim
 
 using namespace tetsim;  // (private header of the ABI's own translation units; the handle type lives in the global namespace)
@@ -283,6 +305,7 @@ struct tetsim_body {
     std::vector<tetsim_body*> group;      // in-process group transport: partition i of the decomposition (or empty)
 
     SkinDev skin;  // embedded visual mesh
+    std::vector<uint32_t> vis_tet;     // the tet (caller's numbering) that carries each attached visual vertex
     std::vector<int32_t> vis_global;   // row of the caller's visVerts behind each attached visual vertex (a partition keeps the rows of the tets it owns)
     bool vis_attached = false;
     uint32_t vis_total = 0;            // rows of the caller's visVerts (a partition keeps num_vis_verts of them)
@@ -301,6 +324,7 @@ struct tetsim_body {
     std::vector<tetsim_snapshot_s*> snapshots;
     uint32_t *d_snap_first_vert = nullptr, *d_snap_first_elem = nullptr, *d_snap_tet_body = nullptr;
     ObsDev obs;                    // tetsim_observe_bodies_device / tetsim_read_body_observations (observe.hip)
+    StrainDev strain;              // tetsim_tet_strain_device / tetsim_body_strain_device / tetsim_visual_strain_device (strain.hip)
     double* d_best = nullptr; uint32_t* d_best_id = nullptr;  // tetsim_start_grab candidates
     // tetsim_raycast_visual / tetsim_read_visual_bounding_sphere (query_kernels.hip): allocated by the first query, grown on demand
     uint32_t* d_sphere = nullptr;
@@ -353,6 +377,19 @@ inline uint32_t body_of_tet(const tetsim_body* h, uint32_t t) {   // t: a tet in
     const std::vector<uint32_t>& first = h->batch_first_tet;
     return first.empty() ? 0u : static_cast<uint32_t>(std::upper_bound(first.begin(), first.end(), t) - first.begin()) - 1u;
 }
+
+// V0 of a tet as the observations and the strain rows define it: dot(r1-r0, cross(r2-r0, r3-r0)) / 6 of the f32 rest positions in f64,
+// with its sign (observe.hip: obs_volume is the same expression on the device); for units built with -ffp-contract=off
+inline double rest_volume(const float* v, const int32_t* t) {
+    const float *a = v + 3 * t[0], *b = v + 3 * t[1], *c = v + 3 * t[2], *d = v + 3 * t[3];
+    const double e1x = static_cast<double>(b[0]) - a[0], e1y = static_cast<double>(b[1]) - a[1], e1z = static_cast<double>(b[2]) - a[2];
+    const double e2x = static_cast<double>(c[0]) - a[0], e2y = static_cast<double>(c[1]) - a[1], e2z = static_cast<double>(c[2]) - a[2];
+    const double e3x = static_cast<double>(d[0]) - a[0], e3y = static_cast<double>(d[1]) - a[1], e3z = static_cast<double>(d[2]) - a[2];
+    const double cx = e2y * e3z - e2z * e3y, cy = e2z * e3x - e2x * e3z, cz = e2x * e3y - e2y * e3x;
+    return ((e1x * cx + e1y * cy) + e1z * cz) / 6.0;
+}
+
+void build_strain_table(const float* verts, uint32_t nv, const int32_t* tets, uint32_t nt, double density, StrainRec* out);   // tetsim_host.cpp
 
 #define HIPCHK(h, call)                                                                                 \
     do {                                                                                                \

@@ -191,16 +191,6 @@ __global__ __launch_bounds__(256) void observe_finish_kernel(const ObsBody* __re
     o[TETSIM_OBS_RESERVED] = 0.0;
 }
 
-// the host's V0 of a tet: the kernel's obs_volume on the rest positions
-double rest_volume(const float* v, const int32_t* t) {
-    const float *a = v + 3 * t[0], *b = v + 3 * t[1], *c = v + 3 * t[2], *d = v + 3 * t[3];
-    const double e1x = static_cast<double>(b[0]) - a[0], e1y = static_cast<double>(b[1]) - a[1], e1z = static_cast<double>(b[2]) - a[2];
-    const double e2x = static_cast<double>(c[0]) - a[0], e2y = static_cast<double>(c[1]) - a[1], e2z = static_cast<double>(c[2]) - a[2];
-    const double e3x = static_cast<double>(d[0]) - a[0], e3y = static_cast<double>(d[1]) - a[1], e3z = static_cast<double>(d[2]) - a[2];
-    const double cx = e2y * e3z - e2z * e3y, cy = e2z * e3x - e2x * e3z, cz = e2x * e3y - e2y * e3x;
-    return ((e1x * cx + e1y * cy) + e1z * cz) / 6.0;
-}
-
 // The constant tables, built and uploaded by the handle's first observation (the only part of a call that blocks, with the export's
 // events and index map): per tet its four API particle ids and V0, per chunk its body and rows, per body its chunks; and the scratch
 // of the partial rows and the rows of the host read.  All of it counts into TetSimInfo.device_bytes from then on.
@@ -216,7 +206,7 @@ int ensure_tables(tetsim_body* h) {
     for (uint32_t e = 0; e < nt; e++) {
         const int32_t* t = &h->h_tets[4ull * e];
         ids[e] = make_int4(t[0], t[1], t[2], t[3]);
-        v0[e] = rest_volume(h->h_verts.data(), t);
+        v0[e] = rest_volume(h->h_verts.data(), t);   // (body.h)
     }
     std::vector<ObsChunk> chunks;
     std::vector<ObsBody> bodies(nb);

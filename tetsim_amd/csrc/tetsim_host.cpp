@@ -3,6 +3,28 @@
 
 using namespace tetsim;
 
+namespace tetsim {
+// The strain calls' constant record of every tet (strain.hip): the caller's corner ids, the f32 invRestPose of prep_rest, |V0| of the
+// observation's rest volume, and the mark of a tet without a usable rest shape.
+void build_strain_table(const float* verts, uint32_t nv, const int32_t* tets, uint32_t nt, double density, StrainRec* out) {
+    std::vector<float> inv_mass(nv), irp(9ull * nt), irv(nt);
+    prep_rest(verts, nv, tets, nt, density, inv_mass.data(), irp.data(), irv.data());
+    for (uint32_t e = 0; e < nt; e++) {
+        StrainRec& r = out[e];
+        const int32_t* t = &tets[4ull * e];
+        const double v0 = rest_volume(verts, t);
+        bool finite = true;
+        for (uint32_t k = 0; k < 9u; k++) {
+            r.b[k] = irp[9ull * e + k];
+            finite = finite && std::isfinite(r.b[k]);
+        }
+        for (uint32_t k = 0; k < 4u; k++) r.id[k] = t[k];
+        r.degenerate = (v0 == 0.0 || !finite) ? 1u : 0u;
+        r.v0_abs = std::fabs(v0);
+    }
+}
+}  // namespace tetsim
+
 extern "C" {
 
 // ---- .tetsim mesh container ---------------------------------------------------------------------------------------
@@ -223,6 +245,17 @@ int tetsim_prep_rest(const float* verts, uint32_t nv, const int32_t* tets, uint3
     std::string e = validate_mesh(verts, nv, tets, nt, false);
     if (!e.empty()) return fail(nullptr, TETSIM_EINVAL, e);
     prep_rest(verts, nv, tets, nt, density, inv_mass, inv_rest_pose, inv_rest_volume);
+    return 0;
+}
+
+// the strain calls' per-tet records (strain.hip; include/tetsim.h: tetsim_prep_strain_table)
+int tetsim_prep_strain_table(const float* verts, uint32_t nv, const int32_t* tets, uint32_t nt, double density, void* records_out) {
+    if (nt && !records_out) return TETSIM_EINVAL;
+    std::string e = validate_mesh(verts, nv, tets, nt, false);
+    if (!e.empty()) return fail(nullptr, TETSIM_EINVAL, e);
+    std::vector<StrainRec> recs(nt);
+    build_strain_table(verts, nv, tets, nt, density, recs.data());
+    if (nt) std::memcpy(records_out, recs.data(), recs.size() * sizeof(StrainRec));
     return 0;
 }
 

@@ -32,6 +32,7 @@ int tetsim_set_visual_mesh(tetsim_handle h, const float* vis_verts, uint32_t nvi
     }
     std::vector<int4> corner;
     std::vector<float4> weight, n0;
+    std::vector<uint32_t> vis_tet;
     std::vector<int32_t> qidx, kept, row_body;   // (row_body: batches -- moved into the handle only when the call has succeeded)
     for (uint32_t i = 0; i < nvis; i++) {
         const float tn = vis_verts[4 * i];
@@ -68,6 +69,7 @@ int tetsim_set_visual_mesh(tetsim_handle h, const float* vis_verts, uint32_t nvi
         qidx.push_back(pjs ? tet_pos[el] : 0);
         if (rest_normals) n0.push_back(make_float4(rest_normals[3 * i], rest_normals[3 * i + 1], rest_normals[3 * i + 2], 0.0f));
         kept.push_back(static_cast<int32_t>(i));
+        vis_tet.push_back(e);
         if (is_batch(h)) row_body.push_back(static_cast<int32_t>(body_of_tet(h, e)));   // (ray casts name the body of a hit: the body whose tets carry the row)
     }
     const uint32_t nk = static_cast<uint32_t>(kept.size());
@@ -89,6 +91,7 @@ int tetsim_set_visual_mesh(tetsim_handle h, const float* vis_verts, uint32_t nvi
     k.corner = dc; k.weight = dw; k.qidx = dq; k.normal0 = dn;
     k.nvis = nk;
     h->vis_global = kept;
+    h->vis_tet = vis_tet;
     h->vis_row_body = row_body;
     h->vis_total = nvis;
     h->vis_attached = true;

@@ -122,6 +122,11 @@ _EXPORT_FIELDS = {"pos": (capi.FIELD_POSITIONS, "owned_particles", 3), "vel": (c
                   "visVertexNormals": (capi.FIELD_VISUAL_VERTEX_NORMALS, "num_vis_verts", 3)}
 
 
+# names of the channels of a tet's strain row (visualStrainDevice): F<row><column> is stored column-major
+_STRAIN_CHANNELS = dict({"F%d%d" % (i, j): capi.STRAIN_F + 3 * j + i for i in range(3) for j in range(3)}, J=capi.STRAIN_J, dev=capi.STRAIN_DEV,
+                        stretch0=capi.STRAIN_STRETCH, stretch1=capi.STRAIN_STRETCH + 1, stretch2=capi.STRAIN_STRETCH + 2, green=capi.STRAIN_GREEN)
+
+
 def _check_rows(torch, t, dev, n, width, name):
     """A tensor the device hand-over may read or write: float32 [n, width] on dev, every row contiguous, rows not overlapping."""
     if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != dev or tuple(t.shape) != (n, width)
@@ -502,6 +507,68 @@ class SoftBodyHIP:
         """observeBodies() on the host: a numpy float64 [num_bodies, 20] array.  Synchronises."""
         out = np.empty((self.info.num_bodies, capi.OBS_WIDTH), dtype=np.float64)
         capi.check(self._L.tetsim_read_body_observations(self._h, out.ctypes.data_as(C.POINTER(C.c_double))), self._h)
+        return out
+
+    # -- per-tet strain (include/tetsim.h: tetsim_tet_strain_device / _body_strain_device / _visual_strain_device) -----------------
+    def _strain_out(self, torch, dev, key, out, n, w, dtype):
+        """The cached tensor of a strain call, or the caller's `out` behind the checks of observeBodies."""
+        if out is None:
+            out = self._export_cache.get(key)
+            if out is None or out.shape[0] != n:
+                out = self._export_cache[key] = torch.empty((n, w), dtype=dtype, device=dev)
+        elif (not isinstance(out, torch.Tensor) or out.dtype != dtype or out.device != dev or tuple(out.shape) != (n, w)
+              or (n and out.stride(1) != 1) or (n > 1 and out.stride(0) < w)):
+            raise ValueError("out must be a %s tensor on %s of shape (%d, %d) with contiguous, non-overlapping rows" % (dtype, dev, n, w))
+        return out
+
+    def tetStrainDevice(self, out=None, stream=None):
+        """torch.float32 [num_elems, 16] on the handle's device, row t = tet t of the caller's numbering: the deformation gradient F
+        (9, column-major), J = det F, DEV (the reference's r_s), the principal stretches (3, descending) and the norm of the Green
+        strain (columns: _capi.STRAIN_*; definitions: include/tetsim.h); a degenerate tet's row is NaN.  No host copy and no
+        synchronisation; `out` and `stream` as in observeBodies."""
+        import torch
+        dev, s = self._torch_stream(torch, stream)
+        n, w = self.info.num_elems, capi.STRAIN_WIDTH
+        out = self._strain_out(torch, dev, "tetStrain", out, n, w, torch.float32)
+        capi.check(self._L.tetsim_tet_strain_device(self._h, out.data_ptr(), 4 * out.stride(0) if n > 1 else 0, s), self._h)
+        return out
+
+    def tetStrain(self):
+        """tetStrainDevice() on the host: a numpy float32 [num_elems, 16] array.  Synchronises."""
+        out = np.empty((self.info.num_elems, capi.STRAIN_WIDTH), dtype=np.float32)
+        capi.check(self._L.tetsim_read_tet_strain(self._h, _fp(out.reshape(-1))), self._h)
+        return out
+
+    def bodyStrainDevice(self, out=None, stream=None):
+        """torch.float64 [num_bodies, 8] on the handle's device: per body the largest and the smallest stretch, min and max J, max GREEN,
+        the sums of |V0| * GREEN^2 and of |V0|, and the number of tets left out (degenerate or non-finite).  The tet rows are not
+        materialised.  `out` and `stream` as in observeBodies."""
+        import torch
+        dev, s = self._torch_stream(torch, stream)
+        n, w = self.info.num_bodies, capi.STRAIN_BODY_WIDTH
+        out = self._strain_out(torch, dev, "bodyStrain", out, n, w, torch.float64)
+        capi.check(self._L.tetsim_body_strain_device(self._h, out.data_ptr(), 8 * out.stride(0) if n > 1 else 0, s), self._h)
+        return out
+
+    def visualStrainDevice(self, channel, out=None, stream=None):
+        """torch.float32 [num_vis_verts] on the handle's device: for every attached visual vertex the value `channel` of the tet that
+        carries it -- what a renderer colours the skinned mesh by.  channel: an index 0..14 or one of _STRAIN_CHANNELS ("J", "dev",
+        "stretch0".."stretch2", "green", "F00".."F22" as F<row><column>).  `out` and `stream` as in observeBodies."""
+        import torch
+        dev, s = self._torch_stream(torch, stream)
+        if isinstance(channel, str):
+            if channel not in _STRAIN_CHANNELS:
+                raise ValueError("channel must be an index 0..14 or one of %s" % sorted(_STRAIN_CHANNELS))
+            channel = _STRAIN_CHANNELS[channel]
+        n = self.info.num_vis_verts
+        if out is None:
+            out = self._export_cache.get("visualStrain")
+            if out is None or out.shape[0] != n:
+                out = self._export_cache["visualStrain"] = torch.empty((n,), dtype=torch.float32, device=dev)
+        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != dev or tuple(out.shape) != (n,)
+              or (n > 1 and out.stride(0) < 1)):
+            raise ValueError("out must be a float32 tensor on %s of shape (%d,) with non-overlapping elements" % (dev, n))
+        capi.check(self._L.tetsim_visual_strain_device(self._h, int(channel), out.data_ptr(), 4 * out.stride(0) if n > 1 else 0, s), self._h)
         return out
 
     # -- embedded visual mesh (Softbody.js:259-277 / SoftbodyGPU.js:424-448), skinned on the device ---------------
