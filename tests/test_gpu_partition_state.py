@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, load_f32, load_mesh
+from skin_ref import skin_f32
 from tetsim_amd import SoftBodyHIP, TetSimError, group_p2p_connect, group_refresh_final, group_step_n, group_visual_vertex_normals, make_lattice
 
 pytestmark = pytest.mark.gpu
@@ -90,15 +91,6 @@ def test_two_layer_ghost_regions_have_no_checkpoint():
         deep[0].saveState()
 
 
-def _host_skin(pos, tets, vis):
-    """The vertex shader's arithmetic (SoftbodyGPU.js:429-435) in numpy f32: ((p0*b0 + p1*b1) + p2*b2) + p3*b3, b3 = 1 - ((b0 + b1) + b2)."""
-    e = vis[:, 0].astype(np.int64)
-    b0, b1, b2 = (vis[:, k].astype(np.float32)[:, None] for k in (1, 2, 3))
-    b3 = np.float32(1.0) - ((b0 + b1) + b2)
-    p = [pos[tets[e, k]] for k in range(4)]
-    return ((p[0] * b0 + p[1] * b1) + p[2] * b2) + p[3] * b3
-
-
 @pytest.mark.parametrize("mesh,parts,precision", [("dragon", 3, "precise"), ("dragon", 4, "fast"), ("lattice", 8, "precise"), ("lattice", 8, "fast")])
 def test_the_partitions_skins_add_up_to_the_whole_visual_mesh(mesh, parts, precision):
     rng = np.random.default_rng(7)
@@ -131,7 +123,7 @@ def test_the_partitions_skins_add_up_to_the_whole_visual_mesh(mesh, parts, preci
         p, n = b.visualPositions(with_normals=True)
         pos[b.visualIds], nrm[b.visualIds] = p, n
     # against the group's own particle positions, skinned on the host with the shader's f32 arithmetic: bit for bit in either precision
-    assert _same(pos, _host_skin(_gather(bodies, len(v)), t, vis))
+    assert _same(pos, skin_f32(_gather(bodies, len(v)), t, vis))
     assert np.abs(np.linalg.norm(nrm, axis=1) - 1.0).max() < 1e-5
     mono = SoftBodyHIP(v, t, None, dict(PP), solver="polar", precision=precision)
     mono.setVisualMesh(vis, n0)
@@ -206,4 +198,4 @@ def test_a_partition_that_keeps_no_row_of_the_visual_mesh():
     group_step_n(bodies, 5, DT, PP)
     group_refresh_final(bodies)
     assert bodies[3].visualPositions().shape == (0, 3) and len(bodies[3].visualIds) == 0
-    assert _same(bodies[0].visualPositions(), _host_skin(_gather(bodies, len(v)), t, vis))
+    assert _same(bodies[0].visualPositions(), skin_f32(_gather(bodies, len(v)), t, vis))

@@ -108,19 +108,9 @@ def test_vertex_normals_golden_is_threejs_computeVertexNormals():
     import os
     import numpy as np
     from conftest import GOLDEN, load_f32
+    from skin_ref import vertex_normals_threejs
     pos = load_f32("dragon_vispos_10.f32").reshape(-1, 3)
     tri = np.fromfile(os.path.join(GOLDEN, "dragon_vistris.u16"), dtype="<u2").astype(np.int64).reshape(-1, 3)
     ref = load_f32("dragon_visnormal_10.f32").reshape(-1, 3)
-    P = pos.astype(np.float64)
-    cb, ab = P[tri[:, 2]] - P[tri[:, 1]], P[tri[:, 0]] - P[tri[:, 1]]
-    face = np.stack([cb[:, 1] * ab[:, 2] - cb[:, 2] * ab[:, 1], cb[:, 2] * ab[:, 0] - cb[:, 0] * ab[:, 2],
-                     cb[:, 0] * ab[:, 1] - cb[:, 1] * ab[:, 0]], axis=1)
-    n = np.zeros_like(pos)
-    for t in range(len(tri)):
-        for v in tri[t]:
-            n[v] = (n[v].astype(np.float64) + face[t]).astype(np.float32)
-    N = n.astype(np.float64)
-    length = np.sqrt(N[:, 0] * N[:, 0] + N[:, 1] * N[:, 1] + N[:, 2] * N[:, 2])
-    length[length == 0] = 1.0
-    out = (N * (1.0 / length)[:, None]).astype(np.float32)
+    out = vertex_normals_threejs(pos, tri)
     assert np.array_equal(out.view(np.uint32), ref.view(np.uint32))
