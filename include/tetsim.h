@@ -464,6 +464,59 @@ typedef struct TetSimCollider {
  * rounded once to f32. */
 int tetsim_set_colliders(tetsim_handle h, const TetSimCollider *colliders, uint32_t count);
 
+/* --- body grabs: one held particle per body of a batch, settable from device memory ------------- */
+
+/* tetsim_set_grab holds ONE particle of the whole concatenation at a point in host memory.  The body-grab table holds one particle
+ * of EVERY body (tetsim_create_batch; a single body is a batch of one), and a GPU-side loop can write it without the host.  An
+ * ADDITIVE extension of ABI version 5 (TETSIM_ABI_VERSION is unchanged; no existing struct changed): look the symbols up.
+ *
+ * While body grabs are ON, particle first_particle[b] + particles[b] of body b is treated in every substep exactly as the particle
+ * named by tetsim_set_grab is treated on that path: POLAR_JACOBI sets it to the target before the clamp, NEOHOOKEAN_GS after clamp
+ * and floor, the colliders skip it.  Nothing else about a substep changes.  THE CONTRACT: body b of a batch with row (i, x) gives
+ * the bits that body b created alone gives with tetsim_set_grab(i, x), for both solvers and both precisions, on every stepping
+ * path.  A handle that never switches body grabs on executes what it always executed plus one uniform branch per particle pass.
+ *
+ * The table lives in device memory owned by the handle (num_bodies rows of 16 bytes and a body index per particle; it counts into
+ * device_bytes).  The first set call allocates it with every row "none"; it is the only call that may block.  A set call writes
+ * the table with one small kernel on the handle's stream, behind every substep enqueued so far; every substep enqueued afterwards
+ * sees it.  tetsim_set_body_grabs_device follows the stream contract of tetsim_import_device: the handle's stream waits for
+ * caller_stream, the kernel runs, caller_stream waits for the kernel; the host never reads the arrays and never synchronises.
+ * Switching OFF (particles == NULL) is host state; it also puts every row back to "none".  The table is not solver state:
+ * checkpoints and snapshots do not hold it, and their sizes do not change.
+ *
+ * Rows the host cannot see are normalised by the device kernel: a particle index outside [0, particles of body b) -- -1 is the
+ * intended spelling -- or a non-finite target component makes THAT row "none" and disturbs no other body.  The host variant
+ * refuses the same cases (other than -1) with TETSIM_EINVAL and leaves the table as it was.
+ *
+ * One kind of grab at a time: with body grabs ON, tetsim_set_grab(id >= 0), tetsim_start_grab and tetsim_start_grab_ray return
+ * TETSIM_ESTATE (tetsim_set_grab(-1) stays legal); switching body grabs ON while a handle grab is set is TETSIM_ESTATE.  Also
+ * TETSIM_ESTATE: any partitioned body; a handle with TETSIM_FLAG_REF_GRAB_TEXEL.  TETSIM_EINVAL: a NULL handle; NULL targets
+ * with non-NULL particles; a stride that is neither 0 nor a multiple of 4 of at least 12; a pointer that is not 4-byte aligned,
+ * that hipPointerGetAttributes does not place on the handle's device, or whose rows do not fit its allocation.  Every error is
+ * found before anything is enqueued.
+ * Cost, measured on an MI355X (tools/body_grabs_cost.py, profiles/body_grabs_cost.txt): never switched on, the benchmark
+ * line is inside the parent's run-to-run spread; 64 Dragons in one batch with every body held against none held, one call of 20
+ * substeps: polar FAST x1.20, Neo-Hookean FAST x0.99-1.02.
+ * Out of scope: more than one grab per body; per-body colliders or parameters; partitioned bodies; gradients; a Node binding. */
+
+/* particles [num_bodies] int32: index INSIDE the body (0 = the body's first particle), -1 = this body is not held.
+ * targets [num_bodies] rows of 3 f32.  particles == NULL: body grabs OFF (targets ignored). */
+int tetsim_set_body_grabs(tetsim_handle h, const int32_t *particles, const float *targets);
+/* The same from DEVICE memory: particles packed int32, targets rows of xyz f32 at targets + b * target_stride (0 = packed 12; else a
+ * multiple of 4, >= 12), body_mask as for tetsim_snapshot_restore (num_bodies bytes, nonzero = take this body's row; NULL = all). */
+int tetsim_set_body_grabs_device(tetsim_handle h, const void *particles, const void *targets, uint64_t target_stride,
+                                 const void *body_mask, void *caller_stream);
+/* The particle of every body nearest to a point, on the device: the counterpart of tetsim_nearest_particle / Grabber.start for a batch.
+ * points: num_bodies rows of xyz f32 (stride 0 = packed 12).  ids [num_bodies] int32 packed: the body-local index of body b's particle
+ * nearest to points[b]; dist2 [num_bodies] f64 packed, or NULL.  The squared distance is a0*a0 + a1*a1 + a2*a2 in f64 on the stored f32
+ * positions of the last enqueued substep, without contraction; a NaN distance is never picked, the lowest index wins among equal
+ * distances: id and dist2 are what tetsim_nearest_particle returns for body b alone in the same state, bit for bit.  A body with no
+ * pickable particle gives -1 and DBL_MAX.  Two launches, no floating-point atomics: two calls give the same bits.  Stream contract and
+ * pointer checks of tetsim_export_device (ids 4-byte, dist2 8-byte aligned); no host synchronisation; TETSIM_ESTATE for partitioned
+ * bodies.  The ids it writes are directly the `particles` argument of tetsim_set_body_grabs_device. */
+int tetsim_nearest_particles_device(tetsim_handle h, const void *points, uint64_t point_stride,
+                                    void *ids, void *dist2, void *caller_stream);
+
 /* --- device-side export and import: results for another GPU program, without a host copy -------- */
 
 /* Whoever consumes the state on the device -- a PyTorch model, a renderer, a training loop that resets a batch of bodies -- gets it
@@ -507,7 +560,7 @@ int tetsim_set_colliders(tetsim_handle h, const TetSimCollider *colliders, uint3
  * VISUAL_NORMALS on a NEOHOOKEAN_GS body (VISUAL_NORMALS also needs the rest normals of tetsim_set_visual_mesh); PREV_POSITIONS on
  * a POLAR_JACOBI body; a visual field without a visual mesh, VISUAL_VERTEX_NORMALS without triangles; any partitioned body (its halo
  * stream and ghosts need a contract of their own).
- * Out of scope: partitioned bodies; element types other than f32; gradients; device-resident grab targets or collider lists. */
+ * Out of scope: partitioned bodies; element types other than f32; gradients; device-resident collider lists. */
 enum { TETSIM_FIELD_POSITIONS = 0, TETSIM_FIELD_VELOCITIES = 1, TETSIM_FIELD_PREV_POSITIONS = 2,
        TETSIM_FIELD_QUATS = 3, TETSIM_FIELD_VISUAL_POSITIONS = 4, TETSIM_FIELD_VISUAL_NORMALS = 5,
        TETSIM_FIELD_VISUAL_VERTEX_NORMALS = 6 };
@@ -568,7 +621,7 @@ int tetsim_import_device(tetsim_handle h, const void *pos, uint64_t pos_stride,
  * Every error is found before anything is enqueued and leaves the state and the snapshot as they were.  TETSIM_EINVAL: a NULL handle,
  * snapshot or `out`; a snapshot of another handle; a mask that hipPointerGetAttributes does not report as device memory of the handle's
  * device, or whose allocation holds fewer than num_bodies bytes from that pointer.  TETSIM_ESTATE: any partitioned body.
- * Out of scope: partitioned bodies; per-body grabs or parameters (a restore does not touch them); snapshots shared between handles; a
+ * Out of scope: partitioned bodies; per-body parameters; the body-grab table (tetsim_set_body_grabs: a restore does not touch it); snapshots shared between handles; a
  * snapshot in caller-owned memory. */
 typedef struct tetsim_snapshot_s *tetsim_snapshot;
 int tetsim_snapshot_create(tetsim_handle h, tetsim_snapshot *out);
@@ -676,8 +729,8 @@ int tetsim_read_body_observations(tetsim_handle h, double *out);
  * partitioned body; with ray_body != NULL a triangle whose three rows belong to different bodies (found once on the host; such a
  * mesh still casts with ray_body == NULL).  count == 0 succeeds and enqueues nothing.
  * Out of scope: partitioned bodies; an acceleration structure; all hits along a ray; back-side or double-side materials; f32 rays or
- * hits; rays attached to a moving frame (the caller transforms them, on the device, before the call); gradients; device-resident grab
- * targets or collider lists; a Node binding (Node has no device tensors). */
+ * hits; rays attached to a moving frame (the caller transforms them, on the device, before the call); gradients; device-resident
+ * collider lists; a Node binding (Node has no device tensors). */
 #define TETSIM_RAY_INVALID (-1)   /* TetSimRayHit.hit of a ray the device refused */
 int tetsim_raycast_visual_device(tetsim_handle h,
         const void *rays,     uint64_t ray_stride,   /* DEVICE: count TetSimRay records (64 B); stride 0 = packed, else a multiple of 8, >= 64 */

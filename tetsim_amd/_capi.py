@@ -140,6 +140,7 @@ SYMBOLS = [
     "tetsim_observe_bodies_device", "tetsim_read_body_observations",
     "tetsim_raycast_visual_device", "tetsim_visual_bounding_spheres_device",
     "tetsim_tet_strain_device", "tetsim_read_tet_strain", "tetsim_body_strain_device", "tetsim_visual_strain_device", "tetsim_prep_strain_table",
+    "tetsim_set_body_grabs", "tetsim_set_body_grabs_device", "tetsim_nearest_particles_device",
     "tetsim_mesh_write", "tetsim_mesh_open", "tetsim_mesh_arrays", "tetsim_mesh_close", "tetsim_create_from_file",
 ]
 
@@ -149,7 +150,8 @@ OPTIONAL_SYMBOLS = ("tetsim_set_colliders", "tetsim_raycast_visual", "tetsim_sta
                     "tetsim_snapshot_create", "tetsim_snapshot_capture", "tetsim_snapshot_restore", "tetsim_snapshot_destroy",
                     "tetsim_observe_bodies_device", "tetsim_read_body_observations",
                     "tetsim_raycast_visual_device", "tetsim_visual_bounding_spheres_device",
-                    "tetsim_tet_strain_device", "tetsim_read_tet_strain", "tetsim_body_strain_device", "tetsim_visual_strain_device", "tetsim_prep_strain_table")
+                    "tetsim_tet_strain_device", "tetsim_read_tet_strain", "tetsim_body_strain_device", "tetsim_visual_strain_device", "tetsim_prep_strain_table",
+                    "tetsim_set_body_grabs", "tetsim_set_body_grabs_device", "tetsim_nearest_particles_device")
 
 _lib = None
 
@@ -242,6 +244,10 @@ def lib():
         L.tetsim_body_strain_device.argtypes = [H, C.c_void_p, C.c_uint64, C.c_void_p]
         L.tetsim_visual_strain_device.argtypes = [H, i32, C.c_void_p, C.c_uint64, C.c_void_p]
         L.tetsim_prep_strain_table.argtypes = [fp, u32, ip, u32, dbl, C.c_void_p]
+    if hasattr(L, "tetsim_set_body_grabs"):   # (additive to ABI 5; device arrays, the mask and the stream travel as plain addresses)
+        L.tetsim_set_body_grabs.argtypes = [H, ip, fp]
+        L.tetsim_set_body_grabs_device.argtypes = [H, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.tetsim_nearest_particles_device.argtypes = [H, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
     L.tetsim_profile.argtypes = [H, u32, dbl, PP, C.POINTER(TetSimProfile)]
     L.tetsim_time_kernels.argtypes = [H, u32, dbl, PP, C.POINTER(TetSimProfile)]
     L.tetsim_time_step_n.argtypes = [H, u32, dbl, PP, dp]

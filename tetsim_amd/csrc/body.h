@@ -12,6 +12,8 @@
 //                      launches over a constant per-tet table, a fixed reduction tree
 //   strain.hip         per-tet strain on the device (tetsim_tet_strain_device / _body_strain_device / _visual_strain_device): deformation
 //                      gradient, stretches, Green strain -- one lane per tet over a constant 64-byte record, the observation's reduction tree
+//   body_grabs.hip     one held particle per body of a batch, set from host or device memory (tetsim_set_body_grabs / _device): the table the
+//                      particle passes read; the nearest particle of every body on the device (tetsim_nearest_particles_device)
 //   tetsim_measure.hip measurement: per-kernel profile, kernel timing loops, device copy bandwidth
 //   tetsim_create.hip  construction of the two solvers' device state (host preprocessing -> uploads)
 //   tetsim_halo.hip    multi-GPU: per-substep halo choreography (two queues, flag or event synchronised), in-process group stepping
@@ -213,6 +215,19 @@ struct tetsim_body {
     uint32_t n_colliders = 0;
     DevColliderF col[kMaxColliders] = {};
     DevColliderD d_col[kMaxColliders] = {};
+    // body grabs (tetsim_set_body_grabs / _device, body_grabs.hip): one held particle per body.  The table -- the body of every particle in
+    // device order, a 16-byte row per body -- is made by the first set call and keeps its addresses (fill_params copies them into
+    // DevParams); ON / OFF is host state and travels as DevParams::body_grabs.  Not solver state: no checkpoint or snapshot holds it.
+    bool body_grabs_on = false;
+    uint32_t* d_grab_body = nullptr;    // [particles]
+    int4* d_grab_rows = nullptr;        // [bodies]
+    uint32_t* d_body_first = nullptr;   // [bodies + 1] first particle of every body in the CALLER's numbering (also tetsim_nearest_particles_device)
+    // tetsim_nearest_particles_device: a body's particles in chunks of 256 -- {body, first particle} per chunk, per body its first chunk, a candidate per chunk
+    uint2* d_near_chunks = nullptr;
+    uint32_t* d_near_first = nullptr;   // [bodies + 1]
+    double* d_near_d2 = nullptr;
+    uint32_t* d_near_id = nullptr;
+    uint32_t near_chunks = 0;
     std::map<uint32_t, hipGraphExec_t> graphs;
     std::vector<void*> allocs;
     std::vector<float> h_verts;
@@ -526,6 +541,7 @@ int check_device_span(tetsim_body* h, const void* ptr, uint64_t need, const std:
 bool record_stride_ok(uint64_t stride, uint64_t row_bytes, uint32_t align);
 int check_device_records(tetsim_body* h, const void* ptr, uint64_t stride, uint32_t rows, uint64_t row_bytes, uint32_t align, const std::string& what);
 extern const char* const kPartitionedIo;           // the refusal of a partitioned body, one text for every device-side call
+extern const char* const kBodyGrabsOn;             // the refusal of the handle's grab while body grabs are on (body_grabs.hip)
 void release_snapshots(tetsim_body* h);            // tetsim_destroy: the snapshots that are left (snapshot.hip)
 
 // ---- construction (tetsim_create.hip)

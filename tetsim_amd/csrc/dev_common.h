@@ -27,7 +27,8 @@ struct DevColliderD {
 // the caller changes dt / physicsParams / grab between frames (kernels read it with scalar loads).
 struct DevParams {
     // f32 view -- POLAR_JACOBI: the reference uploads these as f32 uniforms (SoftbodyGPU.js:614-637)
-    float dt, gravity, friction, pad0;
+    float dt, gravity, friction;
+    uint32_t body_grabs;   // non-zero: the body-grab table below decides which particles are held, grab / grab_local are not looked at (tetsim_set_body_grabs)
     float lo[3], pad1;
     float hi[3], pad2;
     float grab[3];
@@ -39,6 +40,10 @@ struct DevParams {
     // f64 view -- NEOHOOKEAN_GS: JS numbers (Softbody.js:195-240)
     double d_dt, d_gravity, d_friction, d_dev_compliance, d_vol_compliance;
     double d_lo[3], d_hi[3];
+    // body grabs (body_grabs.hip): the body of every particle in DEVICE particle order (constant), and one row per body --
+    // {device particle or -1, target x, y, z as float bits}.  Both null until the handle's first set call; their addresses never change.
+    const uint32_t* grab_body;
+    const int4* grab_rows;
     // kinematic colliders (collide.h): entries [0, n_colliders) are meaningful, in both views.  Behind every field above, so that a
     // body without colliders reads what it always read at the offsets it always read it from.
     DevColliderF col[kMaxColliders];     // f32 view: polar solver, FAST Neo-Hookean
@@ -59,6 +64,19 @@ __device__ __forceinline__ void store_params(DevParams* dst, const DevParams& v)
 #pragma unroll
     for (size_t i = 0; i < kDevParamsHead / 8; i++) d[i] = s[i];
     for (uint32_t k = 0; k < v.n_colliders && k < kMaxColliders; k++) { dst->col[k] = v.col[k]; dst->d_col[k] = v.d_col[k]; }
+}
+
+// Body grabs in a particle pass (tetsim_set_body_grabs): behind ONE uniform branch, the row of the particle's body decides whether particle v
+// (device index) is held and where -- the handle's grab, tested in front of it exactly as ever, names nobody while body grabs are on.  Only a
+// selection: the particle passes that are inlined into several kernels and held to bit-equality get no arithmetic from here, and a handle
+// that never switches body grabs on executes what it always executed plus the branch.  v must be a particle of the body (the tile
+// kernels' idle lanes carry a valid id too).
+__device__ __forceinline__ void body_grab_pick(const DevParams& P, uint32_t v, bool& held, float& x, float& y, float& z) {
+    if (P.body_grabs) {
+        const int4 row = P.grab_rows[P.grab_body[v]];
+        held = row.x == static_cast<int32_t>(v);
+        if (held) { x = __int_as_float(row.y); y = __int_as_float(row.z); z = __int_as_float(row.w); }
+    }
 }
 
 // ---- POLAR_JACOBI device state (all arrays 16-byte elements: one dwordx4 per lane) ----------------

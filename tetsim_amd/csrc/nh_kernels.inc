@@ -199,6 +199,9 @@ struct VParams {
     T dt, gravity, friction, lo[3], hi[3];
     int32_t grab_local;
     float grab[3];
+    uint32_t body_grabs;           // non-zero: the body's row decides (tetsim_set_body_grabs), grab_local / grab are not looked at
+    const uint32_t* grab_body;     // the table's two addresses as values; post_vertex reads a particle's row before anything is stored
+    const int4* grab_rows;
     const DevParams* all;   // the colliders (collide.h)
 };
 __device__ __forceinline__ VParams load_vparams(const DevParams& P) {
@@ -211,6 +214,7 @@ __device__ __forceinline__ VParams load_vparams(const DevParams& P) {
 #pragma unroll
     for (int k = 0; k < 3; k++) { q.lo[k] = static_cast<T>(P.d_lo[k]); q.hi[k] = static_cast<T>(P.d_hi[k]); q.grab[k] = P.grab[k]; }
     q.grab_local = P.grab_local;
+    q.body_grabs = P.body_grabs; q.grab_body = P.grab_body; q.grab_rows = P.grab_rows;
     q.all = &P;
     return q;
 }
@@ -291,8 +295,14 @@ __device__ __forceinline__ void post_vertex(const VParams& P, uint32_t v, float4
         pos.x = fr(static_cast<T>(pos.x) + static_cast<T>(Fx) * m);
         pos.z = fr(static_cast<T>(pos.z) + static_cast<T>(Fz) * m);
     }
-    const bool grabbed = static_cast<int32_t>(v) == P.grab_local;
+    bool grabbed = static_cast<int32_t>(v) == P.grab_local;
     if (grabbed) { pos.x = P.grab[0]; pos.y = P.grab[1]; pos.z = P.grab[2]; }
+    if (P.body_grabs) {   // body grabs (tetsim_set_body_grabs): behind one uniform branch the row of the particle's body decides -- the handle's
+                          // grab names nobody then; the row is read through the VALUES of its addresses, before this particle's stores
+        const int4 row = P.grab_rows[P.grab_body[v]];
+        grabbed = row.x == static_cast<int32_t>(v);
+        if (grabbed) { pos.x = __int_as_float(row.y); pos.y = __int_as_float(row.z); pos.z = __int_as_float(row.w); }
+    }
     if (P.all->n_colliders != 0u && !grabbed) {   // kinematic colliders (collide.h)
 #if TETSIM_FAST
         collide_f32<true>(pos.x, pos.y, pos.z, prev.x, prev.y, prev.z, *P.all);

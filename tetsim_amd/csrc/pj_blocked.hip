@@ -74,8 +74,9 @@ __device__ __forceinline__ VertexOut pjb_vertex_update(f3 acc, float wsum, f3 pr
     const float rw = __builtin_amdgcn_rcpf(wsum);
     f3 p = F3(acc.x * rw, acc.y * rw, acc.z * rw);  // 0 * inf = NaN for a particle without tets, as in the reference
     // P6, SoftbodyGPU.js:340-355
-    const bool grabbed = static_cast<int32_t>(v) == P.grab_local || static_cast<int32_t>(v) == P.grab_local2;
+    bool grabbed = static_cast<int32_t>(v) == P.grab_local || static_cast<int32_t>(v) == P.grab_local2;
     if (grabbed) p = F3(P.grab[0], P.grab[1], P.grab[2]);
+    body_grab_pick(P, v, grabbed, p.x, p.y, p.z);   // (body grabs, dev_common.h: a selection behind one uniform branch, no arithmetic)
     p.x = fminf(fmaxf(p.x, P.lo[0]), P.hi[0]);
     p.y = fminf(fmaxf(p.y, P.lo[1]), P.hi[1]);
     p.z = fminf(fmaxf(p.z, P.lo[2]), P.hi[2]);

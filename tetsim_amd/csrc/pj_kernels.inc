@@ -103,8 +103,9 @@ __global__ __launch_bounds__(256) void TETSIM_SFX(pj_vertex_kernel_)(PJDev d, ui
 
     // P6, :340-355
     const f3 prev = xyz(prev4);  // end of the previous substep == texturePrevPos after P1
-    const bool grabbed = static_cast<int32_t>(v) == P.grab_local || static_cast<int32_t>(v) == P.grab_local2;
+    bool grabbed = static_cast<int32_t>(v) == P.grab_local || static_cast<int32_t>(v) == P.grab_local2;
     if (grabbed) p = F3(P.grab[0], P.grab[1], P.grab[2]);
+    body_grab_pick(P, v, grabbed, p.x, p.y, p.z);   // (body grabs, dev_common.h: a selection behind one uniform branch, no arithmetic)
     p.x = fminf(fmaxf(p.x, P.lo[0]), P.hi[0]);
     p.y = fminf(fmaxf(p.y, P.lo[1]), P.hi[1]);
     p.z = fminf(fmaxf(p.z, P.lo[2]), P.hi[2]);

@@ -148,8 +148,11 @@ __device__ __forceinline__ void pjq_solve(float cur[4], float rest[4], QRot& q, 
 }
 
 // ---- P5's division + P6 + P7 (+ P1, P2 of the next substep) for one component of one particle ---------------------------------
-struct QParams { float dt, rdt, fr, g_dt, lo, hi, grab; int32_t grab0, grab1; const DevParams* all; };   // all: the colliders
-__device__ __forceinline__ QParams load_qparams(const DevParams& P, uint32_t c) {
+struct QParams { float dt, rdt, fr, g_dt, lo, hi, grab; int32_t grab0, grab1; uint32_t body_grabs; const DevParams* all; };   // all: the colliders
+// vid: the lane's particle, the same for the whole call -- with body grabs on (tetsim_set_body_grabs) its body's row is read here, once, and
+// `grab` says it all: the target's component if the particle is held (always finite: body_grabs.hip), NaN if it is not.  (No register
+// beyond those the handle's grab needs: the frame kernel has none to spare.)
+__device__ __forceinline__ QParams load_qparams(const DevParams& P, uint32_t c, uint32_t vid) {
     QParams o;
     o.dt = P.dt;
     o.rdt = __builtin_amdgcn_rcpf(P.dt);
@@ -159,6 +162,11 @@ __device__ __forceinline__ QParams load_qparams(const DevParams& P, uint32_t c) 
     o.hi = c == 0u ? P.hi[0] : c == 1u ? P.hi[1] : P.hi[2];
     o.grab = c == 0u ? P.grab[0] : c == 1u ? P.grab[1] : P.grab[2];
     o.grab0 = P.grab_local; o.grab1 = P.grab_local2;
+    o.body_grabs = P.body_grabs;
+    if (P.body_grabs) {   // (uniform)
+        const int4 row = P.grab_rows[P.grab_body[vid]];
+        o.grab = row.x == static_cast<int32_t>(vid) ? __int_as_float(c == 0u ? row.y : c == 1u ? row.z : row.w) : __uint_as_float(0x7fc00000u);
+    }
     o.all = &P;
     return o;
 }
@@ -166,7 +174,7 @@ struct QVertex { float p, vel, pred; };
 __device__ __forceinline__ QVertex pjq_vertex_update(float acc, float wsum, float prev, const QParams& P, uint32_t vid, uint32_t c) {
     float p = acc * __builtin_amdgcn_rcpf(wsum);   // 0 * inf = NaN for a particle without tets, as in the reference
     // P6, SoftbodyGPU.js:340-355
-    const bool grabbed = static_cast<int32_t>(vid) == P.grab0 || static_cast<int32_t>(vid) == P.grab1;
+    const bool grabbed = P.body_grabs ? P.grab == P.grab : static_cast<int32_t>(vid) == P.grab0 || static_cast<int32_t>(vid) == P.grab1;
     if (grabbed) p = P.grab;
     p = fminf(fmaxf(p, P.lo), P.hi);
     if (dpp<kLane1>(p) < 0.0f) p = c == 1u ? 0.0f : fmaf(prev - p, P.fr, p);   // below the floor: y = 0, x and z rubbed back
@@ -251,7 +259,7 @@ __device__ __forceinline__ void pjq_body(const PJBlk& d, const DevParams& P, con
     float prev = 0.0f, wsum = 1.0f, stage = 0.0f;
     if constexpr (kMode != kModeTet) { prev = comp(d.pos_final[vid], c); wsum = d.wsum[vid]; }
     if constexpr (kMode != kModeVertex) stage = comp(d.pos_pred[vid], c);   // substep 0 starts from the prediction the previous call left
-    const QParams qp = load_qparams(P, c);
+    const QParams qp = load_qparams(P, c, vid);
     const uint32_t epoch = d.epoch ? d.epoch : P.epoch;   // (a direct launch -- tetsim_step -- brings its own block of sequence numbers)
     const int32_t poll_delay = P.poll_delay;
     const uint32_t first = range & 0x7ffu, last = range >> 16;

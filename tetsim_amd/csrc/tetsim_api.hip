@@ -86,6 +86,11 @@ void fill_params(const tetsim_body* h, double dt, const TetSimParams& p, DevPara
             o->grab_local2 = to_device(h->grab_ref[1]);
         } else o->grab_local = to_device(h->grab_global);
     }
+    // body grabs (body_grabs.hip): the switch is host state and goes through push_params' comparison like any parameter; the table's
+    // addresses are null until the handle's first set call and constant from then on
+    o->body_grabs = h->body_grabs_on ? 1u : 0u;
+    o->grab_body = h->d_grab_body;
+    o->grab_rows = h->d_grab_rows;
     o->epoch = h->frame_epoch;
     static const int32_t poll_delay = [] { const char* e = lab_env("TETSIM_QUAD_POLL_DELAY"); return e ? atoi(e) : kQuadPollDelay; }();
     o->poll_delay = poll_delay;

@@ -756,6 +756,61 @@ class SoftBodyHIP:
         arr = make_colliders(list(colliders))
         capi.check(self._L.tetsim_set_colliders(self._h, arr, len(colliders)), self._h)
 
+    # -- body grabs (include/tetsim.h: tetsim_set_body_grabs / _device, tetsim_nearest_particles_device) ---------------
+    def setBodyGrabs(self, particles, targets):
+        """Hold one particle of every body: particles int32 [num_bodies], the index INSIDE the body (-1 = not held), targets float32
+        [num_bodies, 3].  Body b then steps exactly as it would alone with setGrab(particles[b], targets[b]), bit for bit.  None
+        switches body grabs off.  Raises TetSimError(EINVAL) for an index outside its body or a non-finite target (the previous table
+        stays in force), TetSimError(ESTATE) while a handle grab is set."""
+        if particles is None:
+            capi.check(self._L.tetsim_set_body_grabs(self._h, None, None), self._h)
+            return
+        n = self.info.num_bodies
+        p = np.ascontiguousarray(particles, dtype=np.int32).reshape(-1)
+        t = _f32(targets).reshape(-1)
+        if p.size != n or t.size != 3 * n:
+            raise ValueError("particles must hold %d indices and targets %d rows of xyz" % (n, n))
+        capi.check(self._L.tetsim_set_body_grabs(self._h, _ip(p), _fp(t)), self._h)
+
+    def setBodyGrabsDevice(self, particles, targets, bodies=None, stream=None):
+        """setBodyGrabs from device tensors, with no host copy and no synchronisation: particles torch.int32 [num_bodies] (contiguous),
+        targets torch.float32 [num_bodies, 3] (rows contiguous; the row stride is passed through), both on the handle's device and
+        produced on `stream` (as in exportTensors; reusable on it right after the call).  bodies: a mask as in restore -- a body it leaves
+        out keeps its row.  A row the table cannot hold (an index outside its body, a non-finite target) means "not held" for that body."""
+        import torch
+        dev, s = self._torch_stream(torch, stream)
+        n = self.info.num_bodies
+        if (not isinstance(particles, torch.Tensor) or particles.dtype != torch.int32 or particles.device != dev or tuple(particles.shape) != (n,)
+                or not particles.is_contiguous()):
+            raise ValueError("particles must be a contiguous int32 tensor on %s of shape (%d,)" % (dev, n))
+        _check_rows(torch, targets, dev, n, 3, "targets")
+        ptr, keep = self._body_mask(torch, dev, bodies)
+        capi.check(self._L.tetsim_set_body_grabs_device(self._h, particles.data_ptr(), targets.data_ptr(), 4 * targets.stride(0) if n > 1 else 0, ptr, s), self._h)
+        self._mask_keep = keep   # (a converted host sequence lives until the next call: the kernel may not have read it yet)
+
+    def nearestParticlesDevice(self, points, out_ids=None, out_dist2=None, stream=None):
+        """(ids, dist2): per body the index INSIDE the body of its particle nearest to points[b], torch.int32 [num_bodies], and the squared
+        distance, torch.float64 [num_bodies] -- what nearestParticle returns for that body alone in the same state, bit for bit (-1 and
+        DBL_MAX for a body with no pickable particle).  points: torch.float32 [num_bodies, 3] on the handle's device, rows contiguous.
+        No host copy and no synchronisation; `ids` goes straight into setBodyGrabsDevice.  The outputs are allocated once and reused by
+        later calls unless out_ids / out_dist2 supply them (contiguous); `stream` as in exportTensors."""
+        import torch
+        dev, s = self._torch_stream(torch, stream)
+        n = self.info.num_bodies
+        _check_rows(torch, points, dev, n, 3, "points")
+        outs = []
+        for key, out, dtype in (("nearestIds", out_ids, torch.int32), ("nearestDist2", out_dist2, torch.float64)):
+            if out is None:
+                out = self._export_cache.get(key)
+                if out is None:
+                    out = self._export_cache[key] = torch.empty((n,), dtype=dtype, device=dev)
+            elif not isinstance(out, torch.Tensor) or out.dtype != dtype or out.device != dev or tuple(out.shape) != (n,) or not out.is_contiguous():
+                raise ValueError("%s must be a contiguous %s tensor on %s of shape (%d,)" % (key, dtype, dev, n))
+            outs.append(out)
+        capi.check(self._L.tetsim_nearest_particles_device(self._h, points.data_ptr(), 4 * points.stride(0) if n > 1 else 0,
+                                                           outs[0].data_ptr(), outs[1].data_ptr(), s), self._h)
+        return outs[0], outs[1]
+
     # -- measurement ----------------------------------------------------------------------------------
     def profile(self, n, dt, physicsParams=None):
         pp = self.physicsParams if physicsParams is None else physicsParams
