@@ -629,6 +629,71 @@ int tetsim_snapshot_capture(tetsim_handle h, tetsim_snapshot s, const void *body
 int tetsim_snapshot_restore(tetsim_handle h, tetsim_snapshot s, const void *body_mask, void *caller_stream);
 void tetsim_snapshot_destroy(tetsim_snapshot s);
 
+/* --- placement: a rigid motion of chosen bodies' complete state, rows and mask in device memory -------- */
+
+/* A restore puts a body back exactly where the snapshot found it; tetsim_import_device writes positions and velocities and leaves a
+ * POLAR_JACOBI body's per-tet state (quaternion, carried shape) behind.  A PLACEMENT starts an episode somewhere else: every chosen body
+ * b of the handle gets ONE rigid motion, applied to the COMPLETE state -- every section a checkpoint or a snapshot holds -- so that the
+ * body continues as a body that had always been there: randomised start poses, a drop from a new height and orientation, a throw with a
+ * linear and an angular velocity, one environment moved out of another's way.  An ADDITIVE extension of ABI version 5
+ * (TETSIM_ABI_VERSION is unchanged; no existing struct changed): look the symbols up.
+ *
+ * A body's row is TETSIM_PLACE_WIDTH f32: Q (xyzw, any length but 0), PIVOT, OFFSET, LINEAR, ANGULAR (xyz each).  body_mask is as for
+ * tetsim_snapshot_restore: num_bodies bytes, nonzero = chosen; NULL = all.
+ *
+ * DEFINITION.  All arithmetic is f64 on the stored f32 values, every operation rounded on its own (no fused multiply-add); results are
+ * stored as f32 (f32(.) below).  cross is the observations' (above).
+ *   n = sqrt(((qx*qx + qy*qy) + qz*qz) + qw*qw)        (x,y,z,w) = Q / n, component by component
+ *   with xx = x*x, xy = x*y, ... :   m00 = 1 - 2*(yy+zz)   m01 = 2*(xy - wz)     m02 = 2*(xz + wy)
+ *                                    m10 = 2*(xy + wz)     m11 = 1 - 2*(xx+zz)   m12 = 2*(yz - wx)
+ *                                    m20 = 2*(xz - wy)     m21 = 2*(yz + wx)     m22 = 1 - 2*(xx+yy)
+ *   Rot(d)_i = (m_i0*d.x + m_i1*d.y) + m_i2*d.z          c = PIVOT + OFFSET
+ *   positions        r = Rot(p - PIVOT)     p' = f32(r + c)        (NEOHOOKEAN_GS: the previous positions by the same rule)
+ *   velocities       u = LINEAR + cross(ANGULAR, r)     v' = f32(u), or with TETSIM_PLACE_KEEP_VELOCITY  v' = f32(Rot(v) + u)
+ *   quaternions      (POLAR_JACOBI)  q' = f32(qR (x) q), qR = (x,y,z,w), the product in the reference's term order
+ *                    (SoftbodyGPU.js:114-121: q'.x = ((w1*x2 + x1*w2) + y1*z2) - z1*y2, ...); it is not renormalised
+ *   carried shape    (POLAR_JACOBI)  a layout of world-space corners, as the reference's textureElem (the gather formulation): every
+ *                    corner e' = f32(Rot(e - PIVOT) + c).  A layout of corners relative to their own centroid (the blocked formulation:
+ *                    four corners, or the three of TETSIM_FLAG_LEAN_STATE): e' = f32(Rot(e)).  Constant-rest-shape bodies carry none.
+ *   The fourth float of every 16-byte row (inverse volume, inverse mass, sequence numbers) is left as it is; NEOHOOKEAN_GS volError is
+ *   untouched.
+ *   predictions      (POLAR_JACOBI) are state: the chosen bodies are left with pos' + vel' * dt in the re-prediction kernel's arithmetic
+ *                    (f32: a product, then a sum), dt the one the handle's predictions were made with.  The bodies not chosen are not
+ *                    written at all: with a fixed dt they continue bit for bit.  While the handle's predictions are "valid for any dt"
+ *                    (no substep yet) the call marks them stale for the whole handle instead: the next step predicts every particle
+ *                    afresh, which gives a particle of zero velocity its position back.
+ * A TETSIM_FLAG_LEAN_STATE body first brings its stored quaternions up to date on its stream, as a snapshot capture does (no host
+ * wait), then turns shape and quaternion together: the recovery's sign rule keeps seeing a consistent pair.
+ *
+ * A row with a non-finite value or with n == 0 leaves ITS body alone and untouched and disturbs no other, as a row the grab table cannot
+ * hold does; the host variant refuses the same rows of chosen bodies with TETSIM_EINVAL and changes nothing.
+ *
+ * THE STREAM CONTRACT is that of tetsim_import_device: (1) the handle's stream waits for an event recorded on caller_stream -- rows and
+ * mask are complete; (2) ONE kernel moves every section, behind every substep enqueued so far; (3) caller_stream waits for it, so the
+ * caller may reuse rows and mask in stream order.  No host synchronisation; only a handle's first call may block (it uploads the table
+ * that tells every row's body, the snapshots' own; the host variant allocates where its rows wait, num_bodies * 65 bytes that count
+ * into device_bytes).  The host variant copies rows and mask during the call, enqueues the same kernel and does not wait for it.
+ *
+ * Every error is found before anything is enqueued and leaves the state as it was.  TETSIM_EINVAL: a NULL handle or rows; flag bits
+ * other than TETSIM_PLACE_KEEP_VELOCITY; a row_stride that is neither 0 (packed: 64) nor a multiple of 4 of at least 64; rows that are
+ * not 4-byte aligned, that hipPointerGetAttributes does not report as device memory of the handle's device, or that do not fit the
+ * allocation they point into; such a mask.  TETSIM_ESTATE: any partitioned body.
+ * The grab tables, the collider list, snapshots and checkpoints are untouched; a checkpoint saved after a placement holds the placed
+ * state.  A POLAR_JACOBI velocity already holds the next substep's gravity * dt (SoftbodyGPU.js:369-371), and KEEP_VELOCITY turns it
+ * with the rest.  The world clamp and the floor act at the next substep as always.
+ * Cost, measured on an MI355X: tools/place_cost.py, profiles/place_cost.txt.
+ * Out of scope: partitioned bodies; per-body scaling or shear; a Node binding; gradients; placement relative to the mass centre (the
+ * caller passes TETSIM_OBS_COM of tetsim_observe_bodies_device as PIVOT). */
+#define TETSIM_PLACE_WIDTH 16            /* floats per body row: 64 bytes */
+enum { TETSIM_PLACE_Q = 0 /*..3 xyzw*/, TETSIM_PLACE_PIVOT = 4 /*..6*/, TETSIM_PLACE_OFFSET = 7 /*..9*/,
+       TETSIM_PLACE_LINEAR = 10 /*..12*/, TETSIM_PLACE_ANGULAR = 13 /*..15*/ };
+enum { TETSIM_PLACE_KEEP_VELOCITY = 1u << 0 };
+/* rows, body_mask: DEVICE memory of the handle's device; row b at rows + b*row_stride (0 = packed 64; else a multiple of 4, >= 64) */
+int tetsim_place_bodies_device(tetsim_handle h, const void *rows, uint64_t row_stride,
+                               const void *body_mask, uint32_t flags, void *caller_stream);
+/* the same from HOST memory: rows [num_bodies*16] packed, mask num_bodies bytes or NULL */
+int tetsim_place_bodies(tetsim_handle h, const float *rows, const uint8_t *body_mask, uint32_t flags);
+
 /* --- per-body observations on the device: mass centre, bounds, volume, tet health -------- */
 
 /* What decides which bodies of a batch to reset: where each body is, how fast, whether it left the arena, whether a tet turned inside

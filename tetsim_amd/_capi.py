@@ -29,6 +29,10 @@ OBS_WIDTH = 20
 # floats of a tet's row of tetsim_tet_strain_device (and where each quantity starts in it), doubles of a body's row of tetsim_body_strain_device
 STRAIN_WIDTH, STRAIN_BODY_WIDTH, STRAIN_SWEEPS = 16, 8, 4
 STRAIN_F, STRAIN_J, STRAIN_DEV, STRAIN_STRETCH, STRAIN_GREEN, STRAIN_RESERVED = 0, 9, 10, 11, 14, 15
+# floats of a body's row of tetsim_place_bodies / _device (and where each quantity starts in it), and the call's flags
+PLACE_WIDTH = 16
+PLACE_Q, PLACE_PIVOT, PLACE_OFFSET, PLACE_LINEAR, PLACE_ANGULAR = 0, 4, 7, 10, 13
+PLACE_KEEP_VELOCITY = 1
 
 
 class TetSimParams(C.Structure):
@@ -141,6 +145,7 @@ SYMBOLS = [
     "tetsim_raycast_visual_device", "tetsim_visual_bounding_spheres_device",
     "tetsim_tet_strain_device", "tetsim_read_tet_strain", "tetsim_body_strain_device", "tetsim_visual_strain_device", "tetsim_prep_strain_table",
     "tetsim_set_body_grabs", "tetsim_set_body_grabs_device", "tetsim_nearest_particles_device",
+    "tetsim_place_bodies_device", "tetsim_place_bodies",
     "tetsim_mesh_write", "tetsim_mesh_open", "tetsim_mesh_arrays", "tetsim_mesh_close", "tetsim_create_from_file",
 ]
 
@@ -151,7 +156,8 @@ OPTIONAL_SYMBOLS = ("tetsim_set_colliders", "tetsim_raycast_visual", "tetsim_sta
                     "tetsim_observe_bodies_device", "tetsim_read_body_observations",
                     "tetsim_raycast_visual_device", "tetsim_visual_bounding_spheres_device",
                     "tetsim_tet_strain_device", "tetsim_read_tet_strain", "tetsim_body_strain_device", "tetsim_visual_strain_device", "tetsim_prep_strain_table",
-                    "tetsim_set_body_grabs", "tetsim_set_body_grabs_device", "tetsim_nearest_particles_device")
+                    "tetsim_set_body_grabs", "tetsim_set_body_grabs_device", "tetsim_nearest_particles_device",
+                    "tetsim_place_bodies_device", "tetsim_place_bodies")
 
 _lib = None
 
@@ -248,6 +254,9 @@ def lib():
         L.tetsim_set_body_grabs.argtypes = [H, ip, fp]
         L.tetsim_set_body_grabs_device.argtypes = [H, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.tetsim_nearest_particles_device.argtypes = [H, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(L, "tetsim_place_bodies_device"):   # (additive to ABI 5; device rows, the mask and the stream travel as plain addresses)
+        L.tetsim_place_bodies_device.argtypes = [H, C.c_void_p, C.c_uint64, C.c_void_p, u32, C.c_void_p]
+        L.tetsim_place_bodies.argtypes = [H, fp, C.POINTER(C.c_uint8), u32]
     L.tetsim_profile.argtypes = [H, u32, dbl, PP, C.POINTER(TetSimProfile)]
     L.tetsim_time_kernels.argtypes = [H, u32, dbl, PP, C.POINTER(TetSimProfile)]
     L.tetsim_time_step_n.argtypes = [H, u32, dbl, PP, dp]

@@ -14,6 +14,8 @@
 //                      gradient, stretches, Green strain -- one lane per tet over a constant 64-byte record, the observation's reduction tree
 //   body_grabs.hip     one held particle per body of a batch, set from host or device memory (tetsim_set_body_grabs / _device): the table the
 //                      particle passes read; the nearest particle of every body on the device (tetsim_nearest_particles_device)
+//   place.hip          a rigid motion of chosen bodies' complete state, rows and mask in device memory (tetsim_place_bodies / _device): one
+//                      kernel over every section of state_sections(), a row's body from the snapshots' tables
 //   tetsim_measure.hip measurement: per-kernel profile, kernel timing loops, device copy bandwidth
 //   tetsim_create.hip  construction of the two solvers' device state (host preprocessing -> uploads)
 //   tetsim_halo.hip    multi-GPU: per-substep halo choreography (two queues, flag or event synchronised), in-process group stepping
@@ -338,6 +340,9 @@ struct tetsim_body {
     // [bodies + 1] first particle / first tet in device numbering, and for a Neo-Hookean batch the body of every volError entry
     std::vector<tetsim_snapshot_s*> snapshots;
     uint32_t *d_snap_first_vert = nullptr, *d_snap_first_elem = nullptr, *d_snap_tet_body = nullptr;
+    // tetsim_place_bodies (place.hip): where the host variant's rows and mask wait for the kernel, made by its first call
+    float* d_place_rows = nullptr;      // [bodies][TETSIM_PLACE_WIDTH]
+    uint8_t* d_place_mask = nullptr;    // [bodies]
     ObsDev obs;                    // tetsim_observe_bodies_device / tetsim_read_body_observations (observe.hip)
     StrainDev strain;              // tetsim_tet_strain_device / tetsim_body_strain_device / tetsim_visual_strain_device (strain.hip)
     double* d_best = nullptr; uint32_t* d_best_id = nullptr;  // tetsim_start_grab candidates
@@ -543,6 +548,7 @@ int check_device_records(tetsim_body* h, const void* ptr, uint64_t stride, uint3
 extern const char* const kPartitionedIo;           // the refusal of a partitioned body, one text for every device-side call
 extern const char* const kBodyGrabsOn;             // the refusal of the handle's grab while body grabs are on (body_grabs.hip)
 void release_snapshots(tetsim_body* h);            // tetsim_destroy: the snapshots that are left (snapshot.hip)
+int ensure_snapshot_body_tables(tetsim_body* h);   // d_snap_first_vert / _first_elem / _tet_body, uploaded once (snapshot.hip: ensure_body_tables; may block)
 
 // ---- construction (tetsim_create.hip)
 int create_polar(tetsim_body* h, const float* verts, uint32_t nv, const int32_t* tets, uint32_t nt);

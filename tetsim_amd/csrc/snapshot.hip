@@ -203,6 +203,8 @@ void free_snapshot(tetsim_snapshot_s* s) {
 
 }  // namespace
 
+int ensure_snapshot_body_tables(tetsim_body* h) { return ensure_body_tables(h); }   // (place.hip finds a row's body the same way)
+
 void release_snapshots(tetsim_body* h) {   // (tetsim_destroy has drained the queues)
     for (tetsim_snapshot_s* s : h->snapshots) free_snapshot(s);
     h->snapshots.clear();

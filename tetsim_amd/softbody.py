@@ -84,6 +84,20 @@ def rays_tensor(origins, directions, near=0.0, far=np.inf, device="cuda"):
     return torch.from_numpy(rays.view(np.float64).reshape(-1, 8).copy()).to(device)
 
 
+def place_rows(q, pivot=(0.0, 0.0, 0.0), offset=(0.0, 0.0, 0.0), linear=(0.0, 0.0, 0.0), angular=(0.0, 0.0, 0.0)):
+    """float32 [bodies, 16] rows of placeBodies / placeBodiesDevice (include/tetsim.h: TETSIM_PLACE_*): q [bodies, 4] xyzw (any length
+    but 0), pivot, offset, linear, angular [bodies, 3] -- each of them may be a single vector for all bodies.  torch.from_numpy(rows)
+    .to(device) is the tensor placeBodiesDevice reads."""
+    q = np.asarray(q, dtype=np.float32).reshape(-1, 4)
+    parts = [np.asarray(a, dtype=np.float32).reshape(-1, 3) for a in (pivot, offset, linear, angular)]
+    n = max([len(q)] + [len(a) for a in parts])
+    rows = np.empty((n, capi.PLACE_WIDTH), dtype=np.float32)
+    rows[:, capi.PLACE_Q:capi.PLACE_Q + 4] = q
+    for at, a in zip((capi.PLACE_PIVOT, capi.PLACE_OFFSET, capi.PLACE_LINEAR, capi.PLACE_ANGULAR), parts):
+        rows[:, at:at + 3] = a
+    return rows
+
+
 def boundary_surface(tets, nv, verts=None):
     """(visVerts [rows, 4], visTriIds [triangles, 3]) of the tet mesh's boundary, oriented outward, in the reference's visual-mesh
     format -- for bodies without an artist's mesh (include/tetsim.h: tetsim_prep_boundary_surface).  Host only, no GPU needed.
@@ -483,6 +497,38 @@ class SoftBodyHIP:
         """Overwrite the chosen bodies' current state with their part of `snap`: with bodies=None what loadState(saveState() of the capture's
         moment) leaves, bit for bit; with a mask the other bodies are not written.  Arguments as in capture."""
         self._snapshot_call(self._L.tetsim_snapshot_restore, snap, bodies, stream)
+
+    # -- placement (include/tetsim.h: tetsim_place_bodies / _device): a rigid motion of chosen bodies' complete state ----------------
+    def placeBodiesDevice(self, rows, bodies=None, keep_velocity=False, stream=None):
+        """Give every chosen body the rigid motion of its row: rows torch.float32 [num_bodies, 16] on the handle's device (place_rows;
+        rows contiguous, the row stride is passed through), produced on `stream` (as in exportTensors; reusable on it right after the
+        call).  Positions, velocities, predictions, quaternions and carried shapes move together (definition: include/tetsim.h), behind
+        the substeps enqueued so far, with no host copy and no synchronisation.  bodies: a mask as in restore -- a body it leaves out is
+        not written.  keep_velocity: the body's velocities are turned and kept under the row's linear and angular velocity.  A row
+        with a non-finite value or a zero quaternion leaves its body untouched."""
+        import torch
+        dev, s = self._torch_stream(torch, stream)
+        n = self.info.num_bodies
+        _check_rows(torch, rows, dev, n, capi.PLACE_WIDTH, "rows")
+        ptr, keep = self._body_mask(torch, dev, bodies)
+        capi.check(self._L.tetsim_place_bodies_device(self._h, rows.data_ptr(), 4 * rows.stride(0) if n > 1 else 0, ptr,
+                                                      capi.PLACE_KEEP_VELOCITY if keep_velocity else 0, s), self._h)
+        self._mask_keep = keep   # (a converted host sequence lives until the next call: the kernel may not have read it yet)
+
+    def placeBodies(self, rows, bodies=None, keep_velocity=False):
+        """placeBodiesDevice from host arrays: rows float32 [num_bodies, 16] (place_rows), bodies None or a sequence of num_bodies truth
+        values.  Raises TetSimError(EINVAL) for a chosen body's row with a non-finite value or a zero quaternion, and changes nothing."""
+        n = self.info.num_bodies
+        r = _f32(rows).reshape(-1)
+        if r.size != capi.PLACE_WIDTH * n:
+            raise ValueError("rows must hold %d rows of %d floats" % (n, capi.PLACE_WIDTH))
+        m = None
+        if bodies is not None:
+            m = np.ascontiguousarray([bool(b) for b in bodies], dtype=np.uint8)
+            if m.size != n:
+                raise ValueError("bodies must name every one of the %d bodies" % n)
+        capi.check(self._L.tetsim_place_bodies(self._h, _fp(r), m.ctypes.data_as(C.POINTER(C.c_uint8)) if m is not None else None,
+                                               capi.PLACE_KEEP_VELOCITY if keep_velocity else 0), self._h)
 
     # -- per-body observations (include/tetsim.h: tetsim_observe_bodies_device): one row of _capi.OBS_WIDTH doubles per body -------
     def observeBodies(self, out=None, stream=None):
