@@ -750,6 +750,113 @@ int tetsim_observe_bodies_device(tetsim_handle h, void *dst, uint64_t row_stride
 /* the same rows into host memory [num_bodies * TETSIM_OBS_WIDTH]; synchronises */
 int tetsim_read_body_observations(tetsim_handle h, double *out);
 
+/* --- per-body pose on the device: best-fit rotation, angular velocity, rigid-fit residual ------- */
+
+/* Which way up a body is and how it spins: the other half of the rigid state whose first half (mass centre and its velocity) the
+ * observation row holds, and the inverse of tetsim_place_bodies_device -- place a rest body by Q and its pose row reports +-Q.  One row of
+ * TETSIM_POSE_WIDTH doubles per body, in the caller's DEVICE memory, with no host synchronisation (or, through tetsim_read_body_poses,
+ * the same rows on the host).  A read-only query: no solver state changes.  An ADDITIVE extension of ABI version 5 (TETSIM_ABI_VERSION
+ * is unchanged; no existing struct changed): look the symbols up.
+ *
+ * THE TABLE.  Built once on the host in f64, every operation rounded on its own; tetsim_prep_pose_table returns the same values.  With
+ * the observation's V0 and w = (density * V0) / 4 (above, sign kept) and r_i the f32 rest positions:
+ *   m_i = the sum of w over the corners that name particle i, tets in ascending index, corners 0..3 of a tet in that order, from 0.0
+ *   per body, over its own particles in ascending index, from 0.0:  M0 = S m_i,  c0 = (S m_i * r_i) / M0 component by component,
+ *   c0 = 0 if M0 == 0;   q_i = r_i - c0.
+ * A particle's record is { double m, qx, qy, qz }, 32 bytes.
+ *
+ * THE ROW, PART 1: RAW MOMENTS [0..25].  Sums (S) over the body's particles; x, v the stored f32 positions and velocities, m, q the
+ * table's; f64, every operation rounded on its own (no fused multiply-add); dot and cross are the observations'.
+ *   [0]      MASS = S m                [1..3]   MX = S m*x            [4..6]   MV = S m*v
+ *   [7..15]  A, row-major: A_ab = S (m*x_a)*q_b                      (at 7 + 3*a + b)
+ *   [16..18] L0 = S m*cross(x, v)      component by component: m * (x.y*v.z - x.z*v.y), ...
+ *   [19..24] G = S (m*x_a)*x_b for ab = xx, yy, zz, xy, xz, yz
+ *   [25]     Q0 = S m*dot(q, q)
+ * Nothing is filtered: a non-finite particle shows as NaN in its own body's sums and in no other body's.  The reduction is the
+ * observations': a body's particles are cut into chunks of 256 counted from its own first particle, a fixed tree reduces inside a chunk
+ * (lane l takes lane l + 32, 16, .. 1 within a wave of 64, then the four waves as (w0 + w1) + (w2 + w3)), the chunks' rows are reduced
+ * in index order by the same tree (thread t folds rows t, t + 256, .. in that order, from 0.0), and there are no floating-point
+ * atomics.  So two calls give the same bits, and a body of a batch gives the bits it gives alone.
+ *
+ * THE ROW, PART 2: DERIVED VALUES [26..47].  A fixed f64 procedure on the STORED raw values [0..25] and nothing else, with only
+ * + - * / sqrt, comparisons, fabs and negation, every operation rounded on its own and every sum in the order of its parentheses:
+ * tests/pose_ref.py reproduces [26..47] bit for bit in numpy from a row's own [0..25].  (x, y, z = components 0, 1, 2.)
+ *   MASS == 0:  COM = VCOM = OMEGA = L = 0, Q = (0,0,0,1), RESIDUAL = GAP = 0, and nothing below is evaluated.  Otherwise:
+ *   [26..28] COM_a = MX_a / MASS                       [29..31] VCOM_a = MV_a / MASS
+ *   [39..41] L = L0 - cross(COM, MV):   L.x = L0.x - (COM.y*MV.z - COM.z*MV.y), ...          the angular momentum about the mass centre
+ *            Gc_ab = G_ab - (MX_a*MX_b)/MASS  (the six of G)       T = (Gc_xx + Gc_yy) + Gc_zz
+ *            Ic (symmetric):  Ixx = T - Gc_xx, Iyy = T - Gc_yy, Izz = T - Gc_zz, Ixy = -Gc_xy, Ixz = -Gc_xz, Iyz = -Gc_yz
+ *            its adjugate:    a00 = Iyy*Izz - Iyz*Iyz    a01 = Ixz*Iyz - Ixy*Izz    a02 = Ixy*Iyz - Ixz*Iyy
+ *                             a11 = Ixx*Izz - Ixz*Ixz    a12 = Ixy*Ixz - Ixx*Iyz    a22 = Ixx*Iyy - Ixy*Ixy
+ *            det = (Ixx*a00 + Ixy*a01) + Ixz*a02
+ *   [36..38] OMEGA = (adj * L) / det:   OMEGA.x = ((a00*L.x + a01*L.y) + a02*L.z) / det,  .y = ((a01*L.x + a11*L.y) + a12*L.z) / det,
+ *            .z = ((a02*L.x + a12*L.y) + a22*L.z) / det;   det == 0 gives OMEGA = 0                Ic * OMEGA = L
+ *   [32..35] Q (x,y,z,w): the proper rotation R that minimises S m |R q - (x - COM)|^2 (Horn's absolute-orientation quaternion; a
+ *            mirrored body gets its best proper rotation, not a reflection).  With S_ab = A_ba -- the term (MX_a * S m*q_b) / MASS of
+ *            the centred moment is DROPPED: S m*q is 0 up to the rounding of the table and is not part of the row -- the symmetric
+ *              N00 = (Sxx + Syy) + Szz    N01 = Syz - Szy            N02 = Szx - Sxz            N03 = Sxy - Syx
+ *                                         N11 = (Sxx - Syy) - Szz    N12 = Sxy + Syx            N13 = Szx + Sxz
+ *                                                                    N22 = (Syy - Sxx) - Szz    N23 = Syz + Szy
+ *                                                                                               N33 = (Szz - Sxx) - Syy
+ *            is diagonalised by the Jacobi procedure below with V = I accumulating the rotations.  k = the index of the largest diagonal
+ *            entry (found by ascending scan with >, so ties go to the lower index and a NaN leaves k = 0), lambda_max = N_kk,
+ *            (w,x,y,z) = column k of V, divided component by component by n = sqrt(((w*w + x*x) + y*y) + z*z).  The sign: all four are
+ *            negated if w < 0, or if w == 0 and the first non-zero of x, y, z is negative.
+ *   [42]     RESIDUAL = sqrt(e < 0 ? 0 : e),  e = ((T + Q0) - 2*lambda_max) / MASS       the rms distance, in metres, to the best rigid fit
+ *   [43]     GAP = lambda_max - the largest of the other three diagonal entries (ascending scan with >, from the first of them).
+ *            Small against lambda_max: the orientation is ill-defined (flat, collinear, mirrored shapes, a half turn away from a tie)
+ *   [44..47] RESERVED, written as 0
+ *
+ * THE JACOBI PROCEDURE is the strain section's (below), extended to 4x4 with eigenvectors: TETSIM_POSE_SWEEPS cyclic sweeps over the
+ * pairs (0,1), (0,2), (0,3), (1,2), (1,3), (2,3), no convergence test.  For a pair (p,q): nothing if N_pq == 0; otherwise theta, t, c, s
+ * by the strain section's formulas from N_pp, N_qq, N_pq, then
+ *   N_pp -= t*N_pq    N_qq += t*N_pq    N_pq = 0    for the two other indices r (ascending): (N_rp, N_rq) <- (c*N_rp - s*N_rq, s*N_rp + c*N_rq)
+ *   for the four rows k of V:  (V_kp, V_kq) <- (c*V_kp - s*V_kq, s*V_kp + c*V_kq)
+ * WHY 5 SWEEPS.  It is the smallest count at which tests/pose_ref.py agrees with numpy.linalg.eigh on the inputs of
+ * tests/test_pose_cpu.py (4,000 seeded moment sets -- generic, flat, collinear, mirrored, half turns (w = 0), far from the origin -- and
+ * the stepped Dragon states of tests/golden) within that test's margin: d = (48 * sweeps + 16) * 2^-53 * ||N||_F for lambda_max,
+ * 2 * d for GAP and d / GAP for the quaternion (up to sign; sets whose d / GAP exceeds 1e-3 -- the collinear ones -- must report that
+ * small a GAP instead).  Observed at 5 sweeps: 0.033 of the margin at worst for lambda_max, 0.016 for GAP, 0.027 for the quaternion, and
+ * less than 4e-18 * ||N||_F left off the diagonal; at 4 sweeps 6.9e6 times the margin (not converged).
+ * PRECISION.  The moments are taken about the ORIGIN (one pass, no second read of the particles): A, G and L0 carry rounding errors of
+ * about n * 2^-53 * |COM| * |q| per unit mass against a signal of |q|^2, so the rotation loses |COM| / |q| of f64's sixteen digits and
+ * RESIDUAL, a difference of sums, has a floor of about sqrt(n * 2^-53) * |COM|.  A body a kilometre from the origin still has nine
+ * digits of orientation.
+ *
+ * Row b of dst = body b of the handle (tetsim_get_batch_layout), at dst + b * row_stride; only the TETSIM_POSE_WIDTH doubles of a row
+ * are written -- not the padding of a wider row, not a byte outside the rows.  THE STREAM CONTRACT is that of
+ * tetsim_observe_bodies_device: the handle's stream waits for caller_stream, two launches run behind every substep enqueued so far,
+ * caller_stream waits for them.  Only the handle's first pose call may block: it builds the table on the host and uploads it (32 bytes
+ * per particle) with the scratch of the chunk rows (26 doubles per chunk of 256 particles) and the rows of the host read; all of it
+ * counts into TetSimInfo.device_bytes from then on.  tetsim_read_body_poses writes the same rows to host memory,
+ * out[num_bodies * TETSIM_POSE_WIDTH], and synchronises.
+ * THE KERNELS.  One lane per particle, 256 per workgroup: a 32-byte record and two gathered 16-byte rows, 96 bytes per particle, 26
+ * f64 accumulators per lane; one workgroup per body folds the chunk rows, and its first lane runs the derived procedure on the values
+ * it just stored.  Cost, measured on an MI355X against the observation: tools/pose_cost.py, profiles/pose_cost.txt.
+ *
+ * Every error is found before anything is enqueued and leaves `dst` as it was.  TETSIM_EINVAL: a NULL handle, dst or out; a dst that
+ * is not 8-byte aligned; a row_stride that is neither 0 (packed: 384) nor a multiple of 8 of at least 384; a dst that
+ * hipPointerGetAttributes does not report as device memory of the handle's device, or whose rows do not fit the allocation it points
+ * into.  TETSIM_ESTATE: a partitioned body.
+ * Out of scope: partitioned bodies; a body mask; a Node binding; gradients; the inertia in the body's frame; filtering non-finite
+ * particles. */
+#define TETSIM_POSE_WIDTH 48         /* doubles per body row: 384 bytes */
+#define TETSIM_POSE_SWEEPS 5         /* cyclic Jacobi sweeps behind Q */
+enum { TETSIM_POSE_MASS = 0, TETSIM_POSE_MX = 1 /*..3*/, TETSIM_POSE_MV = 4 /*..6*/, TETSIM_POSE_A = 7 /*..15, row-major*/,
+       TETSIM_POSE_L0 = 16 /*..18*/, TETSIM_POSE_G = 19 /*..24: xx yy zz xy xz yz*/, TETSIM_POSE_Q0 = 25,
+       TETSIM_POSE_COM = 26 /*..28*/, TETSIM_POSE_VCOM = 29 /*..31*/, TETSIM_POSE_Q = 32 /*..35 xyzw*/, TETSIM_POSE_OMEGA = 36 /*..38*/,
+       TETSIM_POSE_L = 39 /*..41*/, TETSIM_POSE_RESIDUAL = 42, TETSIM_POSE_GAP = 43, TETSIM_POSE_RESERVED = 44 /*..47, written as 0*/ };
+/* row b of dst (DEVICE memory, f64) = body b of the handle; ordered against caller_stream exactly as tetsim_observe_bodies_device */
+int tetsim_body_poses_device(tetsim_handle h, void *dst, uint64_t row_stride, void *caller_stream);
+/* the same rows into host memory [num_bodies * TETSIM_POSE_WIDTH]; synchronises */
+int tetsim_read_body_poses(tetsim_handle h, double *out);
+/* Host only, no device: the constant per-particle table those calls build, records_out[nv * 32 bytes] = { double m, qx, qy, qz }, and
+ * per body { double c0[3] } into centres_out[3 * num_bodies] (may be NULL).  body_first_vert / body_first_tet: [num_bodies + 1] as
+ * tetsim_create_batch lays them out; both NULL = one body (num_bodies is then taken as 1). */
+int tetsim_prep_pose_table(const float *verts, uint32_t nv, const int32_t *tets, uint32_t nt,
+                           const uint32_t *body_first_vert, const uint32_t *body_first_tet, uint32_t num_bodies,
+                           double density, void *records_out, double *centres_out);
+
 /* --- range sensors on the device: per-body ray casts from device memory ------------------------- */
 
 /* What a depth or touch sensor attached to ONE body of a batch needs: rays, the body each ray belongs to and the hits live in the

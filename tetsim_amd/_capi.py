@@ -26,6 +26,10 @@ MAX_EXPORT_FIELDS = 8
 OBS_WIDTH = 20
 (OBS_MASS, OBS_COM, OBS_VCOM, OBS_VOLUME, OBS_REST_VOLUME, OBS_MIN_VOLUME_RATIO, OBS_INVERTED_TETS, OBS_AABB_MIN, OBS_AABB_MAX, OBS_MAX_SPEED2,
  OBS_NONFINITE, OBS_RESERVED) = 0, 1, 4, 7, 8, 9, 10, 11, 14, 17, 18, 19
+# doubles of a body's row of tetsim_body_poses_device (where each quantity starts in it: [0..25] raw moments, [26..47] derived), its Jacobi sweeps
+POSE_WIDTH, POSE_SWEEPS = 48, 5
+(POSE_MASS, POSE_MX, POSE_MV, POSE_A, POSE_L0, POSE_G, POSE_Q0, POSE_COM, POSE_VCOM, POSE_Q, POSE_OMEGA, POSE_L, POSE_RESIDUAL, POSE_GAP,
+ POSE_RESERVED) = 0, 1, 4, 7, 16, 19, 25, 26, 29, 32, 36, 39, 42, 43, 44
 # floats of a tet's row of tetsim_tet_strain_device (and where each quantity starts in it), doubles of a body's row of tetsim_body_strain_device
 STRAIN_WIDTH, STRAIN_BODY_WIDTH, STRAIN_SWEEPS = 16, 8, 4
 STRAIN_F, STRAIN_J, STRAIN_DEV, STRAIN_STRETCH, STRAIN_GREEN, STRAIN_RESERVED = 0, 9, 10, 11, 14, 15
@@ -142,6 +146,7 @@ SYMBOLS = [
     "tetsim_export_device", "tetsim_import_device",
     "tetsim_snapshot_create", "tetsim_snapshot_capture", "tetsim_snapshot_restore", "tetsim_snapshot_destroy",
     "tetsim_observe_bodies_device", "tetsim_read_body_observations",
+    "tetsim_body_poses_device", "tetsim_read_body_poses", "tetsim_prep_pose_table",
     "tetsim_raycast_visual_device", "tetsim_visual_bounding_spheres_device",
     "tetsim_tet_strain_device", "tetsim_read_tet_strain", "tetsim_body_strain_device", "tetsim_visual_strain_device", "tetsim_prep_strain_table",
     "tetsim_set_body_grabs", "tetsim_set_body_grabs_device", "tetsim_nearest_particles_device",
@@ -157,7 +162,8 @@ OPTIONAL_SYMBOLS = ("tetsim_set_colliders", "tetsim_raycast_visual", "tetsim_sta
                     "tetsim_raycast_visual_device", "tetsim_visual_bounding_spheres_device",
                     "tetsim_tet_strain_device", "tetsim_read_tet_strain", "tetsim_body_strain_device", "tetsim_visual_strain_device", "tetsim_prep_strain_table",
                     "tetsim_set_body_grabs", "tetsim_set_body_grabs_device", "tetsim_nearest_particles_device",
-                    "tetsim_place_bodies_device", "tetsim_place_bodies")
+                    "tetsim_place_bodies_device", "tetsim_place_bodies",
+                    "tetsim_body_poses_device", "tetsim_read_body_poses", "tetsim_prep_pose_table")
 
 _lib = None
 
@@ -257,6 +263,10 @@ def lib():
     if hasattr(L, "tetsim_place_bodies_device"):   # (additive to ABI 5; device rows, the mask and the stream travel as plain addresses)
         L.tetsim_place_bodies_device.argtypes = [H, C.c_void_p, C.c_uint64, C.c_void_p, u32, C.c_void_p]
         L.tetsim_place_bodies.argtypes = [H, fp, C.POINTER(C.c_uint8), u32]
+    if hasattr(L, "tetsim_body_poses_device"):   # (additive to ABI 5; dst and the stream travel as plain addresses)
+        L.tetsim_body_poses_device.argtypes = [H, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.tetsim_read_body_poses.argtypes = [H, dp]
+        L.tetsim_prep_pose_table.argtypes = [fp, u32, ip, u32, C.POINTER(u32), C.POINTER(u32), u32, dbl, C.c_void_p, dp]
     L.tetsim_profile.argtypes = [H, u32, dbl, PP, C.POINTER(TetSimProfile)]
     L.tetsim_time_kernels.argtypes = [H, u32, dbl, PP, C.POINTER(TetSimProfile)]
     L.tetsim_time_step_n.argtypes = [H, u32, dbl, PP, dp]

@@ -41,6 +41,8 @@ UNITS = {
     "observe.hip": ["-ffp-contract=off"],
     # only + - * / sqrt in f64, each rounded on its own: tests/strain_ref.py reproduces the rows bit for bit in numpy
     "strain.hip": ["-ffp-contract=off"],
+    # f64 moments whose error bound counts every rounding, and a derived procedure of + - * / sqrt that tests/pose_ref.py reproduces bit for bit
+    "pose.hip": ["-ffp-contract=off"],
     # the nearest query's f64 squared distance is tetsim_nearest_particle's, compared bit for bit: every multiply and add rounded on its own
     "body_grabs.hip": ["-ffp-contract=off"],
     # the rigid motion is defined in f64 with every operation rounded on its own: tests/place_ref.py reproduces it value for value in numpy

@@ -12,6 +12,8 @@
 //                      launches over a constant per-tet table, a fixed reduction tree
 //   strain.hip         per-tet strain on the device (tetsim_tet_strain_device / _body_strain_device / _visual_strain_device): deformation
 //                      gradient, stretches, Green strain -- one lane per tet over a constant 64-byte record, the observation's reduction tree
+//   pose.hip           per-body pose on the device (tetsim_body_poses_device): mass moments over a constant per-particle table, the best-fit
+//                      rotation (Horn's quaternion by a fixed Jacobi procedure), angular velocity and momentum -- the observation's tree
 //   body_grabs.hip     one held particle per body of a batch, set from host or device memory (tetsim_set_body_grabs / _device): the table the
 //                      particle passes read; the nearest particle of every body on the device (tetsim_nearest_particles_device)
 //   place.hip          a rigid motion of chosen bodies' complete state, rows and mask in device memory (tetsim_place_bodies / _device): one
@@ -174,6 +176,22 @@ struct StrainDev {
     const uint32_t* vis_tet = nullptr; // [num_vis_verts] the tet of every attached visual row (the first visual call)
     double* partial = nullptr;         // [n_chunks][TETSIM_STRAIN_BODY_WIDTH] partial body rows
     float* rows = nullptr;             // [tets][TETSIM_STRAIN_WIDTH]: the device side of tetsim_read_tet_strain
+    uint32_t n_chunks = 0;
+    bool ready = false;
+};
+
+// tetsim_body_poses_device / tetsim_read_body_poses (pose.hip): the constant table and the scratch of a handle's pose calls, made by its
+// first one.  The constant record of a particle (tetsim_prep_pose_table, built once on the host): 32 bytes, read as two 16-byte loads.
+struct PoseRec {
+    double m;             // lumped mass: the sum of (density * V0) / 4 over the corners that name the particle
+    double q[3];          // rest position relative to the body's rest mass centre
+};
+static_assert(sizeof(PoseRec) == 32 && alignof(PoseRec) == 8, "two dwordx4 loads per record");
+struct PoseDev {
+    const void* table = nullptr;       // [particles] 32-byte records in the caller's numbering
+    const void *chunks = nullptr, *bodies = nullptr;   // per workgroup its rows; per body its chunks
+    double* partial = nullptr;         // [n_chunks][26] chunk rows
+    double* rows = nullptr;            // [bodies][TETSIM_POSE_WIDTH]: the device side of tetsim_read_body_poses
     uint32_t n_chunks = 0;
     bool ready = false;
 };
@@ -345,6 +363,7 @@ struct tetsim_body {
     uint8_t* d_place_mask = nullptr;    // [bodies]
     ObsDev obs;                    // tetsim_observe_bodies_device / tetsim_read_body_observations (observe.hip)
     StrainDev strain;              // tetsim_tet_strain_device / tetsim_body_strain_device / tetsim_visual_strain_device (strain.hip)
+    PoseDev pose;                  // tetsim_body_poses_device / tetsim_read_body_poses (pose.hip)
     double* d_best = nullptr; uint32_t* d_best_id = nullptr;  // tetsim_start_grab candidates
     // tetsim_raycast_visual / tetsim_read_visual_bounding_sphere (query_kernels.hip): allocated by the first query, grown on demand
     uint32_t* d_sphere = nullptr;
@@ -410,6 +429,9 @@ inline double rest_volume(const float* v, const int32_t* t) {
 }
 
 void build_strain_table(const float* verts, uint32_t nv, const int32_t* tets, uint32_t nt, double density, StrainRec* out);   // tetsim_host.cpp
+// first_vert: [bodies + 1] first particle of every body; centres: [3 * bodies] the bodies' rest mass centres, or null
+void build_pose_table(const float* verts, uint32_t nv, const int32_t* tets, uint32_t nt, const uint32_t* first_vert, uint32_t bodies, double density,
+                      PoseRec* out, double* centres);   // tetsim_host.cpp
 
 #define HIPCHK(h, call)                                                                                 \
     do {                                                                                                \

@@ -23,6 +23,30 @@ void build_strain_table(const float* verts, uint32_t nv, const int32_t* tets, ui
         r.v0_abs = std::fabs(v0);
     }
 }
+// The pose calls' constant record of every particle (pose.hip; include/tetsim.h, THE TABLE): the lumped mass of the observation's w, corner
+// by corner in tet order, and the rest position relative to its body's rest mass centre.  f64, every operation rounded on its own.
+void build_pose_table(const float* verts, uint32_t nv, const int32_t* tets, uint32_t nt, const uint32_t* first_vert, uint32_t bodies, double density,
+                      PoseRec* out, double* centres) {
+    for (uint32_t i = 0; i < nv; i++) out[i].m = 0.0;
+    for (uint32_t e = 0; e < nt; e++) {
+        const int32_t* t = &tets[4ull * e];
+        const double w = (density * rest_volume(verts, t)) / 4.0;
+        for (uint32_t k = 0; k < 4u; k++) out[t[k]].m = out[t[k]].m + w;
+    }
+    for (uint32_t b = 0; b < bodies; b++) {
+        double m0 = 0.0, s[3] = {0.0, 0.0, 0.0}, c0[3] = {0.0, 0.0, 0.0};
+        for (uint32_t i = first_vert[b]; i < first_vert[b + 1]; i++) {
+            m0 = m0 + out[i].m;
+            for (uint32_t k = 0; k < 3u; k++) s[k] = s[k] + out[i].m * static_cast<double>(verts[3ull * i + k]);
+        }
+        if (m0 != 0.0)
+            for (uint32_t k = 0; k < 3u; k++) c0[k] = s[k] / m0;
+        for (uint32_t i = first_vert[b]; i < first_vert[b + 1]; i++)
+            for (uint32_t k = 0; k < 3u; k++) out[i].q[k] = static_cast<double>(verts[3ull * i + k]) - c0[k];
+        if (centres)
+            for (uint32_t k = 0; k < 3u; k++) centres[3ull * b + k] = c0[k];
+    }
+}
 }  // namespace tetsim
 
 extern "C" {
@@ -256,6 +280,32 @@ int tetsim_prep_strain_table(const float* verts, uint32_t nv, const int32_t* tet
     std::vector<StrainRec> recs(nt);
     build_strain_table(verts, nv, tets, nt, density, recs.data());
     if (nt) std::memcpy(records_out, recs.data(), recs.size() * sizeof(StrainRec));
+    return 0;
+}
+
+// the pose calls' per-particle records (pose.hip; include/tetsim.h: tetsim_prep_pose_table)
+int tetsim_prep_pose_table(const float* verts, uint32_t nv, const int32_t* tets, uint32_t nt, const uint32_t* body_first_vert, const uint32_t* body_first_tet,
+                           uint32_t num_bodies, double density, void* records_out, double* centres_out) {
+    if (nv && !records_out) return TETSIM_EINVAL;
+    if ((body_first_vert == nullptr) != (body_first_tet == nullptr)) return fail(nullptr, TETSIM_EINVAL, "body_first_vert and body_first_tet must both be given or both be NULL");
+    std::string e = validate_mesh(verts, nv, tets, nt, false);
+    if (!e.empty()) return fail(nullptr, TETSIM_EINVAL, e);
+    std::vector<uint32_t> fv = {0u, nv};
+    if (body_first_vert) {
+        if (!num_bodies) return fail(nullptr, TETSIM_EINVAL, "num_bodies is 0");
+        if (body_first_tet[0] != 0 || body_first_vert[0] != 0 || body_first_tet[num_bodies] != nt || body_first_vert[num_bodies] != nv)
+            return fail(nullptr, TETSIM_EINVAL, "body ranges must cover the whole mesh");
+        for (uint32_t b = 0; b < num_bodies; b++) {
+            if (body_first_tet[b] > body_first_tet[b + 1] || body_first_vert[b] > body_first_vert[b + 1]) return fail(nullptr, TETSIM_EINVAL, "body ranges must ascend");
+            for (uint64_t i = 4ull * body_first_tet[b]; i < 4ull * body_first_tet[b + 1]; i++)
+                if (static_cast<uint32_t>(tets[i]) < body_first_vert[b] || static_cast<uint32_t>(tets[i]) >= body_first_vert[b + 1])
+                    return fail(nullptr, TETSIM_EINVAL, "a tet references a particle of another body");
+        }
+        fv.assign(body_first_vert, body_first_vert + num_bodies + 1);
+    }
+    std::vector<PoseRec> recs(nv);
+    build_pose_table(verts, nv, tets, nt, fv.data(), static_cast<uint32_t>(fv.size() - 1), density, recs.data(), centres_out);
+    if (nv) std::memcpy(records_out, recs.data(), recs.size() * sizeof(PoseRec));
     return 0;
 }
 

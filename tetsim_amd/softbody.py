@@ -555,6 +555,32 @@ class SoftBodyHIP:
         capi.check(self._L.tetsim_read_body_observations(self._h, out.ctypes.data_as(C.POINTER(C.c_double))), self._h)
         return out
 
+    # -- per-body pose (include/tetsim.h: tetsim_body_poses_device): one row of _capi.POSE_WIDTH doubles per body --------------------
+    def observePoses(self, out=None, stream=None):
+        """torch.float64 [num_bodies, 48] on the handle's device: per body the mass moments [0..25] and what follows from them -- mass
+        centre and its velocity, the rotation that best maps the rest shape onto the current one (xyzw, w >= 0: what place_rows takes
+        as q), angular velocity and angular momentum about the mass centre, the rms distance to the best rigid fit and the eigenvalue gap
+        that says how well defined the rotation is (columns: _capi.POSE_*; definitions: include/tetsim.h).  `out` and `stream` as in
+        observeBodies: no host copy, no synchronisation, the tensor allocated once and reused unless `out` supplies it."""
+        import torch
+        dev, s = self._torch_stream(torch, stream)
+        n, w = self.info.num_bodies, capi.POSE_WIDTH
+        if out is None:
+            out = self._export_cache.get("poses")
+            if out is None:
+                out = self._export_cache["poses"] = torch.empty((n, w), dtype=torch.float64, device=dev)
+        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or out.device != dev or tuple(out.shape) != (n, w)
+              or out.stride(1) != 1 or (n > 1 and out.stride(0) < w)):
+            raise ValueError("out must be a float64 tensor on %s of shape (%d, %d) with contiguous, non-overlapping rows" % (dev, n, w))
+        capi.check(self._L.tetsim_body_poses_device(self._h, out.data_ptr(), 8 * out.stride(0) if n > 1 else 0, s), self._h)
+        return out
+
+    def bodyPoses(self):
+        """observePoses() on the host: a numpy float64 [num_bodies, 48] array.  Synchronises."""
+        out = np.empty((self.info.num_bodies, capi.POSE_WIDTH), dtype=np.float64)
+        capi.check(self._L.tetsim_read_body_poses(self._h, out.ctypes.data_as(C.POINTER(C.c_double))), self._h)
+        return out
+
     # -- per-tet strain (include/tetsim.h: tetsim_tet_strain_device / _body_strain_device / _visual_strain_device) -----------------
     def _strain_out(self, torch, dev, key, out, n, w, dtype):
         """The cached tensor of a strain call, or the caller's `out` behind the checks of observeBodies."""
