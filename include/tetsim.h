@@ -732,7 +732,9 @@ int tetsim_place_bodies(tetsim_handle h, const float *rows, const uint8_t *body_
  * are written -- not the padding of a wider row, not a byte outside the rows.  THE STREAM CONTRACT is that of tetsim_export_device:
  * the handle's stream waits for caller_stream, two launches run behind every substep enqueued so far, caller_stream waits for them.
  * Only the handle's first observation may block: it builds the constant per-tet table (ids and V0, 24 bytes per tet) on the host and
- * uploads it with the scratch of the partial rows; all of it counts into TetSimInfo.device_bytes from then on.
+ * uploads it with the scratch of the partial rows -- and the handle's two chunk tables (12 bytes per chunk of 256 tets / particles, 8 per
+ * body; shared with the pose, strain and nearest-particle calls, uploaded once by whichever of them comes first); all of it counts into
+ * TetSimInfo.device_bytes from then on.
  * tetsim_read_body_observations writes the same rows to host memory, out[num_bodies * TETSIM_OBS_WIDTH], and synchronises.
  *
  * Every error is found before anything is enqueued and leaves `dst` as it was.  TETSIM_EINVAL: a NULL handle, dst or out; a dst that
@@ -827,7 +829,8 @@ int tetsim_read_body_observations(tetsim_handle h, double *out);
  * are written -- not the padding of a wider row, not a byte outside the rows.  THE STREAM CONTRACT is that of
  * tetsim_observe_bodies_device: the handle's stream waits for caller_stream, two launches run behind every substep enqueued so far,
  * caller_stream waits for them.  Only the handle's first pose call may block: it builds the table on the host and uploads it (32 bytes
- * per particle) with the scratch of the chunk rows (26 doubles per chunk of 256 particles) and the rows of the host read; all of it
+ * per particle) with the scratch of the chunk rows (26 doubles per chunk of 256 particles), the rows of the host read and, unless an
+ * observation or a nearest-particle call made it, the handle's particle chunk table (the observation's; never the tet one); all of it
  * counts into TetSimInfo.device_bytes from then on.  tetsim_read_body_poses writes the same rows to host memory,
  * out[num_bodies * TETSIM_POSE_WIDTH], and synchronises.
  * THE KERNELS.  One lane per particle, 256 per workgroup: a 32-byte record and two gathered 16-byte rows, 96 bytes per particle, 26
@@ -967,7 +970,8 @@ int tetsim_visual_bounding_spheres_device(tetsim_handle h, void *dst, uint64_t r
  * handle's stream waits for caller_stream, the work runs behind every substep enqueued so far, caller_stream waits for it; no host
  * synchronisation.  Only a handle's first strain call may block: it builds the constant per-tet table on the host (64 bytes per tet: the
  * four particle ids, the nine f32 of invRestPose, the degenerate mark, |V0|) and uploads it with the scratch of the partial rows and the
- * rows of the host read (the first visual call: the rows' tets); all of it counts into TetSimInfo.device_bytes from then on.
+ * rows of the host read (the first visual call: the rows' tets) and, unless an observation made it, the handle's tet chunk table (the
+ * observation's); all of it counts into TetSimInfo.device_bytes from then on.
  * tetsim_read_tet_strain writes the tet rows to host memory, out[num_elems * TETSIM_STRAIN_WIDTH], and synchronises.
  * THE KERNEL.  One lane per tet, 256 per workgroup; a lane reads its record as four 16-byte loads and gathers four corners.  Packed rows
  * (row_stride 64) at a 16-byte aligned dst pass through LDS and leave as 16-byte stores that cover contiguous memory wave by wave;

@@ -8,12 +8,13 @@
 //                      index map, what must run first, which requests are errors), the one gather kernel and the staging buffer of the
 //                      host reads that use it; export / import in device memory; every device-side call's guard and ordering against a caller's stream
 //   snapshot.hip       the complete state kept in device memory: capture and restore of chosen bodies (tetsim_snapshot_*), one copy kernel
+//   body_reduce.h      what the four units below share: every body cut into chunks of 256 rows, the fixed reduction tree, the host steps
 //   observe.hip        per-body observations on the device (tetsim_observe_bodies_device): mass centre, volume, tet health, bounds -- two
-//                      launches over a constant per-tet table, a fixed reduction tree
+//                      launches over a constant per-tet table
 //   strain.hip         per-tet strain on the device (tetsim_tet_strain_device / _body_strain_device / _visual_strain_device): deformation
-//                      gradient, stretches, Green strain -- one lane per tet over a constant 64-byte record, the observation's reduction tree
+//                      gradient, stretches, Green strain -- one lane per tet over a constant 64-byte record
 //   pose.hip           per-body pose on the device (tetsim_body_poses_device): mass moments over a constant per-particle table, the best-fit
-//                      rotation (Horn's quaternion by a fixed Jacobi procedure), angular velocity and momentum -- the observation's tree
+//                      rotation (Horn's quaternion by a fixed Jacobi procedure), angular velocity and momentum
 //   body_grabs.hip     one held particle per body of a batch, set from host or device memory (tetsim_set_body_grabs / _device): the table the
 //                      particle passes read; the nearest particle of every body on the device (tetsim_nearest_particles_device)
 //   place.hip          a rigid motion of chosen bodies' complete state, rows and mask in device memory (tetsim_place_bodies / _device): one
@@ -149,14 +150,23 @@ struct NeighDev {
     std::vector<int32_t> send_global, recv_global, send_local;
 };
 
-// tetsim_observe_bodies_device (observe.hip): the constant tables and the scratch of a handle's observations, made by its first one
+// The per-body calls' cut of every body into chunks of 256 particles / tets (body_reduce.h: ensure_chunk_table), one table per kind,
+// uploaded by the first call that needs it; `chunks` is set last
+enum ChunkKind : uint32_t { kParticleChunks = 0, kTetChunks = 1 };
+struct BodyChunk;
+struct BodyChunks;
+struct ChunkTable {
+    const BodyChunk* chunks = nullptr;     // [n_chunks] {first row, rows, body}
+    const BodyChunks* bodies = nullptr;    // [bodies] the body's chunks, which are also its partial rows
+    uint32_t n_chunks = 0;
+};
+
+// tetsim_observe_bodies_device (observe.hip): the constant table and the scratch of a handle's observations, made by its first one
 struct ObsDev {
     const void* tets = nullptr;        // [tets] int4: the four API particle ids
     const double* v0 = nullptr;        // [tets] signed rest volume
-    const void *chunks = nullptr, *bodies = nullptr;   // per workgroup of the first launch its body and rows; per body its chunks
-    double* partial = nullptr;         // [n_chunks] partial rows
+    double* partial = nullptr;         // [tet chunks + particle chunks] partial rows
     double* rows = nullptr;            // [bodies][TETSIM_OBS_WIDTH]: the device side of tetsim_read_body_observations
-    uint32_t n_chunks = 0;
     bool ready = false;
 };
 
@@ -172,11 +182,9 @@ struct StrainRec {
 static_assert(sizeof(StrainRec) == 64 && alignof(StrainRec) == 8, "four dwordx4 loads per record");
 struct StrainDev {
     const void* table = nullptr;       // [tets] 64-byte records: the four API particle ids, invRestPose, the degenerate mark, |V0|
-    const void *chunks = nullptr, *bodies = nullptr;   // per workgroup its rows; per body its chunks
     const uint32_t* vis_tet = nullptr; // [num_vis_verts] the tet of every attached visual row (the first visual call)
-    double* partial = nullptr;         // [n_chunks][TETSIM_STRAIN_BODY_WIDTH] partial body rows
+    double* partial = nullptr;         // [tet chunks][TETSIM_STRAIN_BODY_WIDTH] partial body rows
     float* rows = nullptr;             // [tets][TETSIM_STRAIN_WIDTH]: the device side of tetsim_read_tet_strain
-    uint32_t n_chunks = 0;
     bool ready = false;
 };
 
@@ -189,10 +197,8 @@ struct PoseRec {
 static_assert(sizeof(PoseRec) == 32 && alignof(PoseRec) == 8, "two dwordx4 loads per record");
 struct PoseDev {
     const void* table = nullptr;       // [particles] 32-byte records in the caller's numbering
-    const void *chunks = nullptr, *bodies = nullptr;   // per workgroup its rows; per body its chunks
-    double* partial = nullptr;         // [n_chunks][26] chunk rows
+    double* partial = nullptr;         // [particle chunks][26] chunk rows
     double* rows = nullptr;            // [bodies][TETSIM_POSE_WIDTH]: the device side of tetsim_read_body_poses
-    uint32_t n_chunks = 0;
     bool ready = false;
 };
 
@@ -242,12 +248,9 @@ struct tetsim_body {
     uint32_t* d_grab_body = nullptr;    // [particles]
     int4* d_grab_rows = nullptr;        // [bodies]
     uint32_t* d_body_first = nullptr;   // [bodies + 1] first particle of every body in the CALLER's numbering (also tetsim_nearest_particles_device)
-    // tetsim_nearest_particles_device: a body's particles in chunks of 256 -- {body, first particle} per chunk, per body its first chunk, a candidate per chunk
-    uint2* d_near_chunks = nullptr;
-    uint32_t* d_near_first = nullptr;   // [bodies + 1]
+    // tetsim_nearest_particles_device: a candidate per chunk of the particle chunk table (below)
     double* d_near_d2 = nullptr;
     uint32_t* d_near_id = nullptr;
-    uint32_t near_chunks = 0;
     std::map<uint32_t, hipGraphExec_t> graphs;
     std::vector<void*> allocs;
     std::vector<float> h_verts;
@@ -361,6 +364,7 @@ struct tetsim_body {
     // tetsim_place_bodies (place.hip): where the host variant's rows and mask wait for the kernel, made by its first call
     float* d_place_rows = nullptr;      // [bodies][TETSIM_PLACE_WIDTH]
     uint8_t* d_place_mask = nullptr;    // [bodies]
+    ChunkTable chunk_table[2];     // [ChunkKind]: what the per-body calls reduce over (body_reduce.h)
     ObsDev obs;                    // tetsim_observe_bodies_device / tetsim_read_body_observations (observe.hip)
     StrainDev strain;              // tetsim_tet_strain_device / tetsim_body_strain_device / tetsim_visual_strain_device (strain.hip)
     PoseDev pose;                  // tetsim_body_poses_device / tetsim_read_body_poses (pose.hip)
@@ -427,6 +431,9 @@ inline double rest_volume(const float* v, const int32_t* t) {
     const double cx = e2y * e3z - e2z * e3y, cy = e2z * e3x - e2x * e3z, cz = e2x * e3y - e2y * e3x;
     return ((e1x * cx + e1y * cy) + e1z * cz) / 6.0;
 }
+
+// a float a device row may hold (place.hip, body_grabs.hip): neither infinite nor NaN, by its bits
+__device__ __forceinline__ bool finite_f32(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
 
 void build_strain_table(const float* verts, uint32_t nv, const int32_t* tets, uint32_t nt, double density, StrainRec* out);   // tetsim_host.cpp
 // first_vert: [bodies + 1] first particle of every body; centres: [3 * bodies] the bodies' rest mass centres, or null

@@ -3,7 +3,7 @@
 // pj_quad.hip: load_qparams) is made here: the body of every particle in DEVICE particle order, a constant, and one 16-byte row per body,
 // {device particle or -1, target xyz}, written by one small kernel per set call.  Built with -ffp-contract=off: the nearest query's squared
 // distance is tetsim_nearest_particle's (util_kernels.hip: nearest_kernel), every multiply and add rounded on its own.  See body.h.
-#include "body.h"
+#include "body_reduce.h"
 
 #include <cfloat>
 
@@ -15,9 +15,7 @@ const char* const kBodyGrabsOn = "body grabs are on (tetsim_set_body_grabs): one
 
 namespace {
 
-constexpr uint32_t kNearChunk = 256;   // particles per candidate, counted from the body's own first particle: nearest_kernel's blocks of the body alone
-
-__device__ __forceinline__ bool finite_f32(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
+constexpr uint32_t kNearChunk = kBodyChunk;   // particles per candidate, counted from the body's own first particle: nearest_kernel's blocks of the body alone
 
 // One lane per body: the caller's row -> the table's.  first[b]: the body's first particle in the caller's numbering; map: caller's
 // particle -> device particle (null = identity).  A row the table cannot hold -- an index outside the body, a non-finite target --
@@ -51,18 +49,17 @@ __global__ __launch_bounds__(kRowsPerLaunch) void grab_rows_value_kernel(RowChun
 
 // ---- nearest particle per body: argmin of Softbody.js:279-291 over each body's particles -------------------------------------------------
 // One workgroup per chunk of 256 particles of ONE body: nearest_kernel's candidate -- f64, a0*a0 + a1*a1 + a2*a2, NaN never picked, the lowest
-// index among equals -- for the chunk, against the body's own point.  chunks[c] = {body, first particle (caller's numbering)}.
-__global__ __launch_bounds__(kNearChunk) void near_chunk_kernel(const float4* __restrict__ pos, const uint32_t* __restrict__ map, const uint2* __restrict__ chunks,
-                                                                const uint32_t* __restrict__ first, const char* __restrict__ points, uint64_t stride,
-                                                                double* __restrict__ best_d2, uint32_t* __restrict__ best_id) {
+// index among equals -- for the chunk, against the body's own point.  chunks: the particle chunk table (body_reduce.h).
+__global__ __launch_bounds__(kNearChunk) void near_chunk_kernel(const float4* __restrict__ pos, const uint32_t* __restrict__ map, const BodyChunk* __restrict__ chunks,
+                                                                const char* __restrict__ points, uint64_t stride, double* __restrict__ best_d2, uint32_t* __restrict__ best_id) {
     __shared__ double s_d[kNearChunk];
     __shared__ uint32_t s_i[kNearChunk];
-    const uint2 ck = chunks[blockIdx.x];
-    const uint32_t b = ck.x, a = ck.y + threadIdx.x, end = first[b + 1u];
-    const float* const q = reinterpret_cast<const float*>(points + static_cast<uint64_t>(b) * stride);
+    const BodyChunk ck = chunks[blockIdx.x];
+    const uint32_t a = ck.first + threadIdx.x;
+    const float* const q = reinterpret_cast<const float*>(points + static_cast<uint64_t>(ck.body) * stride);
     const double px = static_cast<double>(q[0]), py = static_cast<double>(q[1]), pz = static_cast<double>(q[2]);
     double d2 = DBL_MAX;
-    if (a < end) {
+    if (threadIdx.x < ck.count) {
         const float4 p = pos[map ? map[a] : a];
         const double a0 = px - static_cast<double>(p.x), a1 = py - static_cast<double>(p.y), a2 = pz - static_cast<double>(p.z);
         d2 = a0 * a0 + a1 * a1 + a2 * a2;
@@ -82,13 +79,14 @@ __global__ __launch_bounds__(kNearChunk) void near_chunk_kernel(const float4* __
     if (threadIdx.x == 0) { best_d2[blockIdx.x] = s_d[0]; best_id[blockIdx.x] = s_i[0]; }
 }
 // One lane per body: its chunks' candidates in index order, `<` keeps the first minimum -- the loop the host runs behind nearest_kernel
-__global__ __launch_bounds__(256) void near_body_kernel(const double* __restrict__ best_d2, const uint32_t* __restrict__ best_id, const uint32_t* __restrict__ chunk_first,
+__global__ __launch_bounds__(256) void near_body_kernel(const double* __restrict__ best_d2, const uint32_t* __restrict__ best_id, const BodyChunks* __restrict__ body_chunks,
                                                         const uint32_t* __restrict__ first, int32_t* __restrict__ ids, double* __restrict__ dist2, uint32_t bodies) {
     const uint32_t b = blockIdx.x * 256u + threadIdx.x;
     if (b >= bodies) return;
+    const BodyChunks mine = body_chunks[b];
     double best = DBL_MAX;
     int32_t id = -1;
-    for (uint32_t c = chunk_first[b]; c < chunk_first[b + 1u]; c++) {
+    for (uint32_t c = mine.chunk0; c < mine.chunk0 + mine.chunks; c++) {
         const double d = best_d2[c];
         if (d < best) { best = d; id = static_cast<int32_t>(best_id[c] - first[b]); }
     }
@@ -227,31 +225,17 @@ int tetsim_nearest_particles_device(tetsim_handle h, const void* points, uint64_
     if (dist2) { if (int rc = check_device_records(h, dist2, 8u, nb, 8u, 8u, "dist2")) return rc; }
     // ---- every argument is good
     if (int rc = ensure_body_first(h)) return rc;
-    if (!h->d_near_chunks) {   // (the first call: the chunk table, built once on the host)
-        std::vector<uint32_t> first_vert, first_tet;
-        body_ranges(h, &first_vert, &first_tet);
-        std::vector<uint2> chunks;
-        std::vector<uint32_t> chunk_first(nb + 1u, 0u);
-        for (uint32_t b = 0; b < nb; b++) {
-            chunk_first[b] = static_cast<uint32_t>(chunks.size());
-            for (uint32_t a = first_vert[b]; a < first_vert[b + 1u]; a += kNearChunk) chunks.push_back(make_uint2(b, a));
-        }
-        chunk_first[nb] = static_cast<uint32_t>(chunks.size());
-        uint2* d_chunks = nullptr;
-        if (int rc = dev_alloc(h, &d_chunks, chunks.size())) return rc;
-        if (int rc = upload(h, d_chunks, chunks)) return rc;
-        if (int rc = dev_alloc(h, &h->d_near_first, chunk_first.size())) return rc;
-        if (int rc = upload(h, h->d_near_first, chunk_first)) return rc;
-        if (int rc = dev_alloc(h, &h->d_near_d2, chunks.size())) return rc;
-        if (int rc = dev_alloc(h, &h->d_near_id, chunks.size())) return rc;
-        h->near_chunks = static_cast<uint32_t>(chunks.size());
-        h->d_near_chunks = d_chunks;
+    if (int rc = ensure_chunk_table(h, kParticleChunks)) return rc;
+    const ChunkTable& t = h->chunk_table[kParticleChunks];
+    if (!h->d_near_id) {   // (the first call: a candidate per chunk; the id's pointer is set last)
+        if (int rc = dev_alloc(h, &h->d_near_d2, t.n_chunks)) return rc;
+        if (int rc = dev_alloc(h, &h->d_near_id, t.n_chunks)) return rc;
     }
     return on_caller_stream(h, caller_stream, [&]() -> int {
-        if (h->near_chunks)
-            hipLaunchKernelGGL(near_chunk_kernel, dim3(h->near_chunks), dim3(kNearChunk), 0, h->stream, current_positions(h), h->d_api2dev, h->d_near_chunks, h->d_body_first,
+        if (t.n_chunks)
+            hipLaunchKernelGGL(near_chunk_kernel, dim3(t.n_chunks), dim3(kNearChunk), 0, h->stream, current_positions(h), h->d_api2dev, t.chunks,
                                static_cast<const char*>(points), stride, h->d_near_d2, h->d_near_id);
-        hipLaunchKernelGGL(near_body_kernel, dim3((nb + 255u) / 256u), dim3(256), 0, h->stream, h->d_near_d2, h->d_near_id, h->d_near_first, h->d_body_first,
+        hipLaunchKernelGGL(near_body_kernel, dim3((nb + 255u) / 256u), dim3(256), 0, h->stream, h->d_near_d2, h->d_near_id, t.bodies, h->d_body_first,
                            static_cast<int32_t*>(ids), static_cast<double*>(dist2), nb);
         return launched(h);
     });

@@ -3,26 +3,21 @@
 // the inverted tets, the box of the particles, the fastest particle, the non-finite particles -- computed on the device from the rows the
 // export hands out (device_io.hip: resolve_field / prepare_fields, gathered through d_api2dev), so no stepping path's tet order matters, and
 // ordered against the caller's stream as the export is (on_caller_stream).  f64 arithmetic on the stored f32 values, every operation
-// rounded on its own (this unit is built with -ffp-contract=off); a fixed reduction tree, no atomics: the same state gives the same bits,
-// and a body of a batch the bits it gives alone.  See body.h.
-#include "body.h"
+// rounded on its own (this unit is built with -ffp-contract=off); the fixed reduction tree over the chunks of body_reduce.h, no atomics: the
+// same state gives the same bits, and a body of a batch the bits it gives alone.  See body.h.
+#include "body_reduce.h"
 
 using namespace tetsim;
 
 namespace tetsim {
 namespace {
 
-constexpr uint32_t kObsChunk = 256;     // tets / particles of one workgroup; a body's chunks count from ITS first tet / particle
 constexpr uint32_t kObsPartial = 12;    // doubles of a chunk's partial row (below)
 constexpr uint32_t kObsTetVals = 10, kObsVertVals = 7;
-enum : uint32_t { kObsTets = 0u, kObsVerts = 1u };
 // A tet chunk's partial row: [0] sum 4w, [1..3] sum w * (x0+x1+x2+x3), [4..6] the same of the velocities, [7] sum V, [8] sum V0,
 // [9] min V/V0, [10] inverted tets (a 64-bit count in the double's place).  A particle chunk's: [0..2] box min, [3..5] box max,
-// [6] max speed^2, [7] non-finite particles (a count, likewise).
+// [6] max speed^2, [7] non-finite particles (a count, likewise).  The tet chunks' rows come first, then the particle chunks'.
 constexpr uint32_t kTetCountAt = 10, kVertCountAt = 7;
-
-struct ObsChunk { uint32_t body, first, count, kind; };          // first: the chunk's first tet / particle in the API's numbering
-struct ObsBody { uint32_t tet_chunk0, tet_chunks, vert_chunk0, vert_chunks; };   // the body's partial rows
 
 __device__ __forceinline__ double obs_dot(double ux, double uy, double uz, double vx, double vy, double vz) { return (ux * vx + uy * vy) + uz * vz; }
 // dot(b - a, cross(c - a, d - a)) / 6 of four float4 corners
@@ -38,56 +33,31 @@ __device__ __forceinline__ double obs_corner_sum(float a, float b, float c, floa
 }
 
 // which of the partial row's values are sums, minima, maxima
-__device__ __forceinline__ bool tet_is_min(uint32_t k) { return k == 9u; }
-__device__ __forceinline__ double obs_combine(double a, double b, uint32_t k, bool tets) {
-    if (tets) return tet_is_min(k) ? fmin(a, b) : a + b;
-    return k < 3u ? fmin(a, b) : fmax(a, b);
-}
-__device__ __forceinline__ double obs_identity(uint32_t k, bool tets) {
-    if (tets) return tet_is_min(k) ? INFINITY : 0.0;
-    return k < 3u ? INFINITY : k < 6u ? -INFINITY : 0.0;
-}
+struct TetOps {
+    static __device__ __forceinline__ double combine(double a, double b, uint32_t k) { return k == 9u ? fmin(a, b) : a + b; }
+    static __device__ __forceinline__ double identity(uint32_t k) { return k == 9u ? INFINITY : 0.0; }
+};
+struct VertOps {
+    static __device__ __forceinline__ double combine(double a, double b, uint32_t k) { return k < 3u ? fmin(a, b) : fmax(a, b); }
+    static __device__ __forceinline__ double identity(uint32_t k) { return k < 3u ? INFINITY : k < 6u ? -INFINITY : 0.0; }
+};
 
-// The fixed tree of a workgroup of 256: wave64 shuffles (lane l takes lane l + 32, 16, .. 1), then the four waves' results through LDS
-// as (w0 + w1) + (w2 + w3).  The result is valid in thread 0.  Counts travel as integers.
-template <uint32_t K, bool TETS, class Count>
-__device__ __forceinline__ void obs_block_reduce(double (&v)[K], Count& n, double (*lds)[kObsTetVals], unsigned long long* lds_n) {
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (uint32_t off = 32u; off; off >>= 1) {
-#pragma unroll
-        for (uint32_t k = 0; k < K; k++) v[k] = obs_combine(v[k], __shfl_down(v[k], off), k, TETS);
-        n += __shfl_down(n, off);
-    }
-    __syncthreads();   // (the LDS rows may still be read by the reduction before this one)
-    if (lane == 0u) {
-#pragma unroll
-        for (uint32_t k = 0; k < K; k++) lds[wave][k] = v[k];
-        lds_n[wave] = n;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0u) {
-#pragma unroll
-        for (uint32_t k = 0; k < K; k++)
-            v[k] = obs_combine(obs_combine(lds[0][k], lds[1][k], k, TETS), obs_combine(lds[2][k], lds[3][k], k, TETS), k, TETS);
-        n = static_cast<Count>((lds_n[0] + lds_n[1]) + (lds_n[2] + lds_n[3]));
-    }
-}
-
-// First launch: one workgroup per chunk, one lane per tet / particle; the chunk's partial row leaves through thread 0.
-__global__ __launch_bounds__(256) void observe_chunks_kernel(const ObsChunk* __restrict__ chunks, const int4* __restrict__ tets, const double* __restrict__ v0,
-                                                            const float4* __restrict__ pos, const float4* __restrict__ vel, const uint32_t* __restrict__ map,
-                                                            double density, double* __restrict__ partial) {
+// First launch: one workgroup per chunk -- the tet chunks, then the particle chunks -- one lane per tet / particle; the chunk's partial row
+// leaves through thread 0.
+__global__ __launch_bounds__(256) void observe_chunks_kernel(const BodyChunk* __restrict__ tet_chunks, uint32_t n_tet_chunks, const BodyChunk* __restrict__ vert_chunks,
+                                                            const int4* __restrict__ tets, const double* __restrict__ v0, const float4* __restrict__ pos,
+                                                            const float4* __restrict__ vel, const uint32_t* __restrict__ map, double density, double* __restrict__ partial) {
     __shared__ double lds[4][kObsTetVals];
     __shared__ unsigned long long lds_n[4];
-    const ObsChunk c = chunks[blockIdx.x];
+    const bool of_tets = blockIdx.x < n_tet_chunks;   // (uniform)
+    const BodyChunk c = of_tets ? tet_chunks[blockIdx.x] : vert_chunks[blockIdx.x - n_tet_chunks];
     double* const row = partial + static_cast<uint64_t>(blockIdx.x) * kObsPartial;
     const bool live = threadIdx.x < c.count;
     const uint32_t r = c.first + threadIdx.x;
-    if (c.kind == kObsTets) {
+    if (of_tets) {
         double v[kObsTetVals];
 #pragma unroll
-        for (uint32_t k = 0; k < kObsTetVals; k++) v[k] = obs_identity(k, true);
+        for (uint32_t k = 0; k < kObsTetVals; k++) v[k] = TetOps::identity(k);
         uint32_t inverted = 0u;
         if (live) {
             const int4 id = tets[r];
@@ -112,7 +82,8 @@ __global__ __launch_bounds__(256) void observe_chunks_kernel(const ObsChunk* __r
                 inverted = ratio <= 0.0 ? 1u : 0u;
             }
         }
-        obs_block_reduce<kObsTetVals, true>(v, inverted, lds, lds_n);
+        __syncthreads();   // (the kernel's barriers are what they were when the tree began with one)
+        block_reduce<TetOps>(v, inverted, lds, lds_n);
         if (threadIdx.x == 0u) {
 #pragma unroll
             for (uint32_t k = 0; k < kObsTetVals; k++) row[k] = v[k];
@@ -122,7 +93,7 @@ __global__ __launch_bounds__(256) void observe_chunks_kernel(const ObsChunk* __r
     } else {
         double v[kObsVertVals];
 #pragma unroll
-        for (uint32_t k = 0; k < kObsVertVals; k++) v[k] = obs_identity(k, false);
+        for (uint32_t k = 0; k < kObsVertVals; k++) v[k] = VertOps::identity(k);
         uint32_t nonfinite = 0u;
         if (live) {
             const uint32_t i = map ? map[r] : r;
@@ -133,7 +104,8 @@ __global__ __launch_bounds__(256) void observe_chunks_kernel(const ObsChunk* __r
                 v[6] = (ux * ux + uy * uy) + uz * uz;
             } else nonfinite = 1u;
         }
-        obs_block_reduce<kObsVertVals, false>(v, nonfinite, lds, lds_n);
+        __syncthreads();
+        block_reduce<VertOps>(v, nonfinite, lds, lds_n);
         if (threadIdx.x == 0u) {
 #pragma unroll
             for (uint32_t k = 0; k < kObsVertVals; k++) row[k] = v[k];
@@ -144,32 +116,19 @@ __global__ __launch_bounds__(256) void observe_chunks_kernel(const ObsChunk* __r
     }
 }
 
-// Second launch: one workgroup per body.  Thread t folds the body's partial rows t, t + 256, .. in that order, then the same tree; thread 0
-// divides and stores the finished row.
-__global__ __launch_bounds__(256) void observe_finish_kernel(const ObsBody* __restrict__ bodies, const double* __restrict__ partial, char* __restrict__ dst, uint64_t stride) {
+// Second launch: one workgroup per body.  The fold of the body's partial rows (body_reduce.h: fold_rows), then the same tree, for its tets
+// and for its particles; thread 0 divides and stores the finished row.
+__global__ __launch_bounds__(256) void observe_finish_kernel(const BodyChunks* __restrict__ tet_bodies, const BodyChunks* __restrict__ vert_bodies, const double* __restrict__ tet_partial,
+                                                            const double* __restrict__ vert_partial, char* __restrict__ dst, uint64_t stride) {
     __shared__ double lds[4][kObsTetVals];
     __shared__ unsigned long long lds_n[4];
-    const ObsBody b = bodies[blockIdx.x];
     double t[kObsTetVals], p[kObsVertVals];
     unsigned long long inverted = 0ull, nonfinite = 0ull;
-#pragma unroll
-    for (uint32_t k = 0; k < kObsTetVals; k++) t[k] = obs_identity(k, true);
-#pragma unroll
-    for (uint32_t k = 0; k < kObsVertVals; k++) p[k] = obs_identity(k, false);
-    for (uint32_t j = threadIdx.x; j < b.tet_chunks; j += 256u) {
-        const double* const row = partial + static_cast<uint64_t>(b.tet_chunk0 + j) * kObsPartial;
-#pragma unroll
-        for (uint32_t k = 0; k < kObsTetVals; k++) t[k] = obs_combine(t[k], row[k], k, true);
-        inverted += static_cast<unsigned long long>(__double_as_longlong(row[kTetCountAt]));
-    }
-    for (uint32_t j = threadIdx.x; j < b.vert_chunks; j += 256u) {
-        const double* const row = partial + static_cast<uint64_t>(b.vert_chunk0 + j) * kObsPartial;
-#pragma unroll
-        for (uint32_t k = 0; k < kObsVertVals; k++) p[k] = obs_combine(p[k], row[k], k, false);
-        nonfinite += static_cast<unsigned long long>(__double_as_longlong(row[kVertCountAt]));
-    }
-    obs_block_reduce<kObsTetVals, true>(t, inverted, lds, lds_n);
-    obs_block_reduce<kObsVertVals, false>(p, nonfinite, lds, lds_n);
+    fold_rows<TetOps, kObsPartial>(tet_bodies[blockIdx.x], tet_partial, t, inverted, kTetCountAt);
+    fold_rows<VertOps, kObsPartial>(vert_bodies[blockIdx.x], vert_partial, p, nonfinite, kVertCountAt);
+    block_reduce<TetOps>(t, inverted, lds, lds_n);
+    __syncthreads();   // (thread 0 has read the tets' LDS rows before the particles' are written)
+    block_reduce<VertOps>(p, nonfinite, lds, lds_n);
     if (threadIdx.x != 0u) return;
     double* const o = reinterpret_cast<double*>(dst + static_cast<uint64_t>(blockIdx.x) * stride);
     const double mass = t[0];
@@ -191,16 +150,15 @@ __global__ __launch_bounds__(256) void observe_finish_kernel(const ObsBody* __re
     o[TETSIM_OBS_RESERVED] = 0.0;
 }
 
-// The constant tables, built and uploaded by the handle's first observation (the only part of a call that blocks, with the export's
-// events and index map): per tet its four API particle ids and V0, per chunk its body and rows, per body its chunks; and the scratch
-// of the partial rows and the rows of the host read.  All of it counts into TetSimInfo.device_bytes from then on.
+// What the handle's first observation builds and uploads (the only part of a call that blocks, with the export's events and index map):
+// both chunk tables (body_reduce.h) unless another call made them, per tet its four API particle ids and V0, and the scratch of the
+// partial rows and the rows of the host read.  All of it counts into TetSimInfo.device_bytes from then on.
 int ensure_tables(tetsim_body* h) {
     ObsDev& d = h->obs;
     if (d.ready) return 0;
+    if (int rc = ensure_chunk_table(h, kTetChunks)) return rc;
+    if (int rc = ensure_chunk_table(h, kParticleChunks)) return rc;
     const uint32_t nt = h->info.num_elems;
-    std::vector<uint32_t> fv, ft;
-    body_ranges(h, &fv, &ft);
-    const uint32_t nb = static_cast<uint32_t>(fv.size() - 1);
     std::vector<int4> ids(nt);
     std::vector<double> v0(nt);
     for (uint32_t e = 0; e < nt; e++) {
@@ -208,34 +166,15 @@ int ensure_tables(tetsim_body* h) {
         ids[e] = make_int4(t[0], t[1], t[2], t[3]);
         v0[e] = rest_volume(h->h_verts.data(), t);   // (body.h)
     }
-    std::vector<ObsChunk> chunks;
-    std::vector<ObsBody> bodies(nb);
-    auto cut = [&](uint32_t body, uint32_t first, uint32_t end, uint32_t kind) {
-        for (uint32_t at = first; at < end; at += kObsChunk) chunks.push_back({body, at, std::min(kObsChunk, end - at), kind});
-    };
-    for (uint32_t b = 0; b < nb; b++) {
-        bodies[b].tet_chunk0 = static_cast<uint32_t>(chunks.size());
-        cut(b, ft[b], ft[b + 1], kObsTets);
-        bodies[b].tet_chunks = static_cast<uint32_t>(chunks.size()) - bodies[b].tet_chunk0;
-    }
-    for (uint32_t b = 0; b < nb; b++) {
-        bodies[b].vert_chunk0 = static_cast<uint32_t>(chunks.size());
-        cut(b, fv[b], fv[b + 1], kObsVerts);
-        bodies[b].vert_chunks = static_cast<uint32_t>(chunks.size()) - bodies[b].vert_chunk0;
-    }
-    int4* d_ids = nullptr; double* d_v0 = nullptr; ObsChunk* d_chunks = nullptr; ObsBody* d_bodies = nullptr;
+    const size_t n_chunks = static_cast<size_t>(h->chunk_table[kTetChunks].n_chunks) + h->chunk_table[kParticleChunks].n_chunks;
+    int4* d_ids = nullptr; double* d_v0 = nullptr;
     if (int rc = dev_alloc(h, &d_ids, ids.size())) return rc;
     if (int rc = dev_alloc(h, &d_v0, v0.size())) return rc;
-    if (int rc = dev_alloc(h, &d_chunks, chunks.size())) return rc;
-    if (int rc = dev_alloc(h, &d_bodies, bodies.size())) return rc;
-    if (int rc = dev_alloc(h, &d.partial, chunks.size() * kObsPartial)) return rc;
-    if (int rc = dev_alloc(h, &d.rows, static_cast<size_t>(nb) * TETSIM_OBS_WIDTH)) return rc;
+    if (int rc = dev_alloc(h, &d.partial, n_chunks * kObsPartial)) return rc;
+    if (int rc = dev_alloc(h, &d.rows, static_cast<size_t>(h->info.num_bodies) * TETSIM_OBS_WIDTH)) return rc;
     if (int rc = upload(h, d_ids, ids)) return rc;
     if (int rc = upload(h, d_v0, v0)) return rc;
-    if (int rc = upload(h, d_chunks, chunks)) return rc;
-    if (int rc = upload(h, d_bodies, bodies)) return rc;
-    d.tets = d_ids; d.v0 = d_v0; d.chunks = d_chunks; d.bodies = d_bodies;
-    d.n_chunks = static_cast<uint32_t>(chunks.size());
+    d.tets = d_ids; d.v0 = d_v0;
     d.ready = true;   // (last: set only when every table is there)
     return 0;
 }
@@ -243,17 +182,15 @@ int ensure_tables(tetsim_body* h) {
 // the two launches on h->stream: row b of dst = body b
 int enqueue_observation(tetsim_body* h, void* dst, uint64_t stride) {
     const ObsDev& d = h->obs;
+    const ChunkTable &tt = h->chunk_table[kTetChunks], &vt = h->chunk_table[kParticleChunks];
     FieldSrc src[2];
-    std::string why;
-    if (int rc = resolve_field(h, TETSIM_FIELD_POSITIONS, false, &src[0], &why)) return fail(h, rc, why);
-    if (int rc = resolve_field(h, TETSIM_FIELD_VELOCITIES, false, &src[1], &why)) return fail(h, rc, why);
-    if (int rc = prepare_fields(h, src, 2)) return rc;
-    if (d.n_chunks)
-        hipLaunchKernelGGL(observe_chunks_kernel, dim3(d.n_chunks), dim3(256), 0, h->stream, static_cast<const ObsChunk*>(d.chunks), static_cast<const int4*>(d.tets), d.v0,
-                           src[0].src, src[1].src, src[0].mapped ? h->d_api2dev : nullptr, h->opt.density, d.partial);
+    if (int rc = export_sources(h, {TETSIM_FIELD_POSITIONS, TETSIM_FIELD_VELOCITIES}, src)) return rc;
+    if (tt.n_chunks + vt.n_chunks)
+        hipLaunchKernelGGL(observe_chunks_kernel, dim3(tt.n_chunks + vt.n_chunks), dim3(256), 0, h->stream, tt.chunks, tt.n_chunks, vt.chunks, static_cast<const int4*>(d.tets),
+                           d.v0, src[0].src, src[1].src, src[0].mapped ? h->d_api2dev : nullptr, h->opt.density, d.partial);
     if (int rc = launched(h)) return rc;
-    hipLaunchKernelGGL(observe_finish_kernel, dim3(h->info.num_bodies), dim3(256), 0, h->stream, static_cast<const ObsBody*>(d.bodies), static_cast<const double*>(d.partial),
-                       static_cast<char*>(dst), stride);
+    hipLaunchKernelGGL(observe_finish_kernel, dim3(h->info.num_bodies), dim3(256), 0, h->stream, tt.bodies, vt.bodies, static_cast<const double*>(d.partial),
+                       static_cast<const double*>(d.partial) + static_cast<size_t>(tt.n_chunks) * kObsPartial, static_cast<char*>(dst), stride);
     return launched(h);
 }
 
@@ -264,14 +201,8 @@ extern "C" {
 
 int tetsim_observe_bodies_device(tetsim_handle h, void* dst, uint64_t row_stride, void* caller_stream) {
     if (!h) return TETSIM_EINVAL;
-    if (!dst) return fail(h, TETSIM_EINVAL, "dst is null");
-    if (reinterpret_cast<uintptr_t>(dst) % 8) return fail(h, TETSIM_EINVAL, "dst is not 8-byte aligned");
-    constexpr uint64_t row = 8ull * TETSIM_OBS_WIDTH;
-    if (row_stride != 0 && (row_stride < row || row_stride % 8)) return fail(h, TETSIM_EINVAL, "row_stride must be 0 or a multiple of 8 of at least 160");
-    if (int rc = device_call_guard(h)) return rc;
-    const uint64_t stride = row_stride ? row_stride : row;
-    const uint32_t nb = h->info.num_bodies;
-    if (int rc = check_device_span(h, dst, static_cast<uint64_t>(nb - 1u) * stride + row, "dst", std::to_string(nb) + " rows do not fit the allocation it points into")) return rc;
+    uint64_t stride;
+    if (int rc = check_dst_rows(h, dst, row_stride, h->info.num_bodies, 8ull * TETSIM_OBS_WIDTH, 8u, &stride)) return rc;
     // ---- every argument is good: from here on only allocation and HIP itself can fail
     if (int rc = ensure_tables(h)) return rc;
     return on_caller_stream(h, caller_stream, [&] { return enqueue_observation(h, dst, stride); });
@@ -282,10 +213,7 @@ int tetsim_read_body_observations(tetsim_handle h, double* out) {
     if (!out) return fail(h, TETSIM_EINVAL, "out is null");
     if (int rc = device_call_guard(h)) return rc;
     if (int rc = ensure_tables(h)) return rc;
-    if (int rc = enqueue_observation(h, h->obs.rows, 8ull * TETSIM_OBS_WIDTH)) return rc;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipMemcpy(out, h->obs.rows, static_cast<size_t>(h->info.num_bodies) * TETSIM_OBS_WIDTH * sizeof(double), hipMemcpyDeviceToHost));
-    return 0;
+    return read_back(h, out, h->obs.rows, static_cast<size_t>(h->info.num_bodies) * TETSIM_OBS_WIDTH, [&] { return enqueue_observation(h, h->obs.rows, 8ull * TETSIM_OBS_WIDTH); });
 }
 
 }  // extern "C"

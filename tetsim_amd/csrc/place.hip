@@ -47,8 +47,6 @@ struct Motion {
     uint32_t valid;                // chosen, every float finite, |q| != 0
 };
 
-__device__ __forceinline__ bool finite_f32(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
-
 __device__ __forceinline__ uint32_t body_of_row(const uint32_t* __restrict__ first, uint32_t bodies, uint32_t row) {
     if (row >= first[bodies]) return bodies;   // padding
     uint32_t lo = 0, hi = bodies;              // first[lo] <= row < first[hi]

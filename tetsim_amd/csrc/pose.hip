@@ -4,50 +4,26 @@
 // (Horn's quaternion: a fixed number of cyclic Jacobi sweeps on a symmetric 4x4), angular velocity and momentum about the mass centre, the
 // rms distance to the best rigid fit.  Positions and velocities come from the rows the export hands out (device_io.hip: resolve_field /
 // prepare_fields, gathered through d_api2dev), and the call is ordered against the caller's stream as the observation is
-// (on_caller_stream).  f64 arithmetic, every operation rounded on its own (this unit is built with -ffp-contract=off); the observation's
-// fixed reduction tree over chunks counted from the body's own first particle, no atomics: the same state gives the same bits, and a body
-// of a batch the bits it gives alone.  The derived values use only + - * / sqrt on the stored raw values: tests/pose_ref.py gives the
-// same bits in numpy.  See body.h.
-#include "body.h"
+// (on_caller_stream).  f64 arithmetic, every operation rounded on its own (this unit is built with -ffp-contract=off); the fixed reduction
+// tree of body_reduce.h over the body's particle chunks, no atomics: the same state gives the same bits, and a body of a batch the bits
+// it gives alone.  The derived values use only + - * / sqrt on the stored raw values: tests/pose_ref.py gives the same bits in numpy.
+// See body.h.
+#include "body_reduce.h"
 
 using namespace tetsim;
 
 namespace tetsim {
 namespace {
 
-constexpr uint32_t kChunk = 256;        // particles of one workgroup; a body's chunks count from ITS first particle
-constexpr uint32_t kRaw = 26;           // the raw moments: row values [0..25], and a chunk's partial row
+constexpr uint32_t kRaw = 26;           // the raw moments: row values [0..25], and a chunk's partial row; every one a sum
 constexpr uint32_t kSweeps = TETSIM_POSE_SWEEPS;   // cyclic Jacobi sweeps (include/tetsim.h says why)
 static_assert(TETSIM_POSE_COM == kRaw, "the derived values follow the raw moments");
 
-struct PoseChunk { uint32_t first, count; };             // the chunk's first particle in the API's numbering
-struct PoseBody { uint32_t chunk0, chunks; };            // the body's partial rows
-
-// The observation's fixed tree of a workgroup of 256 for kRaw sums: wave64 shuffles (lane l takes lane l + 32, 16, .. 1), then the four
-// waves' results through LDS as (w0 + w1) + (w2 + w3).  The result is valid in thread 0.
-__device__ __forceinline__ void pose_block_reduce(double (&v)[kRaw], double (*lds)[kRaw]) {
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (uint32_t off = 32u; off; off >>= 1) {
-#pragma unroll
-        for (uint32_t k = 0; k < kRaw; k++) v[k] = v[k] + __shfl_down(v[k], off);
-    }
-    if (lane == 0u) {
-#pragma unroll
-        for (uint32_t k = 0; k < kRaw; k++) lds[wave][k] = v[k];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0u) {
-#pragma unroll
-        for (uint32_t k = 0; k < kRaw; k++) v[k] = (lds[0][k] + lds[1][k]) + (lds[2][k] + lds[3][k]);
-    }
-}
-
 // First launch: one workgroup per chunk, one lane per particle; the chunk's 26 sums leave through thread 0.
-__global__ __launch_bounds__(256) void pose_chunks_kernel(const PoseChunk* __restrict__ chunks, const PoseRec* __restrict__ table, const float4* __restrict__ pos,
+__global__ __launch_bounds__(256) void pose_chunks_kernel(const BodyChunk* __restrict__ chunks, const PoseRec* __restrict__ table, const float4* __restrict__ pos,
                                                          const float4* __restrict__ vel, const uint32_t* __restrict__ map, double* __restrict__ partial) {
     __shared__ double lds[4][kRaw];
-    const PoseChunk c = chunks[blockIdx.x];
+    const BodyChunk c = chunks[blockIdx.x];
     double v[kRaw];
 #pragma unroll
     for (uint32_t k = 0; k < kRaw; k++) v[k] = 0.0;
@@ -80,7 +56,7 @@ __global__ __launch_bounds__(256) void pose_chunks_kernel(const PoseChunk* __res
         v[TETSIM_POSE_G + 5] = mx[1] * x[2];
         v[TETSIM_POSE_Q0] = m * ((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]);
     }
-    pose_block_reduce(v, lds);
+    block_reduce<SumOps>(v, lds);
     if (threadIdx.x == 0u) {
         double* const row = partial + static_cast<uint64_t>(blockIdx.x) * kRaw;
 #pragma unroll
@@ -210,20 +186,13 @@ __device__ __forceinline__ void pose_derive(double* __restrict__ o) {
     o[TETSIM_POSE_GAP] = lam - second;
 }
 
-// Second launch: one workgroup per body.  Thread t folds the body's chunk rows t, t + 256, .. in that order, then the same tree; thread 0
+// Second launch: one workgroup per body.  The fold of the body's chunk rows (body_reduce.h: fold_rows), then the same tree; thread 0
 // stores the raw values, runs the derived procedure on the values it just stored, and stores the rest.
-__global__ __launch_bounds__(256) void pose_finish_kernel(const PoseBody* __restrict__ bodies, const double* __restrict__ partial, char* __restrict__ dst, uint64_t stride) {
+__global__ __launch_bounds__(256) void pose_finish_kernel(const BodyChunks* __restrict__ bodies, const double* __restrict__ partial, char* __restrict__ dst, uint64_t stride) {
     __shared__ double lds[4][kRaw];
-    const PoseBody body = bodies[blockIdx.x];
     double v[kRaw];
-#pragma unroll
-    for (uint32_t k = 0; k < kRaw; k++) v[k] = 0.0;
-    for (uint32_t j = threadIdx.x; j < body.chunks; j += 256u) {
-        const double* const row = partial + static_cast<uint64_t>(body.chunk0 + j) * kRaw;
-#pragma unroll
-        for (uint32_t k = 0; k < kRaw; k++) v[k] = v[k] + row[k];
-    }
-    pose_block_reduce(v, lds);
+    fold_rows<SumOps, kRaw>(bodies[blockIdx.x], partial, v);
+    block_reduce<SumOps>(v, lds);
     if (threadIdx.x != 0u) return;
     double o[TETSIM_POSE_WIDTH];
 #pragma unroll
@@ -234,36 +203,25 @@ __global__ __launch_bounds__(256) void pose_finish_kernel(const PoseBody* __rest
     for (uint32_t k = 0; k < TETSIM_POSE_WIDTH; k++) out[k] = o[k];
 }
 
-// The constant tables, built and uploaded by the handle's first pose call (the only part of a call that blocks, with the export's events
-// and index map): per particle its record, per chunk its rows, per body its chunks; the scratch of the chunk rows and the rows of the
-// host read.  All of it counts into TetSimInfo.device_bytes from then on.
+// What the handle's first pose call builds and uploads (the only part of a call that blocks, with the export's events and index map): the
+// particle chunk table (body_reduce.h) unless another call made it, per particle its record, the scratch of the chunk rows and the rows
+// of the host read.  All of it counts into TetSimInfo.device_bytes from then on.
 int ensure_tables(tetsim_body* h) {
     PoseDev& d = h->pose;
     if (d.ready) return 0;
+    if (int rc = ensure_chunk_table(h, kParticleChunks)) return rc;
     const uint32_t nt = h->info.num_elems, nv = h->info.num_particles;
     std::vector<uint32_t> fv, ft;
     body_ranges(h, &fv, &ft);
     const uint32_t nb = static_cast<uint32_t>(fv.size() - 1);
     std::vector<PoseRec> recs(nv);
     build_pose_table(h->h_verts.data(), nv, h->h_tets.data(), nt, fv.data(), nb, h->opt.density, recs.data(), nullptr);
-    std::vector<PoseChunk> chunks;
-    std::vector<PoseBody> bodies(nb);
-    for (uint32_t b = 0; b < nb; b++) {
-        bodies[b].chunk0 = static_cast<uint32_t>(chunks.size());
-        for (uint32_t at = fv[b]; at < fv[b + 1]; at += kChunk) chunks.push_back({at, std::min(kChunk, fv[b + 1] - at)});
-        bodies[b].chunks = static_cast<uint32_t>(chunks.size()) - bodies[b].chunk0;
-    }
-    PoseRec* d_recs = nullptr; PoseChunk* d_chunks = nullptr; PoseBody* d_bodies = nullptr;
+    PoseRec* d_recs = nullptr;
     if (int rc = dev_alloc(h, &d_recs, recs.size())) return rc;
-    if (int rc = dev_alloc(h, &d_chunks, chunks.size())) return rc;
-    if (int rc = dev_alloc(h, &d_bodies, bodies.size())) return rc;
-    if (int rc = dev_alloc(h, &d.partial, chunks.size() * kRaw)) return rc;
+    if (int rc = dev_alloc(h, &d.partial, static_cast<size_t>(h->chunk_table[kParticleChunks].n_chunks) * kRaw)) return rc;
     if (int rc = dev_alloc(h, &d.rows, static_cast<size_t>(nb) * TETSIM_POSE_WIDTH)) return rc;
     if (int rc = upload(h, d_recs, recs)) return rc;
-    if (int rc = upload(h, d_chunks, chunks)) return rc;
-    if (int rc = upload(h, d_bodies, bodies)) return rc;
-    d.table = d_recs; d.chunks = d_chunks; d.bodies = d_bodies;
-    d.n_chunks = static_cast<uint32_t>(chunks.size());
+    d.table = d_recs;
     d.ready = true;   // (last: set only when every table is there)
     return 0;
 }
@@ -271,17 +229,14 @@ int ensure_tables(tetsim_body* h) {
 // the two launches on h->stream: row b of dst = body b
 int enqueue_poses(tetsim_body* h, void* dst, uint64_t stride) {
     const PoseDev& d = h->pose;
+    const ChunkTable& t = h->chunk_table[kParticleChunks];
     FieldSrc src[2];
-    std::string why;
-    if (int rc = resolve_field(h, TETSIM_FIELD_POSITIONS, false, &src[0], &why)) return fail(h, rc, why);
-    if (int rc = resolve_field(h, TETSIM_FIELD_VELOCITIES, false, &src[1], &why)) return fail(h, rc, why);
-    if (int rc = prepare_fields(h, src, 2)) return rc;
-    if (d.n_chunks)
-        hipLaunchKernelGGL(pose_chunks_kernel, dim3(d.n_chunks), dim3(256), 0, h->stream, static_cast<const PoseChunk*>(d.chunks), static_cast<const PoseRec*>(d.table),
+    if (int rc = export_sources(h, {TETSIM_FIELD_POSITIONS, TETSIM_FIELD_VELOCITIES}, src)) return rc;
+    if (t.n_chunks)
+        hipLaunchKernelGGL(pose_chunks_kernel, dim3(t.n_chunks), dim3(256), 0, h->stream, t.chunks, static_cast<const PoseRec*>(d.table),
                            src[0].src, src[1].src, src[0].mapped ? h->d_api2dev : nullptr, d.partial);
     if (int rc = launched(h)) return rc;
-    hipLaunchKernelGGL(pose_finish_kernel, dim3(h->info.num_bodies), dim3(256), 0, h->stream, static_cast<const PoseBody*>(d.bodies), static_cast<const double*>(d.partial),
-                       static_cast<char*>(dst), stride);
+    hipLaunchKernelGGL(pose_finish_kernel, dim3(h->info.num_bodies), dim3(256), 0, h->stream, t.bodies, static_cast<const double*>(d.partial), static_cast<char*>(dst), stride);
     return launched(h);
 }
 
@@ -292,14 +247,8 @@ extern "C" {
 
 int tetsim_body_poses_device(tetsim_handle h, void* dst, uint64_t row_stride, void* caller_stream) {
     if (!h) return TETSIM_EINVAL;
-    if (!dst) return fail(h, TETSIM_EINVAL, "dst is null");
-    if (reinterpret_cast<uintptr_t>(dst) % 8) return fail(h, TETSIM_EINVAL, "dst is not 8-byte aligned");
-    constexpr uint64_t row = 8ull * TETSIM_POSE_WIDTH;
-    if (row_stride != 0 && (row_stride < row || row_stride % 8)) return fail(h, TETSIM_EINVAL, "row_stride must be 0 or a multiple of 8 of at least 384");
-    if (int rc = device_call_guard(h)) return rc;
-    const uint64_t stride = row_stride ? row_stride : row;
-    const uint32_t nb = h->info.num_bodies;
-    if (int rc = check_device_span(h, dst, static_cast<uint64_t>(nb - 1u) * stride + row, "dst", std::to_string(nb) + " rows do not fit the allocation it points into")) return rc;
+    uint64_t stride;
+    if (int rc = check_dst_rows(h, dst, row_stride, h->info.num_bodies, 8ull * TETSIM_POSE_WIDTH, 8u, &stride)) return rc;
     // ---- every argument is good: from here on only allocation and HIP itself can fail
     if (int rc = ensure_tables(h)) return rc;
     return on_caller_stream(h, caller_stream, [&] { return enqueue_poses(h, dst, stride); });
@@ -310,10 +259,7 @@ int tetsim_read_body_poses(tetsim_handle h, double* out) {
     if (!out) return fail(h, TETSIM_EINVAL, "out is null");
     if (int rc = device_call_guard(h)) return rc;
     if (int rc = ensure_tables(h)) return rc;
-    if (int rc = enqueue_poses(h, h->pose.rows, 8ull * TETSIM_POSE_WIDTH)) return rc;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipMemcpy(out, h->pose.rows, static_cast<size_t>(h->info.num_bodies) * TETSIM_POSE_WIDTH * sizeof(double), hipMemcpyDeviceToHost));
-    return 0;
+    return read_back(h, out, h->pose.rows, static_cast<size_t>(h->info.num_bodies) * TETSIM_POSE_WIDTH, [&] { return enqueue_poses(h, h->pose.rows, 8ull * TETSIM_POSE_WIDTH); });
 }
 
 }  // extern "C"

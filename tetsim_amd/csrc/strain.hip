@@ -5,22 +5,19 @@
 // resolve_field / prepare_fields, gathered through d_api2dev), so no stepping path's tet order matters, and the calls are ordered against
 // the caller's stream as the export is (on_caller_stream).  f64 arithmetic on the stored f32 values with only + - * / sqrt, every
 // operation rounded on its own (this unit is built with -ffp-contract=off): tests/strain_ref.py gives the same bits in numpy.  The body
-// row is reduced by the observation's fixed tree over chunks counted from the body's own first tet, no atomics.  See body.h.
-#include "body.h"
+// row is reduced by the fixed tree of body_reduce.h over its tet chunks, no atomics.  See body.h.
+#include "body_reduce.h"
 
 using namespace tetsim;
 
 namespace tetsim {
 namespace {
 
-constexpr uint32_t kChunk = 256;        // tets of one workgroup; a body's chunks count from ITS first tet
+constexpr uint32_t kChunk = kBodyChunk; // tets of one workgroup
 constexpr uint32_t kSweeps = TETSIM_STRAIN_SWEEPS;   // cyclic Jacobi sweeps (include/tetsim.h says why 4)
 constexpr uint32_t kVals = 15;          // values of a tet row (RESERVED is the 16th float)
 constexpr uint32_t kBodyVals = 7;       // reduced floating-point values of a body row; the count travels as an integer
 constexpr uint32_t kLdsRow = 20;        // floats between two staged rows: 16 + 4, so that the lanes' 16-byte writes spread over the banks
-
-struct StrainChunk { uint32_t first, count; };            // the chunk's first tet in the API's numbering
-struct StrainBody { uint32_t chunk0, chunks; };           // the body's partial rows
 
 enum : uint32_t { kRowsNone = 0u, kRowsPlain = 1u, kRowsStaged = 2u };
 
@@ -108,53 +105,31 @@ __device__ __forceinline__ void strain_of(const StrainRec& rec, const float4* __
 }
 
 // the body row's values: [0] max, [1] min, [2] min, [3] max, [4] max, [5] [6] sums
-__device__ __forceinline__ double body_combine(double a, double b, uint32_t k) {
-    return (k == 1u || k == 2u) ? fmin(a, b) : (k == 0u || k == 3u || k == 4u) ? fmax(a, b) : a + b;
-}
-__device__ __forceinline__ double body_identity(uint32_t k) {
-    return (k == 1u || k == 2u) ? INFINITY : (k == 0u || k == 3u || k == 4u) ? -INFINITY : 0.0;
-}
-
-// The observation's fixed tree of a workgroup of 256: wave64 shuffles (lane l takes lane l + 32, 16, .. 1), then the four waves' results
-// through LDS as (w0 + w1) + (w2 + w3).  The result is valid in thread 0.  The count travels as an integer.
-__device__ __forceinline__ void body_block_reduce(double (&v)[kBodyVals], unsigned long long& n, double (*lds)[kBodyVals], unsigned long long* lds_n) {
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (uint32_t off = 32u; off; off >>= 1) {
-#pragma unroll
-        for (uint32_t k = 0; k < kBodyVals; k++) v[k] = body_combine(v[k], __shfl_down(v[k], off), k);
-        n += __shfl_down(n, off);
+struct BodyOps {
+    static __device__ __forceinline__ double combine(double a, double b, uint32_t k) {
+        return (k == 1u || k == 2u) ? fmin(a, b) : (k == 0u || k == 3u || k == 4u) ? fmax(a, b) : a + b;
     }
-    if (lane == 0u) {
-#pragma unroll
-        for (uint32_t k = 0; k < kBodyVals; k++) lds[wave][k] = v[k];
-        lds_n[wave] = n;
+    static __device__ __forceinline__ double identity(uint32_t k) {
+        return (k == 1u || k == 2u) ? INFINITY : (k == 0u || k == 3u || k == 4u) ? -INFINITY : 0.0;
     }
-    __syncthreads();
-    if (threadIdx.x == 0u) {
-#pragma unroll
-        for (uint32_t k = 0; k < kBodyVals; k++)
-            v[k] = body_combine(body_combine(lds[0][k], lds[1][k], k), body_combine(lds[2][k], lds[3][k], k), k);
-        n = (lds_n[0] + lds_n[1]) + (lds_n[2] + lds_n[3]);
-    }
-}
+};
 
 // One workgroup per chunk, one lane per tet.  rows: kRowsStaged -- rows are 64 bytes apart and dst is 16-byte aligned: the chunk's rows
 // pass through LDS and leave as 16-byte stores that cover contiguous memory wave by wave; kRowsPlain -- 16 dword stores per row (the
 // destination is only 4-byte aligned and its rows may be padded); kRowsNone -- no rows.  partial != null: the chunk's partial body row
 // (7 doubles and the count of the tets left out) leaves through thread 0.
-__global__ __launch_bounds__(256) void strain_chunks_kernel(const StrainChunk* __restrict__ chunks, const StrainRec* __restrict__ table, const float4* __restrict__ pos,
+__global__ __launch_bounds__(256) void strain_chunks_kernel(const BodyChunk* __restrict__ chunks, const StrainRec* __restrict__ table, const float4* __restrict__ pos,
                                                            const uint32_t* __restrict__ map, char* __restrict__ dst, uint64_t stride, uint32_t rows,
                                                            double* __restrict__ partial) {
     __shared__ float4 staged[kChunk * kLdsRow / 4u];
     __shared__ double lds[4][kBodyVals];
     __shared__ unsigned long long lds_n[4];
-    const StrainChunk c = chunks[blockIdx.x];
+    const BodyChunk c = chunks[blockIdx.x];
     const bool live = threadIdx.x < c.count;
     const uint32_t r = c.first + threadIdx.x;
     double b[kBodyVals];
 #pragma unroll
-    for (uint32_t k = 0; k < kBodyVals; k++) b[k] = body_identity(k);
+    for (uint32_t k = 0; k < kBodyVals; k++) b[k] = BodyOps::identity(k);
     unsigned long long left_out = 0ull;
     if (live) {
         const StrainRec rec = load_rec(table, r);
@@ -196,7 +171,7 @@ __global__ __launch_bounds__(256) void strain_chunks_kernel(const StrainChunk* _
             if (j < pieces) out[j] = staged[(j >> 2) * (kLdsRow / 4u) + (j & 3u)];
     }
     if (!partial) return;   // (uniform)
-    body_block_reduce(b, left_out, lds, lds_n);
+    block_reduce<BodyOps>(b, left_out, lds, lds_n);
     if (threadIdx.x == 0u) {
         double* const row = partial + static_cast<uint64_t>(blockIdx.x) * TETSIM_STRAIN_BODY_WIDTH;
 #pragma unroll
@@ -205,22 +180,14 @@ __global__ __launch_bounds__(256) void strain_chunks_kernel(const StrainChunk* _
     }
 }
 
-// One workgroup per body.  Thread t folds the body's partial rows t, t + 256, .. in that order, then the same tree; thread 0 stores the row.
-__global__ __launch_bounds__(256) void strain_finish_kernel(const StrainBody* __restrict__ bodies, const double* __restrict__ partial, char* __restrict__ dst, uint64_t stride) {
+// One workgroup per body.  The fold of the body's partial rows (body_reduce.h: fold_rows), then the same tree; thread 0 stores the row.
+__global__ __launch_bounds__(256) void strain_finish_kernel(const BodyChunks* __restrict__ bodies, const double* __restrict__ partial, char* __restrict__ dst, uint64_t stride) {
     __shared__ double lds[4][kBodyVals];
     __shared__ unsigned long long lds_n[4];
-    const StrainBody body = bodies[blockIdx.x];
     double b[kBodyVals];
     unsigned long long left_out = 0ull;
-#pragma unroll
-    for (uint32_t k = 0; k < kBodyVals; k++) b[k] = body_identity(k);
-    for (uint32_t j = threadIdx.x; j < body.chunks; j += 256u) {
-        const double* const row = partial + static_cast<uint64_t>(body.chunk0 + j) * TETSIM_STRAIN_BODY_WIDTH;
-#pragma unroll
-        for (uint32_t k = 0; k < kBodyVals; k++) b[k] = body_combine(b[k], row[k], k);
-        left_out += static_cast<unsigned long long>(__double_as_longlong(row[kBodyVals]));
-    }
-    body_block_reduce(b, left_out, lds, lds_n);
+    fold_rows<BodyOps, TETSIM_STRAIN_BODY_WIDTH>(bodies[blockIdx.x], partial, b, left_out, kBodyVals);
+    block_reduce<BodyOps>(b, left_out, lds, lds_n);
     if (threadIdx.x != 0u) return;
     double* const o = reinterpret_cast<double*>(dst + static_cast<uint64_t>(blockIdx.x) * stride);
 #pragma unroll
@@ -242,36 +209,22 @@ __global__ __launch_bounds__(256) void strain_visual_kernel(const uint32_t* __re
     *reinterpret_cast<float*>(dst + static_cast<uint64_t>(row) * stride) = static_cast<float>(pick);
 }
 
-// The constant tables, built and uploaded by the handle's first strain call (the only part of a call that blocks, with the export's events
-// and index map): per tet its record, per chunk its rows, per body its chunks; the scratch of the partial rows and the rows of the host
-// read.  All of it counts into TetSimInfo.device_bytes from then on.
+// What the handle's first strain call builds and uploads (the only part of a call that blocks, with the export's events and index map):
+// the tet chunk table (body_reduce.h) unless another call made it, per tet its record, the scratch of the partial rows and the rows of
+// the host read.  All of it counts into TetSimInfo.device_bytes from then on.
 int ensure_tables(tetsim_body* h) {
     StrainDev& d = h->strain;
     if (d.ready) return 0;
-    const uint32_t nt = h->info.num_elems, nv = h->info.num_particles;
-    std::vector<uint32_t> fv, ft;
-    body_ranges(h, &fv, &ft);
-    const uint32_t nb = static_cast<uint32_t>(ft.size() - 1);
+    if (int rc = ensure_chunk_table(h, kTetChunks)) return rc;
+    const uint32_t nt = h->info.num_elems;
     std::vector<StrainRec> recs(nt);
-    build_strain_table(h->h_verts.data(), nv, h->h_tets.data(), nt, h->opt.density, recs.data());
-    std::vector<StrainChunk> chunks;
-    std::vector<StrainBody> bodies(nb);
-    for (uint32_t b = 0; b < nb; b++) {
-        bodies[b].chunk0 = static_cast<uint32_t>(chunks.size());
-        for (uint32_t at = ft[b]; at < ft[b + 1]; at += kChunk) chunks.push_back({at, std::min(kChunk, ft[b + 1] - at)});
-        bodies[b].chunks = static_cast<uint32_t>(chunks.size()) - bodies[b].chunk0;
-    }
-    StrainRec* d_recs = nullptr; StrainChunk* d_chunks = nullptr; StrainBody* d_bodies = nullptr;
+    build_strain_table(h->h_verts.data(), h->info.num_particles, h->h_tets.data(), nt, h->opt.density, recs.data());
+    StrainRec* d_recs = nullptr;
     if (int rc = dev_alloc(h, &d_recs, recs.size())) return rc;
-    if (int rc = dev_alloc(h, &d_chunks, chunks.size())) return rc;
-    if (int rc = dev_alloc(h, &d_bodies, bodies.size())) return rc;
-    if (int rc = dev_alloc(h, &d.partial, chunks.size() * TETSIM_STRAIN_BODY_WIDTH)) return rc;
+    if (int rc = dev_alloc(h, &d.partial, static_cast<size_t>(h->chunk_table[kTetChunks].n_chunks) * TETSIM_STRAIN_BODY_WIDTH)) return rc;
     if (int rc = dev_alloc(h, &d.rows, static_cast<size_t>(nt) * TETSIM_STRAIN_WIDTH)) return rc;
     if (int rc = upload(h, d_recs, recs)) return rc;
-    if (int rc = upload(h, d_chunks, chunks)) return rc;
-    if (int rc = upload(h, d_bodies, bodies)) return rc;
-    d.table = d_recs; d.chunks = d_chunks; d.bodies = d_bodies;
-    d.n_chunks = static_cast<uint32_t>(chunks.size());
+    d.table = d_recs;
     d.ready = true;   // (last: set only when every table is there)
     return 0;
 }
@@ -287,22 +240,16 @@ int ensure_visual_table(tetsim_body* h) {
     return 0;
 }
 
-// the current positions as the export hands them out, prepared on h->stream
-int positions(tetsim_body* h, FieldSrc* src) {
-    std::string why;
-    if (int rc = resolve_field(h, TETSIM_FIELD_POSITIONS, false, src, &why)) return fail(h, rc, why);
-    return prepare_fields(h, src, 1);
-}
-
 // the chunk launch on h->stream: tet rows to dst (or none), partial body rows (or none)
 int enqueue_chunks(tetsim_body* h, void* dst, uint64_t stride, bool partial) {
     const StrainDev& d = h->strain;
-    if (!d.n_chunks) return 0;
-    FieldSrc src;
-    if (int rc = positions(h, &src)) return rc;
+    const ChunkTable& t = h->chunk_table[kTetChunks];
+    if (!t.n_chunks) return 0;
+    FieldSrc src[1];
+    if (int rc = export_sources(h, {TETSIM_FIELD_POSITIONS}, src)) return rc;
     const uint32_t rows = !dst ? kRowsNone : (stride == 64u && reinterpret_cast<uintptr_t>(dst) % 16u == 0) ? kRowsStaged : kRowsPlain;
-    hipLaunchKernelGGL(strain_chunks_kernel, dim3(d.n_chunks), dim3(256), 0, h->stream, static_cast<const StrainChunk*>(d.chunks), static_cast<const StrainRec*>(d.table),
-                       src.src, src.mapped ? h->d_api2dev : nullptr, static_cast<char*>(dst), stride, rows, partial ? d.partial : nullptr);
+    hipLaunchKernelGGL(strain_chunks_kernel, dim3(t.n_chunks), dim3(256), 0, h->stream, t.chunks, static_cast<const StrainRec*>(d.table),
+                       src[0].src, src[0].mapped ? h->d_api2dev : nullptr, static_cast<char*>(dst), stride, rows, partial ? d.partial : nullptr);
     return launched(h);
 }
 
@@ -313,12 +260,8 @@ extern "C" {
 
 int tetsim_tet_strain_device(tetsim_handle h, void* dst, uint64_t row_stride, void* caller_stream) {
     if (!h) return TETSIM_EINVAL;
-    constexpr uint64_t row = 4ull * TETSIM_STRAIN_WIDTH;
-    if (!dst) return fail(h, TETSIM_EINVAL, "dst is null");
-    if (!record_stride_ok(row_stride, row, 4u)) return fail(h, TETSIM_EINVAL, "row_stride must be 0 or a multiple of 4 of at least 64");
-    if (int rc = device_call_guard(h)) return rc;
-    const uint64_t stride = row_stride ? row_stride : row;
-    if (int rc = check_device_records(h, dst, stride, h->info.num_elems, row, 4u, "dst")) return rc;
+    uint64_t stride;
+    if (int rc = check_dst_rows(h, dst, row_stride, h->info.num_elems, 4ull * TETSIM_STRAIN_WIDTH, 4u, &stride)) return rc;
     if (h->info.num_elems == 0) return 0;
     // ---- every argument is good: from here on only allocation and HIP itself can fail
     if (int rc = ensure_tables(h)) return rc;
@@ -331,24 +274,17 @@ int tetsim_read_tet_strain(tetsim_handle h, float* out) {
     if (int rc = device_call_guard(h)) return rc;
     if (h->info.num_elems == 0) return 0;
     if (int rc = ensure_tables(h)) return rc;
-    if (int rc = enqueue_chunks(h, h->strain.rows, 4ull * TETSIM_STRAIN_WIDTH, false)) return rc;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipMemcpy(out, h->strain.rows, static_cast<size_t>(h->info.num_elems) * TETSIM_STRAIN_WIDTH * sizeof(float), hipMemcpyDeviceToHost));
-    return 0;
+    return read_back(h, out, h->strain.rows, static_cast<size_t>(h->info.num_elems) * TETSIM_STRAIN_WIDTH, [&] { return enqueue_chunks(h, h->strain.rows, 4ull * TETSIM_STRAIN_WIDTH, false); });
 }
 
 int tetsim_body_strain_device(tetsim_handle h, void* dst, uint64_t row_stride, void* caller_stream) {
     if (!h) return TETSIM_EINVAL;
-    constexpr uint64_t row = 8ull * TETSIM_STRAIN_BODY_WIDTH;
-    if (!dst) return fail(h, TETSIM_EINVAL, "dst is null");
-    if (!record_stride_ok(row_stride, row, 8u)) return fail(h, TETSIM_EINVAL, "row_stride must be 0 or a multiple of 8 of at least 64");
-    if (int rc = device_call_guard(h)) return rc;
-    const uint64_t stride = row_stride ? row_stride : row;
-    if (int rc = check_device_records(h, dst, stride, h->info.num_bodies, row, 8u, "dst")) return rc;
+    uint64_t stride;
+    if (int rc = check_dst_rows(h, dst, row_stride, h->info.num_bodies, 8ull * TETSIM_STRAIN_BODY_WIDTH, 8u, &stride)) return rc;
     if (int rc = ensure_tables(h)) return rc;
     return on_caller_stream(h, caller_stream, [&]() -> int {
         if (int rc = enqueue_chunks(h, nullptr, 0, true)) return rc;
-        hipLaunchKernelGGL(strain_finish_kernel, dim3(h->info.num_bodies), dim3(256), 0, h->stream, static_cast<const StrainBody*>(h->strain.bodies),
+        hipLaunchKernelGGL(strain_finish_kernel, dim3(h->info.num_bodies), dim3(256), 0, h->stream, h->chunk_table[kTetChunks].bodies,
                            static_cast<const double*>(h->strain.partial), static_cast<char*>(dst), stride);
         return launched(h);
     });
@@ -368,10 +304,10 @@ int tetsim_visual_strain_device(tetsim_handle h, int32_t channel, void* dst, uin
     if (int rc = ensure_tables(h)) return rc;
     if (int rc = ensure_visual_table(h)) return rc;
     return on_caller_stream(h, caller_stream, [&]() -> int {
-        FieldSrc src;
-        if (int rc = positions(h, &src)) return rc;
+        FieldSrc src[1];
+        if (int rc = export_sources(h, {TETSIM_FIELD_POSITIONS}, src)) return rc;
         hipLaunchKernelGGL(strain_visual_kernel, dim3((nvis + 255u) / 256u), dim3(256), 0, h->stream, h->strain.vis_tet, nvis, static_cast<const StrainRec*>(h->strain.table),
-                           src.src, src.mapped ? h->d_api2dev : nullptr, static_cast<uint32_t>(channel), static_cast<char*>(dst), stride);
+                           src[0].src, src[0].mapped ? h->d_api2dev : nullptr, static_cast<uint32_t>(channel), static_cast<char*>(dst), stride);
         return launched(h);
     });
 }
