@@ -497,7 +497,7 @@ int tetsim_set_colliders(tetsim_handle h, const TetSimCollider *colliders, uint3
  * Cost, measured on an MI355X (tools/body_grabs_cost.py, profiles/body_grabs_cost.txt): never switched on, the benchmark
  * line is inside the parent's run-to-run spread; 64 Dragons in one batch with every body held against none held, one call of 20
  * substeps: polar FAST x1.20, Neo-Hookean FAST x0.99-1.02.
- * Out of scope: more than one grab per body; per-body colliders or parameters; partitioned bodies; gradients; a Node binding. */
+ * Out of scope: more than one grab per body; per-body parameters; partitioned bodies; gradients; a Node binding. */
 
 /* particles [num_bodies] int32: index INSIDE the body (0 = the body's first particle), -1 = this body is not held.
  * targets [num_bodies] rows of 3 f32.  particles == NULL: body grabs OFF (targets ignored). */
@@ -516,6 +516,70 @@ int tetsim_set_body_grabs_device(tetsim_handle h, const void *particles, const v
  * bodies.  The ids it writes are directly the `particles` argument of tetsim_set_body_grabs_device. */
 int tetsim_nearest_particles_device(tetsim_handle h, const void *points, uint64_t point_stride,
                                     void *ids, void *dist2, void *caller_stream);
+
+/* --- body colliders: up to eight colliders per body of a batch, settable from device memory ------ */
+
+/* tetsim_set_colliders gives ONE list, from host memory, to every body of the handle.  The body-collider table gives EVERY body
+ * (tetsim_create_batch; a single body is a batch of one) a list of its own -- a pusher, a jaw, a paddle, a tilted tray per
+ * environment -- and a GPU-side loop can write it without the host.  An ADDITIVE extension of ABI version 5 (TETSIM_ABI_VERSION is
+ * unchanged; no existing struct changed): look the symbols up.
+ *
+ * A row is TETSIM_BODY_COLLIDER_FLOATS f32, the fields of TetSimCollider in its order:
+ *   [0] kind as a value (0.0 sphere, 1.0 capsule, 2.0 box, 3.0 plane; -1.0 = the slot is empty)   [1..3] a   [4..6] b   [7..15] axes
+ *   [16] radius   [17] friction   [18..20] velocity   [21..23] never read
+ * per_body (1 .. TETSIM_MAX_COLLIDERS) rows belong to each body, body-major: row (b, k) is row b * per_body + k.
+ *
+ * THE CONTRACT.  While body colliders are ON, a particle of body b meets the non-empty rows of body b, in slot order, exactly where and
+ * how the handle's list acts on that path: after clamp, floor and grab, before the velocity, never on a held particle (held by
+ * tetsim_set_grab or by the body's row of tetsim_set_body_grabs).  The arithmetic is the one defined above for tetsim_set_colliders.
+ * Body b of a batch with rows r0 .. rk gives the bits that body b created alone gives with tetsim_set_colliders of the same rows
+ * widened to double (every f32 is exactly a double), for both solvers, both precisions, every stepping path, tetsim_step and
+ * tetsim_step_n.  A handle that never switches body colliders on executes what it always executed plus one uniform branch per
+ * particle pass.  WHILE THEY ARE ON, the bodies whose call is one launch step through their stepwise kernels instead, which agree
+ * with it bit for bit as they always have (TetSimInfo.fused_particle_pass keeps naming the body's own path): quad tiles
+ * (fused_particle_pass 3) take two launches per substep, small Neo-Hookean bodies (4) a launch per level and body, clustered FAST
+ * Neo-Hookean bodies a launch per colour.  Those one-launch kernels have no register for a second kind of list.
+ *
+ * The table lives in device memory owned by the handle: per body a count and up to eight compacted entries in the arithmetic view
+ * the handle reads (f32 for POLAR_JACOBI and FAST NEOHOOKEAN_GS, f64 for PRECISE NEOHOOKEAN_GS), and the body index per particle it
+ * shares with the body grabs; it counts into device_bytes.  The first set call allocates it with every body empty; it is the only
+ * call that may block.  A set call writes the table with one small kernel (a lane per body) on the handle's stream, behind every
+ * substep enqueued so far; every substep enqueued afterwards sees it.  Per row the kernel does what tetsim_set_colliders does on
+ * the host: the same validity rules, the same f64 normalisation of the plane normal and the box axes, v / sqrt((v0*v0 + v1*v1) +
+ * v2*v2), the same orthogonality test |u_i . u_j| > 1e-5, radius 0 for boxes and planes, the f32 view rounded once from the f64
+ * view.  tetsim_set_body_colliders_device follows the stream contract of tetsim_import_device (the handle's stream waits for
+ * caller_stream, the kernel runs, caller_stream waits for the kernel; the host never reads the rows and never synchronises).
+ * Switching OFF (rows == NULL) is host state; it also empties every body.  The table is not solver state: checkpoints and
+ * snapshots do not hold it, and their sizes do not change.
+ *
+ * Rows the host cannot see: a row tetsim_set_colliders would refuse -- a kind other than 0, 1, 2, 3 and -1; a non-finite value in
+ * any of floats 0 .. 20; a negative radius, half-extent or friction; a zero normal or axis; axes that are not orthogonal -- becomes an
+ * EMPTY SLOT.  It disturbs no other row and no other body, and the remaining rows keep their order.  A body the mask leaves out
+ * keeps its whole list.  The host variant refuses the same cases (other than kind -1) with TETSIM_EINVAL, names the body and the
+ * slot in tetsim_last_error, and leaves the table as it was.
+ *
+ * One kind of list at a time: with body colliders ON, tetsim_set_colliders with count > 0 returns TETSIM_ESTATE (count 0 stays
+ * legal); switching body colliders ON while the handle's list is non-empty is TETSIM_ESTATE.  A shared obstacle goes into every
+ * body's rows.  Also TETSIM_ESTATE: any partitioned body.  TETSIM_EINVAL: a NULL handle; per_body 0 or above TETSIM_MAX_COLLIDERS;
+ * a stride that is neither 0 nor a multiple of 4 of at least 96; a pointer that is not 4-byte aligned, that hipPointerGetAttributes
+ * does not place on the handle's device, or whose rows do not fit its allocation.  Every error is found before anything is enqueued.
+ * Cost, measured on an MI355X (tools/body_colliders_cost.py, profiles/body_colliders_cost.txt): never switched on, the
+ * benchmark line is inside the parent's run-to-run spread (32,676 .. 32,731 against 32,664 .. 32,811 M tet-solves/s, medians 32,685 and
+ * 32,734) and pjb_call_kernel, pjb_frame_kernel and pjq_frame_kernel keep their registers (62, 162, 127; no scratch); 64 Dragons in
+ * one batch, one call of 20 substeps, four colliders per body against the same four as the handle's list x1.01 (against none x1.37,
+ * the list's own cost); one Dragon of quad tiles x1.76 and 64 small lattices of quad tiles x1.99 against the list (two launches per
+ * substep); 64 Dragons Neo-Hookean FAST x207 (2.49 s against 12 ms: 43,520 level launches in place of one workgroup per body -- a
+ * batch of small Neo-Hookean bodies pays dearly for the table); the set kernel takes 37 us for 64 bodies and 45 us for 4,096.
+ * Out of scope: per-body physicsParams; more than eight colliders per body; f64 rows; colliders
+ * between bodies; partitioned bodies; contact read-back; a Node binding. */
+#define TETSIM_BODY_COLLIDER_FLOATS 24
+/* rows: num_bodies * per_body rows of 24 f32, body-major (row of body b, slot k at index b * per_body + k), packed.
+ * rows == NULL: body colliders OFF (per_body ignored). */
+int tetsim_set_body_colliders(tetsim_handle h, const float *rows, uint32_t per_body);
+/* The same from DEVICE memory: row (b, k) at rows + (b * per_body + k) * row_stride (0 = packed 96; else a multiple of 4, >= 96);
+ * body_mask as for tetsim_set_body_grabs_device (num_bodies bytes, nonzero = take this body's rows; NULL = all). */
+int tetsim_set_body_colliders_device(tetsim_handle h, const void *rows, uint64_t row_stride, uint32_t per_body,
+                                     const void *body_mask, void *caller_stream);
 
 /* --- device-side export and import: results for another GPU program, without a host copy -------- */
 
@@ -560,7 +624,7 @@ int tetsim_nearest_particles_device(tetsim_handle h, const void *points, uint64_
  * VISUAL_NORMALS on a NEOHOOKEAN_GS body (VISUAL_NORMALS also needs the rest normals of tetsim_set_visual_mesh); PREV_POSITIONS on
  * a POLAR_JACOBI body; a visual field without a visual mesh, VISUAL_VERTEX_NORMALS without triangles; any partitioned body (its halo
  * stream and ghosts need a contract of their own).
- * Out of scope: partitioned bodies; element types other than f32; gradients; device-resident collider lists. */
+ * Out of scope: partitioned bodies; element types other than f32; gradients. */
 enum { TETSIM_FIELD_POSITIONS = 0, TETSIM_FIELD_VELOCITIES = 1, TETSIM_FIELD_PREV_POSITIONS = 2,
        TETSIM_FIELD_QUATS = 3, TETSIM_FIELD_VISUAL_POSITIONS = 4, TETSIM_FIELD_VISUAL_NORMALS = 5,
        TETSIM_FIELD_VISUAL_VERTEX_NORMALS = 6 };
@@ -904,8 +968,8 @@ int tetsim_prep_pose_table(const float *verts, uint32_t nv, const int32_t *tets,
  * partitioned body; with ray_body != NULL a triangle whose three rows belong to different bodies (found once on the host; such a
  * mesh still casts with ray_body == NULL).  count == 0 succeeds and enqueues nothing.
  * Out of scope: partitioned bodies; an acceleration structure; all hits along a ray; back-side or double-side materials; f32 rays or
- * hits; rays attached to a moving frame (the caller transforms them, on the device, before the call); gradients; device-resident
- * collider lists; a Node binding (Node has no device tensors). */
+ * hits; rays attached to a moving frame (the caller transforms them, on the device, before the call); gradients; a Node
+ * binding (Node has no device tensors). */
 #define TETSIM_RAY_INVALID (-1)   /* TetSimRayHit.hit of a ray the device refused */
 int tetsim_raycast_visual_device(tetsim_handle h,
         const void *rays,     uint64_t ray_stride,   /* DEVICE: count TetSimRay records (64 B); stride 0 = packed, else a multiple of 8, >= 64 */

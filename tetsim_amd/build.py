@@ -45,6 +45,8 @@ UNITS = {
     "pose.hip": ["-ffp-contract=off"],
     # the nearest query's f64 squared distance is tetsim_nearest_particle's, compared bit for bit: every multiply and add rounded on its own
     "body_grabs.hip": ["-ffp-contract=off"],
+    # the set kernel normalises plane normals and box axes in f64 exactly as tetsim_set_colliders does on the host: every operation rounded on its own
+    "body_colliders.hip": ["-ffp-contract=off"],
     # the rigid motion is defined in f64 with every operation rounded on its own: tests/place_ref.py reproduces it value for value in numpy
     "place.hip": ["-ffp-contract=off"],
     "tetsim_create.hip": ["-ffp-contract=off"],

@@ -17,6 +17,8 @@
 //                      rotation (Horn's quaternion by a fixed Jacobi procedure), angular velocity and momentum
 //   body_grabs.hip     one held particle per body of a batch, set from host or device memory (tetsim_set_body_grabs / _device): the table the
 //                      particle passes read; the nearest particle of every body on the device (tetsim_nearest_particles_device)
+//   body_colliders.hip up to eight kinematic colliders per body of a batch, set from host or device memory (tetsim_set_body_colliders /
+//                      _device): the table collide.h's routines walk in place of the handle's list, one set kernel, a lane per body
 //   place.hip          a rigid motion of chosen bodies' complete state, rows and mask in device memory (tetsim_place_bodies / _device): one
 //                      kernel over every section of state_sections(), a row's body from the snapshots' tables
 //   tetsim_measure.hip measurement: per-kernel profile, kernel timing loops, device copy bandwidth
@@ -245,8 +247,15 @@ struct tetsim_body {
     // device order, a 16-byte row per body -- is made by the first set call and keeps its addresses (fill_params copies them into
     // DevParams); ON / OFF is host state and travels as DevParams::body_grabs.  Not solver state: no checkpoint or snapshot holds it.
     bool body_grabs_on = false;
-    uint32_t* d_grab_body = nullptr;    // [particles]
+    uint32_t* d_grab_body = nullptr;    // [particles]; made by whichever of body grabs and body colliders is set first (ensure_particle_bodies)
     int4* d_grab_rows = nullptr;        // [bodies]
+    // body colliders (tetsim_set_body_colliders / _device, body_colliders.hip): per body a count and kMaxColliders compacted entries, in the
+    // view this handle's arithmetic reads (f32: polar, FAST Neo-Hookean; f64: PRECISE Neo-Hookean -- the other pointer stays null).  Made by
+    // the first set call, every body empty; ON / OFF is host state and travels as DevParams::body_colliders.  Not solver state either.
+    bool body_colliders_on = false;
+    uint32_t* d_bcol_count = nullptr;   // [bodies]
+    DevColliderF* d_bcol_f = nullptr;   // [bodies][kMaxColliders]
+    DevColliderD* d_bcol_d = nullptr;   // [bodies][kMaxColliders]
     uint32_t* d_body_first = nullptr;   // [bodies + 1] first particle of every body in the CALLER's numbering (also tetsim_nearest_particles_device)
     // tetsim_nearest_particles_device: a candidate per chunk of the particle chunk table (below)
     double* d_near_d2 = nullptr;
@@ -576,6 +585,11 @@ bool record_stride_ok(uint64_t stride, uint64_t row_bytes, uint32_t align);
 int check_device_records(tetsim_body* h, const void* ptr, uint64_t stride, uint32_t rows, uint64_t row_bytes, uint32_t align, const std::string& what);
 extern const char* const kPartitionedIo;           // the refusal of a partitioned body, one text for every device-side call
 extern const char* const kBodyGrabsOn;             // the refusal of the handle's grab while body grabs are on (body_grabs.hip)
+extern const char* const kBodyCollidersOn;         // the refusal of a non-empty handle list while body colliders are on (body_colliders.hip)
+// what the per-body tables start from (body_grabs.hip; the first call of each may block)
+uint32_t num_bodies(const tetsim_body* h);
+int ensure_body_first(tetsim_body* h);             // d_body_first and the index map
+int ensure_particle_bodies(tetsim_body* h);        // d_grab_body: the body of every particle in DEVICE particle order
 void release_snapshots(tetsim_body* h);            // tetsim_destroy: the snapshots that are left (snapshot.hip)
 int ensure_snapshot_body_tables(tetsim_body* h);   // d_snap_first_vert / _first_elem / _tet_body, uploaded once (snapshot.hip: ensure_body_tables; may block)
 

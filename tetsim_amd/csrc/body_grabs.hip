@@ -13,6 +13,36 @@ namespace tetsim {
 
 const char* const kBodyGrabsOn = "body grabs are on (tetsim_set_body_grabs): one kind of grab at a time -- switch them off first";
 
+uint32_t num_bodies(const tetsim_body* h) { return is_batch(h) ? static_cast<uint32_t>(h->batch_first_vert.size() - 1u) : 1u; }
+
+// [bodies + 1] first particle of every body (caller's numbering) on the device, and the index map: what both features start from
+int ensure_body_first(tetsim_body* h) {
+    if (h->d_body_first) return ensure_index_map(h);
+    std::vector<uint32_t> first_vert, first_tet;
+    body_ranges(h, &first_vert, &first_tet);
+    if (int rc = dev_alloc(h, &h->d_body_first, first_vert.size())) return rc;
+    if (int rc = upload(h, h->d_body_first, first_vert)) return rc;
+    return ensure_index_map(h);
+}
+
+// the body of every particle in DEVICE particle order, a constant: what the particle passes index the per-body tables with (body grabs,
+// body colliders -- whichever is set first makes it; its address never changes)
+int ensure_particle_bodies(tetsim_body* h) {
+    if (h->d_grab_body) return 0;
+    if (int rc = ensure_body_first(h)) return rc;
+    std::vector<uint32_t> first_vert, first_tet;
+    body_ranges(h, &first_vert, &first_tet);
+    const uint32_t nv = h->info.num_particles, nb = num_bodies(h);
+    std::vector<uint32_t> body(nv);
+    for (uint32_t b = 0; b < nb; b++)
+        for (uint32_t a = first_vert[b]; a < first_vert[b + 1u]; a++) body[h->api2dev.empty() ? a : h->api2dev[a]] = b;
+    uint32_t* d_body = nullptr;
+    if (int rc = dev_alloc(h, &d_body, body.size())) return rc;
+    if (int rc = upload(h, d_body, body)) return rc;
+    h->d_grab_body = d_body;
+    return 0;
+}
+
 namespace {
 
 constexpr uint32_t kNearChunk = kBodyChunk;   // particles per candidate, counted from the body's own first particle: nearest_kernel's blocks of the body alone
@@ -94,36 +124,14 @@ __global__ __launch_bounds__(256) void near_body_kernel(const double* __restrict
     if (dist2) dist2[b] = best;
 }
 
-uint32_t num_bodies(const tetsim_body* h) { return is_batch(h) ? static_cast<uint32_t>(h->batch_first_vert.size() - 1u) : 1u; }
-
-// [bodies + 1] first particle of every body (caller's numbering) on the device, and the index map: what both features start from
-int ensure_body_first(tetsim_body* h) {
-    if (h->d_body_first) return ensure_index_map(h);
-    std::vector<uint32_t> first_vert, first_tet;
-    body_ranges(h, &first_vert, &first_tet);
-    if (int rc = dev_alloc(h, &h->d_body_first, first_vert.size())) return rc;
-    if (int rc = upload(h, h->d_body_first, first_vert)) return rc;
-    return ensure_index_map(h);
-}
-
 // the table, every row "none" (the first set call: allocates and uploads, so it may block)
 int ensure_grab_table(tetsim_body* h) {
     if (h->d_grab_rows) return 0;
-    if (int rc = ensure_body_first(h)) return rc;
-    std::vector<uint32_t> first_vert, first_tet;
-    body_ranges(h, &first_vert, &first_tet);
-    const uint32_t nv = h->info.num_particles, nb = num_bodies(h);
-    std::vector<uint32_t> body(nv);
-    for (uint32_t b = 0; b < nb; b++)
-        for (uint32_t a = first_vert[b]; a < first_vert[b + 1u]; a++) body[h->api2dev.empty() ? a : h->api2dev[a]] = b;
-    const std::vector<int4> none(nb, make_int4(-1, 0, 0, 0));
-    uint32_t* d_body = nullptr;
+    if (int rc = ensure_particle_bodies(h)) return rc;
+    const std::vector<int4> none(num_bodies(h), make_int4(-1, 0, 0, 0));
     int4* d_rows = nullptr;
-    if (int rc = dev_alloc(h, &d_body, body.size())) return rc;
-    if (int rc = upload(h, d_body, body)) return rc;
     if (int rc = dev_alloc(h, &d_rows, none.size())) return rc;
     if (int rc = upload(h, d_rows, none)) return rc;
-    h->d_grab_body = d_body;
     h->d_grab_rows = d_rows;
     return 0;
 }

@@ -1,7 +1,10 @@
 // collide.h -- kinematic colliders (tetsim_set_colliders, include/tetsim.h): one particle against the call's list, ONE routine per
 // arithmetic, inlined into every particle pass (pj_kernels.inc, pjb_vertex_update in pj_blocked.hip, pjq_vertex_update in pj_quad.hip,
 // post_vertex in nh_kernels.inc).  They run after the clamp, floor and grab, before the velocity; the caller skips grabbed particles
-// and calls them only when DevParams::n_colliders != 0 (a uniform scalar test: a body without colliders runs its old code).
+// and calls them only when DevParams::n_colliders != 0 or DevParams::body_colliders != 0 (a uniform scalar test: a body without colliders
+// runs its old code).  The routines walk a list (dt, entries, count); where the list comes from is the caller's business -- the handle's
+// list in DevParams (uniform addresses: scalar loads) or, with body colliders on (tetsim_set_body_colliders), the entries of the
+// particle's body in the table (dev_common.h: body_colliders_pick), made uniform wave by wave -- collide_particle_* below.
 //
 // The definition (tetsim.h restates it), p = position so far, q = end of the previous substep, dot(u, v) = (u.x*v.x + u.y*v.y) + u.z*v.z:
 //   sphere   d = p - a, L = sqrt(dot(d, d)); hit = L < r && L > 0; n = d / L, depth = r - L
@@ -50,13 +53,13 @@ __device__ __forceinline__ double js_min(double a, double b) {
 
 }  // namespace collide
 
-// One particle (px, py, pz) against every collider of P, in list order; (qx, qy, qz) = end of the previous substep.  f32 view.
+// One particle (px, py, pz) against the `count` colliders of `col`, in list order; (qx, qy, qz) = end of the previous substep.  f32 view.
 template <bool kFast>
-__device__ __forceinline__ void collide_f32(float& px, float& py, float& pz, const float qx, const float qy, const float qz, const DevParams& P) {
+__device__ __forceinline__ void collide_f32(float& px, float& py, float& pz, const float qx, const float qy, const float qz, const float dt,
+                                            const DevColliderF* col, const uint32_t count) {
     using namespace collide;
-    const float dt = P.dt;
-    for (uint32_t k = 0; k < P.n_colliders; k++) {
-        const DevColliderF& C = P.col[k];
+    for (uint32_t k = 0; k < count; k++) {
+        const DevColliderF& C = col[k];
         bool hit = false;
         float nx = 0.0f, ny = 0.0f, nz = 0.0f, depth = 0.0f;
         if (C.kind == 0 || C.kind == 1) {   // sphere, capsule: the distance to a point (the centre, the nearest point of the segment)
@@ -112,13 +115,19 @@ __device__ __forceinline__ void collide_f32(float& px, float& py, float& pz, con
     }
 }
 
+// ... against the handle's list (the form every call site had before there were two kinds of list: the same text, the same bits)
+template <bool kFast>
+__device__ __forceinline__ void collide_f32(float& px, float& py, float& pz, const float qx, const float qy, const float qz, const DevParams& P) {
+    collide_f32<kFast>(px, py, pz, qx, qy, qz, P.dt, P.col, P.n_colliders);
+}
+
 // The same in Softbody.js's arithmetic (PRECISE Neo-Hookean): f64 view of the colliders, f64 dt, f32 stores.
-__device__ __forceinline__ void collide_f64(float& px, float& py, float& pz, const float qx, const float qy, const float qz, const DevParams& P) {
+__device__ __forceinline__ void collide_f64(float& px, float& py, float& pz, const float qx, const float qy, const float qz, const double dt,
+                                            const DevColliderD* col, const uint32_t count) {
     using collide::js_max;
     using collide::js_min;
-    const double dt = P.d_dt;
-    for (uint32_t k = 0; k < P.n_colliders; k++) {
-        const DevColliderD& C = P.d_col[k];
+    for (uint32_t k = 0; k < count; k++) {
+        const DevColliderD& C = col[k];
         const double x = px, y = py, z = pz;
         bool hit = false;
         double nx = 0.0, ny = 0.0, nz = 0.0, depth = 0.0;
@@ -169,6 +178,42 @@ __device__ __forceinline__ void collide_f64(float& px, float& py, float& pz, con
         px = static_cast<float>(static_cast<double>(px) + (Dx - nx * dn) * m);
         py = static_cast<float>(static_cast<double>(py) + (Dy - ny * dn) * m);
         pz = static_cast<float>(static_cast<double>(pz) + (Dz - nz * dn) * m);
+    }
+}
+__device__ __forceinline__ void collide_f64(float& px, float& py, float& pz, const float qx, const float qy, const float qz, const DevParams& P) {
+    collide_f64(px, py, pz, qx, qy, qz, P.d_dt, P.d_col, P.n_colliders);
+}
+
+// The uniform test of every call site, and what stands behind it.  A wave may hold particles of several bodies (the particle kernels' blocks
+// span bodies): the lanes that have a particle to push (`push`: not held) are served body by body -- the first waiting lane's body index
+// becomes a uniform value, the lanes of that body walk its list, read with scalar loads, and leave; one trip while body colliders are off
+// (every lane says body 0, the list is the handle's) and wherever a wave holds one body.  No arithmetic of its own.
+__device__ __forceinline__ bool any_colliders(const DevParams& P) { return (P.n_colliders | P.body_colliders) != 0u; }
+template <bool kFast>
+__device__ __forceinline__ void collide_particle_f32(float& px, float& py, float& pz, const float qx, const float qy, const float qz, const DevParams& P, const uint32_t v, bool push) {
+    const uint32_t body = body_colliders_body(P, v);
+    while (push) {
+        const uint32_t now = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int32_t>(body)));
+        if (body == now) {
+            const DevColliderF* list;
+            uint32_t count;
+            body_colliders_pick(P, now, &list, &count);
+            collide_f32<kFast>(px, py, pz, qx, qy, qz, P.dt, list, count);
+            push = false;
+        }
+    }
+}
+__device__ __forceinline__ void collide_particle_f64(float& px, float& py, float& pz, const float qx, const float qy, const float qz, const DevParams& P, const uint32_t v, bool push) {
+    const uint32_t body = body_colliders_body(P, v);
+    while (push) {
+        const uint32_t now = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int32_t>(body)));
+        if (body == now) {
+            const DevColliderD* list;
+            uint32_t count;
+            body_colliders_pick(P, now, &list, &count);
+            collide_f64(px, py, pz, qx, qy, qz, P.d_dt, list, count);
+            push = false;
+        }
     }
 }
 

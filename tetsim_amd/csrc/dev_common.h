@@ -29,7 +29,8 @@ struct DevParams {
     // f32 view -- POLAR_JACOBI: the reference uploads these as f32 uniforms (SoftbodyGPU.js:614-637)
     float dt, gravity, friction;
     uint32_t body_grabs;   // non-zero: the body-grab table below decides which particles are held, grab / grab_local are not looked at (tetsim_set_body_grabs)
-    float lo[3], pad1;
+    float lo[3];
+    uint32_t body_colliders;   // non-zero: a particle meets the rows of ITS body in the table below (tetsim_set_body_colliders); n_colliders is 0 then
     float hi[3], pad2;
     float grab[3];
     int32_t grab_local;  // local vertex index, -1 = none
@@ -44,6 +45,12 @@ struct DevParams {
     // {device particle or -1, target x, y, z as float bits}.  Both null until the handle's first set call; their addresses never change.
     const uint32_t* grab_body;
     const int4* grab_rows;
+    // body colliders (body_colliders.hip): per body a count and kMaxColliders compacted entries, in the view this handle's arithmetic
+    // reads (f32: polar, FAST Neo-Hookean; f64: PRECISE Neo-Hookean) -- the other pointer stays null.  Indexed through grab_body, which
+    // either feature's first set call makes.  Null until then; the addresses never change.
+    const uint32_t* bcol_count;
+    const DevColliderF* bcol_f;
+    const DevColliderD* bcol_d;
     // kinematic colliders (collide.h): entries [0, n_colliders) are meaningful, in both views.  Behind every field above, so that a
     // body without colliders reads what it always read at the offsets it always read it from.
     DevColliderF col[kMaxColliders];     // f32 view: polar solver, FAST Neo-Hookean
@@ -77,6 +84,19 @@ __device__ __forceinline__ void body_grab_pick(const DevParams& P, uint32_t v, b
         held = row.x == static_cast<int32_t>(v);
         if (held) { x = __int_as_float(row.y); y = __int_as_float(row.z); z = __int_as_float(row.w); }
     }
+}
+// Body colliders in a particle pass (tetsim_set_body_colliders): the list a particle of `body` meets -- the body's entries of the table while
+// body colliders are on, the handle's list otherwise (the two never hold entries at once: body_colliders.hip) -- in the view the caller's
+// arithmetic reads.  Only addresses: the arithmetic is collide.h's, whichever list it walks.  Called with a UNIFORM body index (collide.h
+// makes it one, wave by wave; pj_quad.hip's tiles hold one body), so the entries arrive through scalar loads, as the handle's list does.
+__device__ __forceinline__ uint32_t body_colliders_body(const DevParams& P, uint32_t v) { return P.body_colliders ? P.grab_body[v] : 0u; }   // v: a particle of the body (device index), as for body_grab_pick
+__device__ __forceinline__ void body_colliders_pick(const DevParams& P, uint32_t body, const DevColliderF** list, uint32_t* count) {
+    *list = P.col; *count = P.n_colliders;
+    if (P.body_colliders) { *list = P.bcol_f + static_cast<size_t>(body) * kMaxColliders; *count = P.bcol_count[body]; }
+}
+__device__ __forceinline__ void body_colliders_pick(const DevParams& P, uint32_t body, const DevColliderD** list, uint32_t* count) {
+    *list = P.d_col; *count = P.n_colliders;
+    if (P.body_colliders) { *list = P.bcol_d + static_cast<size_t>(body) * kMaxColliders; *count = P.bcol_count[body]; }
 }
 
 // ---- POLAR_JACOBI device state (all arrays 16-byte elements: one dwordx4 per lane) ----------------

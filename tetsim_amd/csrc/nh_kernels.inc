@@ -280,6 +280,10 @@ __device__ __forceinline__ T js_min(T a, T b) {
 }
 
 // bounds / floor friction / grab / velocity, Softbody.js:213-239: (pos, prev) in, (pos, vel) out
+// kBodyColliders: the pass also serves body colliders (tetsim_set_body_colliders).  The stepwise kernels do; the one-launch kernels
+// (nh_frame_kernel, nh_sweep1_kernel, nh_call_kernel) do not -- with the second list they lose a wave of occupancy or gain a stack -- so
+// a body steps through the stepwise kernels while body colliders are on (tetsim_api.hip: nh_frame_now, nh_one_now); they agree bit for bit.
+template <bool kBodyColliders = true>
 __device__ __forceinline__ void post_vertex(const VParams& P, uint32_t v, float4& pos, const float4& prev, float4& vel) {
     const T dt = P.dt, friction = P.friction;
     const T* lo = P.lo;
@@ -303,7 +307,15 @@ __device__ __forceinline__ void post_vertex(const VParams& P, uint32_t v, float4
         grabbed = row.x == static_cast<int32_t>(v);
         if (grabbed) { pos.x = __int_as_float(row.y); pos.y = __int_as_float(row.z); pos.z = __int_as_float(row.w); }
     }
-    if (P.all->n_colliders != 0u && !grabbed) {   // kinematic colliders (collide.h)
+    if constexpr (kBodyColliders) {
+        if (any_colliders(*P.all)) {   // kinematic colliders (collide.h): the handle's list or, with body colliders on, the body's
+#if TETSIM_FAST
+            collide_particle_f32<true>(pos.x, pos.y, pos.z, prev.x, prev.y, prev.z, *P.all, v, !grabbed);
+#else
+            collide_particle_f64(pos.x, pos.y, pos.z, prev.x, prev.y, prev.z, *P.all, v, !grabbed);
+#endif
+        }
+    } else if (P.all->n_colliders != 0u && !grabbed) {   // kinematic colliders (collide.h), the handle's list alone
 #if TETSIM_FAST
         collide_f32<true>(pos.x, pos.y, pos.z, prev.x, prev.y, prev.z, *P.all);
 #else
@@ -357,9 +369,10 @@ __global__ __launch_bounds__(256) void TETSIM_SFX(nh_post_predict_list_kernel_)(
 // kernels below): exactly nh_post_predict_kernel's operations on that particle -- the end of the previous substep, then this
 // substep's prediction -- so the trajectory is the same bit for bit; velocity and previous position go straight back to memory,
 // the predicted position is what the sweep then works on.
+template <bool kBodyColliders = true>
 __device__ __forceinline__ void fold_particle(const NHDev& d, const VParams& q, uint32_t v, float4& pos, const float4& prev_in) {
     float4 vel, prev;
-    post_vertex(q, v, pos, prev_in, vel);
+    post_vertex<kBodyColliders>(q, v, pos, prev_in, vel);
     predict_vertex(q, vel, pos, prev);
     store_wt(d.vel, v, vel);
     store_wt(d.prev, v, prev);
@@ -715,7 +728,7 @@ __global__ __launch_bounds__(512) void TETSIM_SFX(nh_frame_kernel_)(NHDev d, con
         for (uint32_t v = tid; v < nvb; v += nthr) {
             float4 pos = s_pos[v], vel;
             float4 prev = make_float4(s_prev[3u * v], s_prev[3u * v + 1u], s_prev[3u * v + 2u], 0.0f);
-            post_vertex(q, vbase + v, pos, prev, vel);
+            post_vertex<false>(q, vbase + v, pos, prev, vel);
             if (!last) {
                 predict_vertex(q, vel, pos, prev);
                 s_pos[v] = pos;
@@ -907,8 +920,8 @@ __global__ __launch_bounds__(256) void nh_sweep1_kernel(const NHSweepColour* __r
     if constexpr (kFold) {
         if (fmask & (0x11u << c)) {
             const VParams q = load_vparams(P);
-            if ((fmask >> c) & 1u) fold_particle(d, q, ua, ga, pa);
-            if ((fmask >> (c + 4u)) & 1u) fold_particle(d, q, ub, gb, pb);
+            if ((fmask >> c) & 1u) fold_particle<false>(d, q, ua, ga, pa);
+            if ((fmask >> (c + 4u)) & 1u) fold_particle<false>(d, q, ub, gb, pb);
         }
     }
     ga.w = ima; gb.w = imb;   // the inverse masses (lane 3 of a quad reads them from the fourth float below)
@@ -1026,7 +1039,7 @@ __global__ __launch_bounds__(256) void nh_call_kernel(const NHSweepColour* __res
         const VParams q = load_vparams(P);
         auto fold = [&](uint32_t v, float4& pos, const float4& prev_in, float4& prev) {
             float4 vel;
-            post_vertex(q, v, pos, prev_in, vel);
+            post_vertex<false>(q, v, pos, prev_in, vel);
             predict_vertex(q, vel, pos, prev);
             prev.w = __uint_as_float(sub_base);
         };

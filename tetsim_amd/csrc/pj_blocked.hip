@@ -87,7 +87,7 @@ __device__ __forceinline__ VertexOut pjb_vertex_update(f3 acc, float wsum, f3 pr
         p.x = fmaf(Fx, fr, p.x);
         p.z = fmaf(Fz, fr, p.z);
     }
-    if (P.n_colliders != 0u && !grabbed) collide_f32<true>(p.x, p.y, p.z, prev.x, prev.y, prev.z, P);   // kinematic colliders (collide.h)
+    if (any_colliders(P)) collide_particle_f32<true>(p.x, p.y, p.z, prev.x, prev.y, prev.z, P, v, !grabbed);   // kinematic colliders (collide.h): the handle's list or the body's
     // P7, :364-372, then P1 + P2 of the next substep
     const float dt = P.dt;
     const float rdt = __builtin_amdgcn_rcpf(dt);

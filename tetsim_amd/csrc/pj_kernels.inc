@@ -116,7 +116,7 @@ __global__ __launch_bounds__(256) void TETSIM_SFX(pj_vertex_kernel_)(PJDev d, ui
         p.x += F.x * fr;
         p.z += F.z * fr;
     }
-    if (P.n_colliders != 0u && !grabbed) collide_f32<kFast>(p.x, p.y, p.z, prev.x, prev.y, prev.z, P);   // kinematic colliders (collide.h)
+    if (any_colliders(P)) collide_particle_f32<kFast>(p.x, p.y, p.z, prev.x, prev.y, prev.z, P, v, !grabbed);   // kinematic colliders (collide.h): the handle's list or the body's
     // P7, :364-372
     const f3 dpos = p - prev;
     f3 vel;

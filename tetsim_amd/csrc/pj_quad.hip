@@ -171,6 +171,10 @@ __device__ __forceinline__ QParams load_qparams(const DevParams& P, uint32_t c, 
     return o;
 }
 struct QVertex { float p, vel, pred; };
+// kBodyColliders: the pass also serves body colliders (tetsim_set_body_colliders).  The two-launch substep does; the persistent frame kernel
+// does not -- its 128 registers hold the parent's code and not one value more (with the second list it spilled) -- so a quad body steps
+// through the two launches while body colliders are on (tetsim_api.hip: frame_now); the three agree bit for bit, as ever.
+template <bool kBodyColliders>
 __device__ __forceinline__ QVertex pjq_vertex_update(float acc, float wsum, float prev, const QParams& P, uint32_t vid, uint32_t c) {
     float p = acc * __builtin_amdgcn_rcpf(wsum);   // 0 * inf = NaN for a particle without tets, as in the reference
     // P6, SoftbodyGPU.js:340-355
@@ -183,6 +187,16 @@ __device__ __forceinline__ QVertex pjq_vertex_update(float acc, float wsum, floa
         float x = dpp<kLane0>(p), y = dpp<kLane1>(p), z = dpp<kLane2>(p);
         const float qx = dpp<kLane0>(prev), qy = dpp<kLane1>(prev), qz = dpp<kLane2>(prev);
         if (!grabbed) collide_f32<true>(x, y, z, qx, qy, qz, *P.all);
+        p = c == 0u ? x : c == 1u ? y : c == 2u ? z : p;
+    } else if (kBodyColliders && P.all->body_colliders != 0u) {   // body colliders (the handle's list is empty then): the same against the list of the
+        // tile's body.  A tile never spans two bodies and every lane of it carries a particle of the tile (idle lanes the tile's first), so the
+        // body index is the same in every lane: made uniform, the list is read with scalar loads like the handle's.
+        const DevColliderF* list;
+        uint32_t count;
+        body_colliders_pick(*P.all, static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int32_t>(P.all->grab_body[vid]))), &list, &count);
+        float x = dpp<kLane0>(p), y = dpp<kLane1>(p), z = dpp<kLane2>(p);
+        const float qx = dpp<kLane0>(prev), qy = dpp<kLane1>(prev), qz = dpp<kLane2>(prev);
+        if (!grabbed) collide_f32<true>(x, y, z, qx, qy, qz, P.dt, list, count);
         p = c == 0u ? x : c == 1u ? y : c == 2u ? z : p;
     }
     // P7, :364-372, then P1 + P2 of the next substep
@@ -315,7 +329,7 @@ __device__ __forceinline__ void pjq_body(const PJBlk& d, const DevParams& P, con
         float acc = 0.0f;
 #pragma unroll
         for (uint32_t j = 0; j < kQMaxSrc; j++) acc += g[j];   // absent = +0
-        return pjq_vertex_update(acc, wsum, prev, qp, vid, c);
+        return pjq_vertex_update<kMode != kModeFrame>(acc, wsum, prev, qp, vid, c);
     };
     auto store_particle = [&](const QVertex& o) {   // one writer per particle: lane 0 of the owning slot's quad
         const float4 p4 = make_float4(o.p, nxt(o.p), nx2(o.p), 0.0f), v4 = make_float4(o.vel, nxt(o.vel), nx2(o.vel), 0.0f),

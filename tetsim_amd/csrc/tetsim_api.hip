@@ -91,6 +91,11 @@ void fill_params(const tetsim_body* h, double dt, const TetSimParams& p, DevPara
     o->body_grabs = h->body_grabs_on ? 1u : 0u;
     o->grab_body = h->d_grab_body;
     o->grab_rows = h->d_grab_rows;
+    // body colliders (body_colliders.hip): likewise -- the switch, and the table's addresses (grab_body is shared with the body grabs)
+    o->body_colliders = h->body_colliders_on ? 1u : 0u;
+    o->bcol_count = h->d_bcol_count;
+    o->bcol_f = h->d_bcol_f;
+    o->bcol_d = h->d_bcol_d;
     o->epoch = h->frame_epoch;
     static const int32_t poll_delay = [] { const char* e = lab_env("TETSIM_QUAD_POLL_DELAY"); return e ? atoi(e) : kQuadPollDelay; }();
     o->poll_delay = poll_delay;
@@ -241,7 +246,7 @@ void pj_repredict(tetsim_body* h) {
 void nh_sweep(tetsim_body* h, bool fold, bool last, bool one_launch) {
     NHDev nh = h->nh;
     if (!last) nh.vol_err = nullptr;
-    if (one_launch && h->nh_one_launch) {   // clustered FAST: every colour in ONE launch, particles handed on with their stamp (nh_kernels.inc: nh_sweep1_kernel)
+    if (one_launch && h->nh_one_launch && !h->body_colliders_on) {   // (not while body colliders are on: tetsim_step, nh_one_now)   clustered FAST: every colour in ONE launch, particles handed on with their stamp (nh_kernels.inc: nh_sweep1_kernel)
         nh_launch_sweep1_fast(h->stream, nh, h->nh_sweep1, fold, h->nh_sub_index, h->nh_epoch_arg);
         return;
     }
@@ -687,17 +692,29 @@ int tetsim_get_info(tetsim_handle h, TetSimInfo* info) {
     return 0;
 }
 
+// The persistent frame kernel serves this call -- not while a quad body has body colliders on: pjq_frame_kernel has no register for a second
+// kind of list (pj_quad.hip: pjq_vertex_update), the body then takes the two launches per substep that tetsim_profile and the fall-back
+// take, which agree with the frame kernel bit for bit.
+static bool frame_now(const tetsim_body* h) { return h->frame && !(h->quad && h->body_colliders_on); }
+// Likewise the Neo-Hookean calls that are one launch: nh_frame_kernel, nh_sweep1_kernel and nh_call_kernel keep the parent's particle pass
+// (with the second list they lose a wave of occupancy or gain a stack: nh_kernels.inc, post_vertex), so while body colliders are on the
+// body steps through the level / cluster kernels and the particle kernels, which take the table and agree with them bit for bit.
+static bool nh_frame_now(const tetsim_body* h) { return h->nh_frame && !h->body_colliders_on; }
+static bool nh_one_now(const tetsim_body* h) { return h->nh_one_launch && !h->body_colliders_on; }
+// a captured graph holds the kernels of the way the body stepped when it was captured: one set of graphs per way
+static uint32_t graph_key(const tetsim_body* h, uint32_t n) { return h->nh_one_launch && h->body_colliders_on ? n | 0x80000000u : n; }
+
 int tetsim_step(tetsim_handle h, double dt, const TetSimParams* params) {
     if (!h) return TETSIM_EINVAL;
     if (!h->group.empty()) return fail(h, TETSIM_ESTATE, "this body belongs to an in-process group: step it with tetsim_group_step_n");
     HIPCHK(h, hipSetDevice(h->opt.device));
-    if (h->frame) {
+    if (frame_now(h)) {
         // small polar bodies: a single substep is ONE launch too -- the persistent frame kernel for n = 1, its parameters (and with them a
         // block of sequence numbers of its own) among its arguments: no upload, moving grab or not
         if (int rc = params_for_launch(h, dt, params)) return rc;
         return launch_in_turn(h, [&]() -> int { return launch_frame_kernel(h, 1u, 0u); });
     }
-    if (h->nh_frame) {
+    if (nh_frame_now(h)) {
         // small Neo-Hookean bodies: also a single substep is ONE single-workgroup launch (a host that keeps the reference's loop,
         // main.js:79-84, pays one enqueue per substep instead of one per level: 34 on the Dragon); tetsim_profile keeps the level kernels
         if (int rc = params_for_launch(h, dt, params)) return rc;
@@ -706,12 +723,12 @@ int tetsim_step(tetsim_handle h, double dt, const TetSimParams* params) {
     int rc = push_params(h, dt, params, true);   // (unchanged parameters stay where they are)
     if (rc) return rc;
     if ((rc = ensure_prediction(h, dt))) return rc;
-    if (h->nh_one_launch) {   // (the parameters on the device may be the previous call's: this launch brings its own block of stamps, like the frame kernel above)
+    if (nh_one_now(h)) {   // (the parameters on the device may be the previous call's: this launch brings its own block of stamps, like the frame kernel above)
         if (!h->epoch_block_fresh && (rc = next_epoch_block(h))) return rc;
         h->epoch_block_fresh = false;
         h->nh_epoch_arg = h->frame_epoch;
     }
-    if (h->nh_one_launch) rc = launch_in_turn(h, [&]() -> int { return enqueue_substep(h); });   // (see tetsim_step_n)
+    if (nh_one_now(h)) rc = launch_in_turn(h, [&]() -> int { return enqueue_substep(h); });   // (see tetsim_step_n)
     else rc = enqueue_substep(h);
     h->nh_epoch_arg = 0u;
     if (!rc) rc = flush_v(h);
@@ -742,7 +759,7 @@ int tetsim_step_n(tetsim_handle h, uint32_t n, double dt, const TetSimParams* pa
         }
     }
     HIPCHK(h, hipSetDevice(h->opt.device));
-    if (h->nh_call && h->nh_one_launch && !has_transport(h)) {
+    if (h->nh_call && nh_one_now(h) && !has_transport(h)) {
         // clustered FAST Neo-Hookean bodies: prediction | the sweeps of all n substeps in ONE launch (nh_kernels.inc: nh_call_kernel) | the kernel
         // that ends the call -- three direct launches, the first of which brings the call's parameters along
         if (int rc = params_for_launch(h, dt, params)) return rc;
@@ -753,18 +770,25 @@ int tetsim_step_n(tetsim_handle h, uint32_t n, double dt, const TetSimParams* pa
             return launched_with_params(h);
         });
     }
-    if (h->nh_frame) {   // small Neo-Hookean bodies: the whole call is ONE single-workgroup launch with every particle in LDS (nh_kernels.inc: nh_frame_kernel)
+    if (nh_frame_now(h)) {   // small Neo-Hookean bodies: the whole call is ONE single-workgroup launch with every particle in LDS (nh_kernels.inc: nh_frame_kernel)
         if (int rc = params_for_launch(h, dt, params)) return rc;
         return launch_nh_frame_kernel(h, n);
     }
-    if ((h->frame || h->pj_one_launch) && !has_transport(h)) {
+    if (h->nh_frame && !nh_frame_now(h)) {
+        // ... and with body colliders on its level kernels, launched one by one: the stepwise twin launches a kernel per level and BODY, and a
+        // batch's call is tens of thousands of them (64 Dragons x 34 levels x 20 substeps) -- too long a chain to capture as one graph
+        int rc = push_params(h, dt, params);
+        for (uint32_t i = 0; i < n && !rc; i++) rc = enqueue_substep(h, i == 0, i + 1 == n);
+        return rc;
+    }
+    if ((frame_now(h) || h->pj_one_launch) && !has_transport(h)) {
         // Calls that are ONE kernel -- small polar bodies: the persistent frame kernel, every tile's workgroup resident for the n substeps
         // (pjb_frame_kernel, pjq_frame_kernel); large ones: the n substeps' tiles and particles in one grid, handed on by stamped data
         // (pjb_call_kernel) -- are launched directly, one kernel needs no graph, with the call's parameters among the arguments.
         if (int rc = params_for_launch(h, dt, params)) return rc;
         // (in turn with an exclusive frame-kernel body, if one lives on this device: see the graph launch below)
         return launch_in_turn(h, [&]() -> int {
-            if (h->frame) return launch_frame_kernel(h, n, 0u);
+            if (frame_now(h)) return launch_frame_kernel(h, n, 0u);
             pjb_launch_call(h->stream, h->blk, h->call_sched, n, h->d_substep_err, halo_timeout_ms(h), h->params_on_device, h->d_params);
             return launched_with_params(h);
         });
@@ -811,7 +835,7 @@ int tetsim_step_n(tetsim_handle h, uint32_t n, double dt, const TetSimParams* pa
         for (uint32_t i = 0; i < n && !rc; i++) rc = enqueue_substep(h, i == 0, i + 1 == n);
         return rc;
     }
-    auto it = h->graphs.find(n);
+    auto it = h->graphs.find(graph_key(h, n));
     if (it == h->graphs.end()) {
         hipGraphExec_t exec = nullptr;
         if ((rc = build_graph(h, n, &exec))) {
@@ -825,13 +849,13 @@ int tetsim_step_n(tetsim_handle h, uint32_t n, double dt, const TetSimParams* pa
             if (!rc) rc = flush_v(h);
             return rc;
         }
-        it = h->graphs.emplace(n, exec).first;
+        it = h->graphs.emplace(graph_key(h, n), exec).first;
     }
     // (... and so do the calls that run as ONE launch of stamped hand-overs -- pjb_call_kernel, nh_sweep1 / nh_call_kernel: their waiting
     // workgroups hold slots too.  Beside a body whose persistent launch needs most of the device resident AT ONCE the two deadlock until a
     // wait gives up: the frame kernel's resident tiles fill an XCD waiting for tiles that find no slot, the call kernel's workgroups fill the
     // rest waiting for a workgroup that is next in line on THAT XCD -- tools/soak.py, round 6.  Nothing is paid without such a body.)
-    if (h->nh_one_launch)
+    if (nh_one_now(h))
         return launch_in_turn(h, [&]() -> int { HIPCHK(h, hipGraphLaunch(it->second, h->stream)); return 0; });
     HIPCHK(h, hipGraphLaunch(it->second, h->stream));
     return 0;

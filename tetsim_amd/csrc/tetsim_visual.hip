@@ -253,6 +253,7 @@ int tetsim_set_colliders(tetsim_handle h, const TetSimCollider* colliders, uint3
     if (!h) return TETSIM_EINVAL;
     if (count > TETSIM_MAX_COLLIDERS) return fail(h, TETSIM_EINVAL, "more than TETSIM_MAX_COLLIDERS colliders");
     if (count && !colliders) return fail(h, TETSIM_EINVAL, "colliders is null");
+    if (count && h->body_colliders_on) return fail(h, TETSIM_ESTATE, kBodyCollidersOn);   // (clearing the handle's list, count 0, stays legal)
     DevColliderD d[kMaxColliders] = {};
     DevColliderF f[kMaxColliders] = {};
     for (uint32_t k = 0; k < count; k++) {

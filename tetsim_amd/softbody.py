@@ -62,6 +62,26 @@ def make_colliders(colliders):
     return arr
 
 
+def body_collider_rows(lists, per_body=None):
+    """A list per body of the dicts make_colliders takes -> float32 [bodies, per_body, 24], the rows of setBodyColliders /
+    setBodyCollidersDevice (include/tetsim.h: TETSIM_BODY_COLLIDER_FLOATS -- kind as a value, a, b, axes, radius, friction, velocity,
+    three unread floats).  per_body: slots per body, 1 .. 8 (None = the longest list, at least 1); a body's unused slots are empty
+    rows (kind -1).  torch.from_numpy(rows).to(device) is the tensor setBodyCollidersDevice reads."""
+    lists = [list(cs) for cs in lists]
+    longest = max([len(cs) for cs in lists] + [1])
+    per_body = longest if per_body is None else int(per_body)
+    if not 1 <= per_body <= capi.MAX_COLLIDERS or longest > per_body:
+        raise ValueError("per_body must be 1 .. %d and hold the longest list (%d)" % (capi.MAX_COLLIDERS, longest))
+    rows = np.zeros((len(lists), per_body, capi.BODY_COLLIDER_FLOATS), dtype=np.float32)
+    rows[:, :, 0] = -1.0
+    for b, cs in enumerate(lists):
+        for k, c in enumerate(make_colliders(cs)[:len(cs)]):
+            if c.reserved != 0:
+                raise ValueError("body %d, slot %d: a row has no `reserved` field" % (b, k))
+            rows[b, k, :21] = [c.kind] + list(c.a) + list(c.b) + list(c.axes) + [c.radius, c.friction] + list(c.velocity)
+    return rows
+
+
 # tetsim_raycast_visual's records as numpy sees them (include/tetsim.h: TetSimRay, TetSimRayHit)
 RAY_DTYPE = np.dtype([("origin", "<f8", (3,)), ("direction", "<f8", (3,)), ("near", "<f8"), ("far", "<f8")])
 RAY_HIT_DTYPE = np.dtype([("hit", "<i4"), ("body", "<i4"), ("triangle", "<i4"), ("reserved", "<i4"), ("distance", "<f8"), ("point", "<f8", (3,))])
@@ -858,6 +878,43 @@ class SoftBodyHIP:
         _check_rows(torch, targets, dev, n, 3, "targets")
         ptr, keep = self._body_mask(torch, dev, bodies)
         capi.check(self._L.tetsim_set_body_grabs_device(self._h, particles.data_ptr(), targets.data_ptr(), 4 * targets.stride(0) if n > 1 else 0, ptr, s), self._h)
+        self._mask_keep = keep   # (a converted host sequence lives until the next call: the kernel may not have read it yet)
+
+    # -- body colliders (include/tetsim.h: tetsim_set_body_colliders / _device) ---------------------------------------------
+    def setBodyColliders(self, lists_or_rows):
+        """Give every body its own obstacles: a list per body of the dicts setColliders takes (at most 8 each), or the float32
+        [num_bodies, per_body, 24] rows body_collider_rows makes of them.  Body b then steps exactly as it would alone with
+        setColliders of its rows, bit for bit.  None switches body colliders off.  Raises TetSimError(EINVAL) for a row setColliders
+        would refuse (the previous table stays in force), TetSimError(ESTATE) while the handle's own list is set."""
+        if lists_or_rows is None:
+            capi.check(self._L.tetsim_set_body_colliders(self._h, None, 0), self._h)
+            return
+        n = self.info.num_bodies
+        rows = lists_or_rows if isinstance(lists_or_rows, np.ndarray) else body_collider_rows(lists_or_rows)
+        rows = _f32(rows)
+        if rows.ndim != 3 or rows.shape[0] != n or rows.shape[2] != capi.BODY_COLLIDER_FLOATS:
+            raise ValueError("rows must be [%d, per_body, %d]" % (n, capi.BODY_COLLIDER_FLOATS))
+        capi.check(self._L.tetsim_set_body_colliders(self._h, _fp(rows.reshape(-1)), rows.shape[1]), self._h)
+
+    def setBodyCollidersDevice(self, rows, bodies=None, stream=None):
+        """setBodyColliders from a device tensor, with no host copy and no synchronisation: rows torch.float32 [num_bodies, per_body, w]
+        with w >= 24 and a contiguous last dimension, the rows evenly spaced in memory (a [..., :24] view of a wider tensor is fine:
+        nothing outside a row's 24 floats is read), on the handle's device and produced on `stream` (as in exportTensors; reusable on
+        it right after the call).  bodies: a mask as in setBodyGrabsDevice -- a body it leaves out keeps its whole list.  A row the
+        table cannot hold (what setColliders would refuse) is an empty slot for that body and disturbs no other row."""
+        import torch
+        dev, s = self._torch_stream(torch, stream)
+        n, w = self.info.num_bodies, capi.BODY_COLLIDER_FLOATS
+        ok = (isinstance(rows, torch.Tensor) and rows.dtype == torch.float32 and rows.device == dev and rows.dim() == 3 and rows.shape[0] == n
+              and 1 <= rows.shape[1] and rows.shape[2] >= w and rows.stride(2) == 1)
+        if ok:
+            per_body = int(rows.shape[1])
+            step = rows.stride(1) if per_body > 1 else (rows.stride(0) if n > 1 else w)
+            ok = step >= w and (n == 1 or per_body == 1 or rows.stride(0) == per_body * step)
+        if not ok:
+            raise ValueError("rows must be a float32 tensor on %s of shape (%d, per_body, >= %d) with a contiguous last dimension and evenly spaced rows" % (dev, n, w))
+        ptr, keep = self._body_mask(torch, dev, bodies)
+        capi.check(self._L.tetsim_set_body_colliders_device(self._h, rows.data_ptr(), 4 * step if n * per_body > 1 else 0, per_body, ptr, s), self._h)
         self._mask_keep = keep   # (a converted host sequence lives until the next call: the kernel may not have read it yet)
 
     def nearestParticlesDevice(self, points, out_ids=None, out_dist2=None, stream=None):
