@@ -214,7 +214,7 @@ int tetsim_create(const float *verts, uint32_t nv, const int32_t *tets, uint32_t
  * (verts[b], nv[b], tets[b], nt[b]); the handle's particles / tets are their concatenation (tetsim_get_batch_layout gives the
  * ranges) and every other entry point works on that concatenation -- one tetsim_step_n steps all bodies with ONE launch per
  * kernel: a Dragon-sized body alone fills 15 of the chip's 2,048 workgroup slots, sixty-four of them 960.  All bodies share
- * physicsParams; tetsim_set_grab addresses a particle of the concatenation.  Each body's results equal its solo run BIT FOR BIT
+ * physicsParams (unless tetsim_set_body_params gives each its own); tetsim_set_grab addresses a particle of the concatenation.  Each body's results equal its solo run BIT FOR BIT
  * (both solvers, both precisions): tiles never span two bodies and are cut per body exactly as for a body alone, the
  * reference's slot-table quirk applies to every body's own first tet, Gauss-Seidel schedules of disjoint bodies are independent
  * (tetsim_get_tet_order then refers to the concatenation).  Unpartitioned only. */
@@ -570,7 +570,7 @@ int tetsim_nearest_particles_device(tetsim_handle h, const void *points, uint64_
  * the list's own cost); one Dragon of quad tiles x1.76 and 64 small lattices of quad tiles x1.99 against the list (two launches per
  * substep); 64 Dragons Neo-Hookean FAST x207 (2.49 s against 12 ms: 43,520 level launches in place of one workgroup per body -- a
  * batch of small Neo-Hookean bodies pays dearly for the table); the set kernel takes 37 us for 64 bodies and 45 us for 4,096.
- * Out of scope: per-body physicsParams; more than eight colliders per body; f64 rows; colliders
+ * Out of scope: more than eight colliders per body; f64 rows; colliders
  * between bodies; partitioned bodies; contact read-back; a Node binding. */
 #define TETSIM_BODY_COLLIDER_FLOATS 24
 /* rows: num_bodies * per_body rows of 24 f32, body-major (row of body b, slot k at index b * per_body + k), packed.
@@ -580,6 +580,59 @@ int tetsim_set_body_colliders(tetsim_handle h, const float *rows, uint32_t per_b
  * body_mask as for tetsim_set_body_grabs_device (num_bodies bytes, nonzero = take this body's rows; NULL = all). */
 int tetsim_set_body_colliders_device(tetsim_handle h, const void *rows, uint64_t row_stride, uint32_t per_body,
                                      const void *body_mask, void *caller_stream);
+
+/* --- body parameters: physics parameters per body of a batch, settable from device memory ------- */
+
+/* Everything else that differs between the bodies of a batch already lives in per-body tables in device memory (grabs, colliders, poses,
+ * resets); this table does the same for physicsParams: a stiff and a soft body, a slippery and a sticky floor, low gravity or another
+ * arena for one environment, in ONE handle.  An ADDITIVE extension of ABI version 5 (TETSIM_ABI_VERSION is unchanged; no existing
+ * struct changed): look the symbols up.
+ *
+ * A row is TETSIM_BODY_PARAMS_WIDTH f64, exactly a TetSimParams (sizeof == 80): gravity, friction, devCompliance, volCompliance,
+ * worldBounds lo xyz, hi xyz.  f64 because PRECISE NEOHOOKEAN_GS reads the parameters as f64; the f32 view POLAR_JACOBI and FAST
+ * NEOHOOKEAN_GS read is rounded once from the row, by the casts a call's TetSimParams goes through.
+ *
+ * THE CONTRACT.  While body parameters are ON, every substep of body b reads gravity, friction, devCompliance, volCompliance and
+ * worldBounds from b's row.  The `params` argument of tetsim_step, tetsim_step_n and tetsim_profile must still be non-NULL; its values
+ * are not looked at (as the handle's grab names nobody while body grabs are on).  dt stays the call's, for every body.  A
+ * POLAR_JACOBI handle created with TETSIM_FLAG_REF_FIXED_BOUNDS keeps the reference's constant box for every body.  Body b gives the
+ * bits it gives alone with those TetSimParams: both solvers, both precisions, every order, every stepping path, tetsim_step and
+ * tetsim_step_n, with or without the handle's grab, body grabs, the handle's collider list and body colliders.  A handle that never
+ * switches body parameters on executes what it always executed plus uniform branches on ONE flag (DevParams::body_params).
+ *
+ * Which kernel takes the table, per stepping path (TetSimInfo.fused_particle_pass): 0 POLAR_JACOBI gather / PRECISE -- pj_vertex_kernel,
+ * per lane; 0 NEOHOOKEAN_GS levels, colours, clusters -- the level, cluster and particle kernels, per lane (tets through a tet -> body
+ * array), and the one-launch clustered FAST sweeps nh_sweep1_kernel and nh_call_kernel likewise; 1 and 2 -- pjb_vertex_kernel per lane,
+ * the fused tile kernel per tile (scalar loads); 3 -- pjq_frame_kernel and its two-launch twin, per tile (scalar loads); 2 / 3 with the
+ * persistent pjb_frame_kernel -- per tile (scalar loads); 4 -- nh_frame_kernel, one workgroup per body (scalar loads); 5 --
+ * pjb_call_kernel: tiles per tile, particle blocks per lane.  No path falls back to
+ * other kernels while the table is on.
+ *
+ * The table lives in device memory owned by the handle, in the view its arithmetic reads (f32 or f64), with -- NEOHOOKEAN_GS -- the body
+ * of every tet in the device's tet order; it counts into device_bytes.  The first set call allocates it with every body at
+ * tetsim_default_params(); only that call may block.  A set call runs one small kernel, a lane per body, on the handle's stream, behind
+ * every substep enqueued so far.  tetsim_set_body_params_device follows the stream contract of tetsim_import_device: no host read of
+ * the rows, no host synchronisation.  A body the mask leaves out keeps its row.  Switching OFF (rows == NULL) is host state; the rows
+ * stay.  The table is not solver state: checkpoints and snapshots do not hold it, and their sizes do not change.
+ *
+ * Rows the host cannot see: a row with a non-finite value in any of its ten doubles leaves its body's previous row in place and
+ * disturbs no other body.  The host variant refuses such a row with TETSIM_EINVAL, names the body in tetsim_last_error and changes
+ * nothing.  TETSIM_EINVAL also: a NULL handle; a stride that is neither 0 nor a multiple of 8 of at least 80; a pointer that is not
+ * 8-byte aligned, not on the handle's device, or whose rows do not fit the allocation it points into; a mask with any of these faults.
+ * TETSIM_ESTATE: any partitioned body.  Every error is found before anything is enqueued.
+ * Cost, measured on an MI355X (tools/body_params_cost.py, profiles/body_params_cost.txt): never switched on, the benchmark
+ * line is not below the parent's run-to-run range (medians 32,578.3 parent, 32,623.3 this change); switched on, 64 Dragons in one batch,
+ * one call of 20 substeps: polar FAST x1.00, Neo-Hookean FAST x1.00 against the table off; the set kernel takes 32 us for 64 or 4,096 bodies.
+ * Out of scope: per-body dt or density; a gravity vector; per-tet or per-particle material; partitioned bodies; a Node binding;
+ * gradients. */
+#define TETSIM_BODY_PARAMS_WIDTH 10   /* doubles per body row: 80 bytes, the fields of TetSimParams in its order */
+enum { TETSIM_BP_GRAVITY = 0, TETSIM_BP_FRICTION = 1, TETSIM_BP_DEV_COMPLIANCE = 2, TETSIM_BP_VOL_COMPLIANCE = 3,
+       TETSIM_BP_BOUNDS_LO = 4 /*..6*/, TETSIM_BP_BOUNDS_HI = 7 /*..9*/ };
+/* rows: num_bodies rows of 10 f64, packed (an array of TetSimParams); rows == NULL: body parameters OFF */
+int tetsim_set_body_params(tetsim_handle h, const double *rows);
+/* The same from DEVICE memory: row b at rows + b * row_stride (0 = packed 80; else a multiple of 8, >= 80); body_mask as for
+ * tetsim_set_body_grabs_device (num_bodies bytes, nonzero = take this body's row; NULL = all). */
+int tetsim_set_body_params_device(tetsim_handle h, const void *rows, uint64_t row_stride, const void *body_mask, void *caller_stream);
 
 /* --- device-side export and import: results for another GPU program, without a host copy -------- */
 

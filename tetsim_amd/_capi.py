@@ -21,6 +21,8 @@ K_TET, K_VERTEX, K_HALO, K_COUNT = 0, 1, 2, 3
 COLLIDER_SPHERE, COLLIDER_CAPSULE, COLLIDER_BOX, COLLIDER_PLANE = 0, 1, 2, 3
 MAX_COLLIDERS = 8
 BODY_COLLIDER_FLOATS = 24   # TETSIM_BODY_COLLIDER_FLOATS: a row of tetsim_set_body_colliders
+BODY_PARAMS_WIDTH = 10      # TETSIM_BODY_PARAMS_WIDTH: doubles per row of tetsim_set_body_params, the fields of TetSimParams in its order
+BP_GRAVITY, BP_FRICTION, BP_DEV_COMPLIANCE, BP_VOL_COMPLIANCE, BP_BOUNDS_LO, BP_BOUNDS_HI = 0, 1, 2, 3, 4, 7
 FIELD_POSITIONS, FIELD_VELOCITIES, FIELD_PREV_POSITIONS, FIELD_QUATS, FIELD_VISUAL_POSITIONS, FIELD_VISUAL_NORMALS, FIELD_VISUAL_VERTEX_NORMALS = range(7)
 MAX_EXPORT_FIELDS = 8
 # doubles of a body's row of tetsim_observe_bodies_device, and where each quantity starts in it
@@ -152,6 +154,7 @@ SYMBOLS = [
     "tetsim_tet_strain_device", "tetsim_read_tet_strain", "tetsim_body_strain_device", "tetsim_visual_strain_device", "tetsim_prep_strain_table",
     "tetsim_set_body_grabs", "tetsim_set_body_grabs_device", "tetsim_nearest_particles_device",
     "tetsim_set_body_colliders", "tetsim_set_body_colliders_device",
+    "tetsim_set_body_params", "tetsim_set_body_params_device",
     "tetsim_place_bodies_device", "tetsim_place_bodies",
     "tetsim_mesh_write", "tetsim_mesh_open", "tetsim_mesh_arrays", "tetsim_mesh_close", "tetsim_create_from_file",
 ]
@@ -165,6 +168,7 @@ OPTIONAL_SYMBOLS = ("tetsim_set_colliders", "tetsim_raycast_visual", "tetsim_sta
                     "tetsim_tet_strain_device", "tetsim_read_tet_strain", "tetsim_body_strain_device", "tetsim_visual_strain_device", "tetsim_prep_strain_table",
                     "tetsim_set_body_grabs", "tetsim_set_body_grabs_device", "tetsim_nearest_particles_device",
                     "tetsim_set_body_colliders", "tetsim_set_body_colliders_device",
+                    "tetsim_set_body_params", "tetsim_set_body_params_device",
                     "tetsim_place_bodies_device", "tetsim_place_bodies",
                     "tetsim_body_poses_device", "tetsim_read_body_poses", "tetsim_prep_pose_table")
 
@@ -266,6 +270,9 @@ def lib():
     if hasattr(L, "tetsim_set_body_colliders"):   # (additive to ABI 5; device rows, the mask and the stream travel as plain addresses)
         L.tetsim_set_body_colliders.argtypes = [H, fp, u32]
         L.tetsim_set_body_colliders_device.argtypes = [H, C.c_void_p, C.c_uint64, u32, C.c_void_p, C.c_void_p]
+    if hasattr(L, "tetsim_set_body_params"):
+        L.tetsim_set_body_params.argtypes = [H, C.POINTER(C.c_double)]
+        L.tetsim_set_body_params_device.argtypes = [H, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
     if hasattr(L, "tetsim_place_bodies_device"):   # (additive to ABI 5; device rows, the mask and the stream travel as plain addresses)
         L.tetsim_place_bodies_device.argtypes = [H, C.c_void_p, C.c_uint64, C.c_void_p, u32, C.c_void_p]
         L.tetsim_place_bodies.argtypes = [H, fp, C.POINTER(C.c_uint8), u32]

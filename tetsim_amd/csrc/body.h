@@ -17,6 +17,7 @@
 //                      rotation (Horn's quaternion by a fixed Jacobi procedure), angular velocity and momentum
 //   body_grabs.hip     one held particle per body of a batch, set from host or device memory (tetsim_set_body_grabs / _device): the table the
 //                      particle passes read; the nearest particle of every body on the device (tetsim_nearest_particles_device)
+//   body_params.hip   physics parameters per body of a batch, set from host or device memory (tetsim_set_body_params / _device)
 //   body_colliders.hip up to eight kinematic colliders per body of a batch, set from host or device memory (tetsim_set_body_colliders /
 //                      _device): the table collide.h's routines walk in place of the handle's list, one set kernel, a lane per body
 //   place.hip          a rigid motion of chosen bodies' complete state, rows and mask in device memory (tetsim_place_bodies / _device): one
@@ -256,6 +257,14 @@ struct tetsim_body {
     uint32_t* d_bcol_count = nullptr;   // [bodies]
     DevColliderF* d_bcol_f = nullptr;   // [bodies][kMaxColliders]
     DevColliderD* d_bcol_d = nullptr;   // [bodies][kMaxColliders]
+    // body parameters (tetsim_set_body_params / _device, body_params.hip): a row per body -- gravity, friction, the two compliances, the bounds --
+    // in the view this handle's arithmetic reads (the other pointer stays null), and for Neo-Hookean handles the body of every tet in the
+    // device's tet order.  Made by the first set call, every body at tetsim_default_params(); ON / OFF is host state and travels as
+    // DevParams::body_params.  Not solver state either.
+    bool body_params_on = false;
+    BodyParamsF* d_bp_f = nullptr;      // [bodies]
+    BodyParamsD* d_bp_d = nullptr;      // [bodies]
+    uint32_t* d_tet_body = nullptr;     // [tets] Neo-Hookean only
     uint32_t* d_body_first = nullptr;   // [bodies + 1] first particle of every body in the CALLER's numbering (also tetsim_nearest_particles_device)
     // tetsim_nearest_particles_device: a candidate per chunk of the particle chunk table (below)
     double* d_near_d2 = nullptr;

@@ -23,6 +23,15 @@ struct DevColliderD {
     int32_t kind, pad;
 };
 
+// A body's row of physics parameters (tetsim_set_body_params; body_params.hip) in the two views: f64 is the caller's row, f32 every value
+// rounded once from it -- the casts fill_params makes (lo / hi: the reference's constant box for a POLAR_JACOBI handle created with
+// TETSIM_FLAG_REF_FIXED_BOUNDS).
+__host__ __device__ inline float ref_fixed_lo(int c) { return c == 1 ? -1.0f : -2.5f; }   // that box, SoftbodyGPU.js:347: the one place it is written down
+__host__ __device__ inline float ref_fixed_hi(int c) { return c == 1 ? 10.0f : 2.5f; }
+struct BodyParamsF { float gravity, friction, dev_compliance, vol_compliance, lo[3], hi[3], pad[2]; };   // 48 bytes: three 16-byte loads
+struct BodyParamsD { double gravity, friction, dev_compliance, vol_compliance, lo[3], hi[3]; };          // = TetSimParams
+static_assert(sizeof(BodyParamsF) == 48 && sizeof(BodyParamsD) == 80, "body parameter rows");
+
 // Per-step dynamic parameters, resident in device memory so that captured HIP graphs stay valid when
 // the caller changes dt / physicsParams / grab between frames (kernels read it with scalar loads).
 struct DevParams {
@@ -31,7 +40,8 @@ struct DevParams {
     uint32_t body_grabs;   // non-zero: the body-grab table below decides which particles are held, grab / grab_local are not looked at (tetsim_set_body_grabs)
     float lo[3];
     uint32_t body_colliders;   // non-zero: a particle meets the rows of ITS body in the table below (tetsim_set_body_colliders); n_colliders is 0 then
-    float hi[3], pad2;
+    float hi[3];
+    uint32_t body_params;   // non-zero: gravity, friction, the compliances and the bounds of a body come from ITS row of the table below (tetsim_set_body_params); the fields here are not looked at
     float grab[3];
     int32_t grab_local;  // local vertex index, -1 = none
     int32_t grab_local2; // second pinned particle (TETSIM_FLAG_REF_GRAB_TEXEL can select two), -1 = none
@@ -51,6 +61,12 @@ struct DevParams {
     const uint32_t* bcol_count;
     const DevColliderF* bcol_f;
     const DevColliderD* bcol_d;
+    // body parameters (body_params.hip): a row per body in the view this handle's arithmetic reads (the other pointer stays null), indexed
+    // through grab_body in the particle passes and through tet_body -- the body of every tet in the device's tet order, Neo-Hookean only --
+    // in the tet solves.  Null until the handle's first set call; the addresses never change.
+    const BodyParamsF* bp_f;
+    const BodyParamsD* bp_d;
+    const uint32_t* tet_body;
     // kinematic colliders (collide.h): entries [0, n_colliders) are meaningful, in both views.  Behind every field above, so that a
     // body without colliders reads what it always read at the offsets it always read it from.
     DevColliderF col[kMaxColliders];     // f32 view: polar solver, FAST Neo-Hookean
@@ -97,6 +113,30 @@ __device__ __forceinline__ void body_colliders_pick(const DevParams& P, uint32_t
 __device__ __forceinline__ void body_colliders_pick(const DevParams& P, uint32_t body, const DevColliderD** list, uint32_t* count) {
     *list = P.d_col; *count = P.n_colliders;
     if (P.body_colliders) { *list = P.bcol_d + static_cast<size_t>(body) * kMaxColliders; *count = P.bcol_count[body]; }
+}
+
+// Body parameters (tetsim_set_body_params): the row of `body` in the view the caller's arithmetic reads (picked by the type of the third
+// argument).  Only an address, and only to be called behind the uniform test of DevParams::body_params: a handle that never switches the
+// table on executes what it always executed plus that branch.  With a UNIFORM body index (body_params_uniform: the tile kernels, whose
+// tiles hold one body; one workgroup per body) the row arrives through scalar loads and its values sit where the kernel arguments sat;
+// where a wave spans bodies the index is the lane's own (grab_body[v], tet_body[e]) and the row's values are vector registers.
+__device__ __forceinline__ const BodyParamsF* body_params_row(const DevParams& P, uint32_t body, float) { return P.bp_f + body; }
+__device__ __forceinline__ const BodyParamsD* body_params_row(const DevParams& P, uint32_t body, double) { return P.bp_d + body; }
+__device__ __forceinline__ uint32_t body_params_uniform(uint32_t body) { return static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int32_t>(body))); }
+// ... and the four values of a polar particle pass: the call's, or -- behind that one branch -- those of the body of particle v (device
+// index; the tile kernels' idle lanes carry a valid id too).  kUniform: every lane of the wave holds a particle of ONE body.
+struct PolarBodyParams { float gravity, friction, lo[3], hi[3]; };
+template <bool kUniform>
+__device__ __forceinline__ PolarBodyParams body_params_polar(const DevParams& P, uint32_t v) {
+    PolarBodyParams o = {P.gravity, P.friction, {P.lo[0], P.lo[1], P.lo[2]}, {P.hi[0], P.hi[1], P.hi[2]}};
+    if (P.body_params) {
+        uint32_t body = P.grab_body[v];
+        if constexpr (kUniform) body = body_params_uniform(body);
+        const BodyParamsF* const r = body_params_row(P, body, 0.0f);
+        o.gravity = r->gravity; o.friction = r->friction;
+        for (int k = 0; k < 3; k++) { o.lo[k] = r->lo[k]; o.hi[k] = r->hi[k]; }
+    }
+    return o;
 }
 
 // ---- POLAR_JACOBI device state (all arrays 16-byte elements: one dwordx4 per lane) ----------------

@@ -156,6 +156,23 @@ __device__ __forceinline__ T solve_elem(g3 p[4], const float im[4], const float 
     return vol - static_cast<T>(1.0);
 }
 
+// Body parameters in a tet solve (tetsim_set_body_params): behind ONE uniform branch the two compliances come from the row of the body of
+// tet e (solve position; DevParams::tet_body), in this unit's arithmetic -- only where the values come from, the solve's text is untouched.
+__device__ __forceinline__ void body_compliances(const DevParams& P, uint32_t e, T& devC, T& volC) {
+    if (P.body_params) {
+        const auto* const r = body_params_row(P, P.tet_body[e], T());
+        devC = r->dev_compliance; volC = r->vol_compliance;
+    }
+}
+__device__ __forceinline__ uint32_t cluster_body(const DevParams& P, uint32_t e) { return P.body_params ? P.tet_body[e] : 0u; }   // e: any tet of the cluster
+// ... with the body index at hand (one workgroup per body: uniform, scalar loads)
+__device__ __forceinline__ void body_compliances_of(const DevParams& P, uint32_t body, T& devC, T& volC) {
+    if (P.body_params) {
+        const auto* const r = body_params_row(P, body, T());
+        devC = r->dev_compliance; volC = r->vol_compliance;
+    }
+}
+
 // One dependency level: lanes [first, first+count) of the solve order.
 template <bool kWriteThrough>
 __global__ __launch_bounds__(256) void TETSIM_SFX(nh_level_kernel_)(NHDev d, uint32_t first, uint32_t count) {
@@ -164,10 +181,13 @@ __global__ __launch_bounds__(256) void TETSIM_SFX(nh_level_kernel_)(NHDev d, uin
     const uint32_t e = first + i;
     const DevParams& P = *d.params;
 #if TETSIM_FAST
-    const T dt = P.dt, devC = static_cast<T>(P.d_dev_compliance), volC = static_cast<T>(P.d_vol_compliance);
+    const T dt = P.dt;
+    T devC = static_cast<T>(P.d_dev_compliance), volC = static_cast<T>(P.d_vol_compliance);
 #else
-    const T dt = P.d_dt, devC = P.d_dev_compliance, volC = P.d_vol_compliance;
+    const T dt = P.d_dt;
+    T devC = P.d_dev_compliance, volC = P.d_vol_compliance;
 #endif
+    body_compliances(P, e, devC, volC);
     const int4 id = d.tet_idx[e];
     const float4 ia = d.irp_a[e], ib = d.irp_b[e], ic = d.irp_c[e];
     const float ir[9] = {ia.x, ia.y, ia.z, ia.w, ib.x, ib.y, ib.z, ib.w, ic.x};
@@ -218,6 +238,20 @@ __device__ __forceinline__ VParams load_vparams(const DevParams& P) {
     q.all = &P;
     return q;
 }
+// ... for a particle of `body`: with body parameters on (tetsim_set_body_params), behind one uniform branch, gravity, friction and the
+// bounds are those of the body's row
+__device__ __forceinline__ VParams load_vparams_of(const DevParams& P, uint32_t body) {
+    VParams q = load_vparams(P);
+    if (P.body_params) {
+        const auto* const r = body_params_row(P, body, T());
+        q.gravity = r->gravity; q.friction = r->friction;
+#pragma unroll
+        for (int k = 0; k < 3; k++) { q.lo[k] = r->lo[k]; q.hi[k] = r->hi[k]; }
+    }
+    return q;
+}
+// ... for particle v (device index), whose body the particle -> body array names: a lane of its own, a wave that spans bodies
+__device__ __forceinline__ VParams load_vparams(const DevParams& P, uint32_t v) { return load_vparams_of(P, P.body_params ? P.grab_body[v] : 0u); }
 
 // XPBD prediction, Softbody.js:198-202: vel and pos in, (vel, prev, pos) out
 __device__ __forceinline__ void predict_vertex(const VParams& P, float4& vel, float4& pos, float4& prev) {
@@ -236,7 +270,7 @@ __global__ __launch_bounds__(256) void TETSIM_SFX(nh_predict_kernel_)(NHDev d) {
     const uint32_t v = blockIdx.x * 256u + threadIdx.x;
     if (v >= d.nv) return;
     float4 vel = d.vel[v], pos = d.pos[v], prev;
-    predict_vertex(load_vparams(*d.params), vel, pos, prev);
+    predict_vertex(load_vparams(*d.params, v), vel, pos, prev);
     d.vel[v] = vel;
     d.prev[v] = prev;
     d.pos[v] = pos;
@@ -248,7 +282,7 @@ __global__ __launch_bounds__(256) void TETSIM_SFX(nh_predict_value_kernel_)(NHDe
     const uint32_t v = blockIdx.x * 256u + threadIdx.x;
     if (v >= d.nv) return;
     float4 vel = d.vel[v], pos = d.pos[v], prev;
-    predict_vertex(load_vparams(pv), vel, pos, prev);
+    predict_vertex(load_vparams(pv, v), vel, pos, prev);
     // nh_call_kernel polls prev.w for its own fold's stamp of one substep before, and may look before that store has landed: it then
     // finds this value.  `prev = pos` carries the inverse mass, any non-negative float -- one whose bits equal the awaited stamp was
     // taken for the fold's store (a velocity from the wrong previous position).  0 is no stamp (tetsim_api.hip: next_epoch_block);
@@ -336,7 +370,7 @@ __global__ __launch_bounds__(256) void TETSIM_SFX(nh_post_kernel_)(NHDev d) {
     const uint32_t v = blockIdx.x * 256u + threadIdx.x;
     if (v >= d.nv) return;
     float4 pos = d.pos[v], vel;
-    post_vertex(load_vparams(*d.params), v, pos, d.prev[v], vel);
+    post_vertex(load_vparams(*d.params, v), v, pos, d.prev[v], vel);
     d.pos[v] = pos;
     d.vel[v] = vel;
 }
@@ -345,7 +379,7 @@ __global__ __launch_bounds__(256) void TETSIM_SFX(nh_post_predict_kernel_)(NHDev
     const uint32_t v = blockIdx.x * 256u + threadIdx.x;
     if (v >= d.nv) return;
     float4 pos = d.pos[v], vel, prev;
-    const VParams q = load_vparams(*d.params);
+    const VParams q = load_vparams(*d.params, v);
     post_vertex(q, v, pos, d.prev[v], vel);
     predict_vertex(q, vel, pos, prev);
     store_wt(d.vel, v, vel);
@@ -358,7 +392,7 @@ __global__ __launch_bounds__(256) void TETSIM_SFX(nh_post_predict_list_kernel_)(
     if (i >= n) return;
     const uint32_t v = list[i];
     float4 pos = d.pos[v], vel, prev;
-    const VParams q = load_vparams(*d.params);
+    const VParams q = load_vparams(*d.params, v);
     post_vertex(q, v, pos, d.prev[v], vel);
     predict_vertex(q, vel, pos, prev);
     store_wt(d.vel, v, vel);
@@ -390,10 +424,13 @@ __global__ __launch_bounds__(64) void TETSIM_SFX(nh_cluster_kernel_)(NHDev d, NH
     if (i >= L.clusters) return;
     const DevParams& P = *d.params;
 #if TETSIM_FAST
-    const T dt = P.dt, devC = static_cast<T>(P.d_dev_compliance), volC = static_cast<T>(P.d_vol_compliance);
+    const T dt = P.dt;
+    T devC = static_cast<T>(P.d_dev_compliance), volC = static_cast<T>(P.d_vol_compliance);
 #else
-    const T dt = P.d_dt, devC = P.d_dev_compliance, volC = P.d_vol_compliance;
+    const T dt = P.d_dt;
+    T devC = P.d_dev_compliance, volC = P.d_vol_compliance;
 #endif
+    body_compliances(P, L.first[0] + i, devC, volC);   // (a cluster's tets and particles are one body's: its first tet names it)
     int32_t vid[kNHClusterVerts];
 #pragma unroll
     for (uint32_t k = 0; k < kNHClusterVerts; k++) vid[k] = L.slot_vid[static_cast<size_t>(k) * L.clusters + i];
@@ -415,7 +452,7 @@ __global__ __launch_bounds__(64) void TETSIM_SFX(nh_cluster_kernel_)(NHDev d, NH
         float4 before[kNHClusterVerts];
 #pragma unroll
         for (uint32_t k = 0; k < kNHClusterVerts; k++) before[k] = d.prev[vid[k] < 0 ? 0 : vid[k]];
-        const VParams q = load_vparams(P);
+        const VParams q = load_vparams_of(P, cluster_body(P, L.first[0] + i));   // (only FAST handles fold -- tetsim_create.hip: nh_fold -- the PRECISE fold variants are never launched)
 #pragma unroll
         for (uint32_t k = 0; k < kNHClusterVerts; k++)
             if ((mask >> k) & 1u) fold_particle(d, q, static_cast<uint32_t>(vid[k]), gathered[k], before[k]);
@@ -650,12 +687,15 @@ __global__ __launch_bounds__(512) void TETSIM_SFX(nh_frame_kernel_)(NHDev d, con
     const uint32_t tid = threadIdx.x, nthr = blockDim.x, c = tid & 3u, qd = tid >> 2, nq = nthr >> 2;
     const DevParams& P = pv;
 #if TETSIM_FAST
-    const T dt = P.dt, devC = static_cast<T>(P.d_dev_compliance), volC = static_cast<T>(P.d_vol_compliance);
+    const T dt = P.dt;
+    T devC = static_cast<T>(P.d_dev_compliance), volC = static_cast<T>(P.d_vol_compliance);
 #else
-    const T dt = P.d_dt, devC = P.d_dev_compliance, volC = P.d_vol_compliance;
+    const T dt = P.d_dt;
+    T devC = P.d_dev_compliance, volC = P.d_vol_compliance;
 #endif
+    body_compliances_of(P, body, devC, volC);   // (one workgroup per body: the row arrives through scalar loads)
     const T a_dev = devC / dt / dt, a_vol = volC / dt / dt, c_off = volC / devC;   // (left to right, as `devC / dt / dt * irv` evaluates)
-    const VParams q = load_vparams(P);
+    const VParams q = load_vparams_of(P, body);
     for (uint32_t v = tid; v < nvb; v += nthr) {   // the call starts with a prediction (Softbody.js:198-202), as enqueue_substep(first) does
         float4 pos = d.pos[vbase + v], vel = d.vel[vbase + v], prev;
         predict_vertex(q, vel, pos, prev);
@@ -750,10 +790,13 @@ __global__ __launch_bounds__(256) void TETSIM_SFX(nh_level4_kernel_)(NHDev d, ui
     if (i >= count) return;   // (whole quads)
     const DevParams& P = *d.params;
 #if TETSIM_FAST
-    const T dt = P.dt, devC = static_cast<T>(P.d_dev_compliance), volC = static_cast<T>(P.d_vol_compliance);
+    const T dt = P.dt;
+    T devC = static_cast<T>(P.d_dev_compliance), volC = static_cast<T>(P.d_vol_compliance);
 #else
-    const T dt = P.d_dt, devC = P.d_dev_compliance, volC = P.d_vol_compliance;
+    const T dt = P.d_dt;
+    T devC = P.d_dev_compliance, volC = P.d_vol_compliance;
 #endif
+    body_compliances(P, first + i, devC, volC);
     const T a_dev = devC / dt / dt, a_vol = volC / dt / dt, c_off = volC / devC;
     const uint32_t e = first + i;
     const T ve = nh_solve_record_quad(reinterpret_cast<float*>(d.pos), nh_load_record(d, e), c, a_dev, a_vol, c_off);
@@ -774,10 +817,13 @@ __global__ __launch_bounds__(256) void TETSIM_SFX(nh_cluster4_kernel_)(const int
     if (i >= a_clusters) return;   // (whole quads leave: the DPP moves stay inside a quad)
     const DevParams& P = *d.params;
 #if TETSIM_FAST
-    const T dt = P.dt, devC = static_cast<T>(P.d_dev_compliance), volC = static_cast<T>(P.d_vol_compliance);
+    const T dt = P.dt;
+    T devC = static_cast<T>(P.d_dev_compliance), volC = static_cast<T>(P.d_vol_compliance);
 #else
-    const T dt = P.d_dt, devC = P.d_dev_compliance, volC = P.d_vol_compliance;
+    const T dt = P.d_dt;
+    T devC = P.d_dev_compliance, volC = P.d_vol_compliance;
 #endif
+    body_compliances(P, L.first[0] + i, devC, volC);   // (the cluster's body, as in nh_cluster_kernel)
     const T a_dev = devC / dt / dt, a_vol = volC / dt / dt, c_off = volC / devC;
     // the cluster's <= 8 particles: lane c fetches slots c and c + 4 (unconditionally, see nh_cluster_kernel) and writes them back
     const int32_t va = a_slot_vid[static_cast<size_t>(c) * a_clusters + i], vb = a_slot_vid[static_cast<size_t>(c + 4u) * a_clusters + i];
@@ -813,7 +859,7 @@ __global__ __launch_bounds__(256) void TETSIM_SFX(nh_cluster4_kernel_)(const int
         // the lane that loads a particle the cluster touches first finishes the previous substep and predicts this one for it (whole
         // particles, two per lane: the per-coordinate split starts behind this)
         if (fmask & (0x11u << c)) {
-            const VParams q = load_vparams(P);
+            const VParams q = load_vparams_of(P, cluster_body(P, L.first[0] + i));
             if ((fmask >> c) & 1u) fold_particle(d, q, static_cast<uint32_t>(va), ga, pa);
             if ((fmask >> (c + 4u)) & 1u) fold_particle(d, q, static_cast<uint32_t>(vb), gb, pb);
         }
@@ -863,7 +909,9 @@ __global__ __launch_bounds__(256) void nh_sweep1_kernel(const NHSweepColour* __r
     const uint32_t clusters = L.clusters;
     if (i >= clusters) return;   // (whole quads leave)
     const DevParams& P = *d.params;
-    const T dt = P.dt, devC = static_cast<T>(P.d_dev_compliance), volC = static_cast<T>(P.d_vol_compliance);
+    const T dt = P.dt;
+    T devC = static_cast<T>(P.d_dev_compliance), volC = static_cast<T>(P.d_vol_compliance);
+    body_compliances(P, L.first[0] + i, devC, volC);
     const T a_dev = devC / dt / dt, a_vol = volC / dt / dt, c_off = volC / devC;
     const uint32_t stamp = (epoch_arg ? epoch_arg : P.epoch) + sub_index * ncol + k + 1u;
     const int32_t va = L.slot_vid[static_cast<size_t>(c) * clusters + i], vb = L.slot_vid[static_cast<size_t>(c + 4u) * clusters + i];
@@ -919,7 +967,7 @@ __global__ __launch_bounds__(256) void nh_sweep1_kernel(const NHSweepColour* __r
     }
     if constexpr (kFold) {
         if (fmask & (0x11u << c)) {
-            const VParams q = load_vparams(P);
+            const VParams q = load_vparams_of(P, cluster_body(P, L.first[0] + i));
             if ((fmask >> c) & 1u) fold_particle<false>(d, q, ua, ga, pa);
             if ((fmask >> (c + 4u)) & 1u) fold_particle<false>(d, q, ub, gb, pb);
         }
@@ -975,7 +1023,9 @@ __global__ __launch_bounds__(256) void nh_call_kernel(const NHSweepColour* __res
     const uint32_t clusters = L.clusters;
     if (i >= clusters) return;   // (whole quads leave)
     const DevParams& P = *d.params;
-    const T dt = P.dt, devC = static_cast<T>(P.d_dev_compliance), volC = static_cast<T>(P.d_vol_compliance);
+    const T dt = P.dt;
+    T devC = static_cast<T>(P.d_dev_compliance), volC = static_cast<T>(P.d_vol_compliance);
+    body_compliances(P, L.first[0] + i, devC, volC);
     const T a_dev = devC / dt / dt, a_vol = volC / dt / dt, c_off = volC / devC;
     const uint32_t sub_base = P.epoch + sub * ncol, stamp = sub_base + k + 1u;
     const bool last_sub = sub + 1u == n_sub;
@@ -1036,7 +1086,7 @@ __global__ __launch_bounds__(256) void nh_call_kernel(const NHSweepColour* __res
     // solves of colour 0 started ~1 us late (tools/nh_link_trace.py)
     float4 keep_a = pa, keep_b = pb;
     if (fold_a || fold_b) {
-        const VParams q = load_vparams(P);
+        const VParams q = load_vparams_of(P, cluster_body(P, L.first[0] + i));
         auto fold = [&](uint32_t v, float4& pos, const float4& prev_in, float4& prev) {
             float4 vel;
             post_vertex<false>(q, v, pos, prev_in, vel);

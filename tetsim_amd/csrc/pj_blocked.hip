@@ -70,6 +70,10 @@ struct VertexOut { f3 p, vel, pred; };
 // (Every multiply-add below is spelled out: with -ffp-contract=fast the compiler decides per call site which products to fuse, and this
 // function is inlined into several kernels whose results must agree bit for bit -- a fourth call site (profiles/archive/r03_tile_finish.txt)
 // came out an ulp off.  The spelling is the one the particle kernel has always compiled to.)
+// kUniformBody: every lane of the wave carries a particle of ONE body (a tile's own particles) -- a body's row of parameters
+// (tetsim_set_body_params) then arrives through scalar loads; the particle kernels' waves span bodies and load per lane.
+// kTable = false: compiled without the table (the caller has tested DevParams::body_params itself and found it off).
+template <bool kUniformBody, bool kTable = true>
 __device__ __forceinline__ VertexOut pjb_vertex_update(f3 acc, float wsum, f3 prev, const DevParams& P, uint32_t v) {
     const float rw = __builtin_amdgcn_rcpf(wsum);
     f3 p = F3(acc.x * rw, acc.y * rw, acc.z * rw);  // 0 * inf = NaN for a particle without tets, as in the reference
@@ -77,13 +81,15 @@ __device__ __forceinline__ VertexOut pjb_vertex_update(f3 acc, float wsum, f3 pr
     bool grabbed = static_cast<int32_t>(v) == P.grab_local || static_cast<int32_t>(v) == P.grab_local2;
     if (grabbed) p = F3(P.grab[0], P.grab[1], P.grab[2]);
     body_grab_pick(P, v, grabbed, p.x, p.y, p.z);   // (body grabs, dev_common.h: a selection behind one uniform branch, no arithmetic)
-    p.x = fminf(fmaxf(p.x, P.lo[0]), P.hi[0]);
-    p.y = fminf(fmaxf(p.y, P.lo[1]), P.hi[1]);
-    p.z = fminf(fmaxf(p.z, P.lo[2]), P.hi[2]);
+    PolarBodyParams B = {P.gravity, P.friction, {P.lo[0], P.lo[1], P.lo[2]}, {P.hi[0], P.hi[1], P.hi[2]}};
+    if constexpr (kTable) B = body_params_polar<kUniformBody>(P, v);   // (body parameters, dev_common.h: the call's values or the body's row)
+    p.x = fminf(fmaxf(p.x, B.lo[0]), B.hi[0]);
+    p.y = fminf(fmaxf(p.y, B.lo[1]), B.hi[1]);
+    p.z = fminf(fmaxf(p.z, B.lo[2]), B.hi[2]);
     if (p.y < 0.0f) {
         p.y = 0.0f;
         const float Fx = prev.x - p.x, Fz = prev.z - p.z;
-        const float fr = fminf(1.0f, P.dt * P.friction);
+        const float fr = fminf(1.0f, P.dt * B.friction);
         p.x = fmaf(Fx, fr, p.x);
         p.z = fmaf(Fz, fr, p.z);
     }
@@ -93,7 +99,7 @@ __device__ __forceinline__ VertexOut pjb_vertex_update(f3 acc, float wsum, f3 pr
     const float rdt = __builtin_amdgcn_rcpf(dt);
     VertexOut o;
     o.p = p;
-    const float gx = dt * 0.0f, gy = dt * P.gravity, gz = dt * 0.0f;   // F3(0, gravity, 0) * dt
+    const float gx = dt * 0.0f, gy = dt * B.gravity, gz = dt * 0.0f;   // F3(0, gravity, 0) * dt
     o.vel = F3(fmaf(rdt, p.x - prev.x, gx), fmaf(rdt, p.y - prev.y, gy), fmaf(rdt, p.z - prev.z, gz));
     o.pred = F3(fmaf(dt, o.vel.x, p.x), fmaf(dt, o.vel.y, p.y), fmaf(dt, o.vel.z, p.z));
     return o;
@@ -228,7 +234,7 @@ __device__ __forceinline__ void pjb_tet_body(const PJBlk& d, uint32_t tile_first
                 if (sj != 0xffffffffu) { acc.x += tj.x; acc.y += tj.y; acc.z += tj.z; }
             }
         }
-        const VertexOut o = pjb_vertex_update(acc, wsum, xyz(prev4), *d.params, vid);
+        const VertexOut o = pjb_vertex_update<true>(acc, wsum, xyz(prev4), *d.params, vid);
         pos_stage = make_float4(o.pred.x, o.pred.y, o.pred.z, 0.0f);
         if (has_slot && ((range >> 15) & 1u)) {   // one writer per particle
             store_wt(d.fin_out, vid, make_float4(o.p.x, o.p.y, o.p.z, 0.0f));
@@ -546,7 +552,7 @@ __device__ __forceinline__ void pjb_frame_body(const PJBlk& d, const DevParams& 
                 acc.x += gj.x; acc.y += gj.y; acc.z += gj.z;
             }
         }
-        return pjb_vertex_update(acc, wsum, prev, P, vid);
+        return pjb_vertex_update<true>(acc, wsum, prev, P, vid);
     };
 
     for (uint32_t s = 0; s < n; s++) {
@@ -713,7 +719,7 @@ __device__ __forceinline__ void pjb_vertex_body(const PJBlk& d, uint32_t first, 
         if (__all(idx[7] == 0xffffffffu)) break;  // lists are front-packed: nobody in this wave has a ninth partial
     }
     // (the weight: sum of the rest volumes of the particle's live corners -- a constant, added up on the host in the tiles' entry order)
-    const VertexOut o = pjb_vertex_update(xyz(acc), d.wsum[v], xyz(d.fin_in[v]), *d.params, v);
+    const VertexOut o = pjb_vertex_update<false>(xyz(acc), d.wsum[v], xyz(d.fin_in[v]), *d.params, v);
     store_wt(d.fin_out, v, make_float4(o.p.x, o.p.y, o.p.z, 0.0f));
     if (d.vel) store_wt(d.vel, v, make_float4(o.vel.x, o.vel.y, o.vel.z, 0.0f));   // (null between two substeps of one call: nothing reads it there)
     store_wt(d.pos_pred, v, make_float4(o.pred.x, o.pred.y, o.pred.z, 0.0f));
@@ -838,7 +844,9 @@ __global__ __launch_bounds__(kTile, 2) void pjb_call_kernel(PJBlk d, uint32_t n_
         }
     }
     TETSIM_POLL_PB(3);
-    const VertexOut o = pjb_vertex_update(xyz(acc), wsum, xyz(prev), pv, v);
+    // (the one uniform branch of the body parameters taken HERE, around the whole update: with the table off this block runs the text it always
+    // ran, its eight values in scalar registers -- per lane behind a join inside the update the benchmark's call was 1 % slower)
+    const VertexOut o = pv.body_params ? pjb_vertex_update<false, true>(xyz(acc), wsum, xyz(prev), pv, v) : pjb_vertex_update<false, false>(xyz(acc), wsum, xyz(prev), pv, v);
     store_wt(d.fin_out, v, make_float4(o.p.x, o.p.y, o.p.z, __uint_as_float(stamp)));
     if (d.vel && sub + 1u == n_sub) store_wt(d.vel, v, make_float4(o.vel.x, o.vel.y, o.vel.z, 0.0f));   // (the velocity array: behind a call's last substep only)
     store_wt(d.pos_pred, v, make_float4(o.pred.x, o.pred.y, o.pred.z, __uint_as_float(stamp)));

@@ -106,13 +106,14 @@ __global__ __launch_bounds__(256) void TETSIM_SFX(pj_vertex_kernel_)(PJDev d, ui
     bool grabbed = static_cast<int32_t>(v) == P.grab_local || static_cast<int32_t>(v) == P.grab_local2;
     if (grabbed) p = F3(P.grab[0], P.grab[1], P.grab[2]);
     body_grab_pick(P, v, grabbed, p.x, p.y, p.z);   // (body grabs, dev_common.h: a selection behind one uniform branch, no arithmetic)
-    p.x = fminf(fmaxf(p.x, P.lo[0]), P.hi[0]);
-    p.y = fminf(fmaxf(p.y, P.lo[1]), P.hi[1]);
-    p.z = fminf(fmaxf(p.z, P.lo[2]), P.hi[2]);
+    const PolarBodyParams B = body_params_polar<false>(P, v);   // (body parameters, dev_common.h: the call's values or, per lane, the body's row)
+    p.x = fminf(fmaxf(p.x, B.lo[0]), B.hi[0]);
+    p.y = fminf(fmaxf(p.y, B.lo[1]), B.hi[1]);
+    p.z = fminf(fmaxf(p.z, B.lo[2]), B.hi[2]);
     if (p.y < 0.0f) {
         p.y = 0.0f;
         const f3 F = prev - p;
-        const float fr = fminf(1.0f, P.dt * P.friction);
+        const float fr = fminf(1.0f, P.dt * B.friction);
         p.x += F.x * fr;
         p.z += F.z * fr;
     }
@@ -122,7 +123,7 @@ __global__ __launch_bounds__(256) void TETSIM_SFX(pj_vertex_kernel_)(PJDev d, ui
     f3 vel;
     if constexpr (kFast) { const float r = __builtin_amdgcn_rcpf(P.dt); vel = dpos * r; }
     else vel = F3(dpos.x / P.dt, dpos.y / P.dt, dpos.z / P.dt);
-    vel = vel + F3(0.0f, P.gravity, 0.0f) * P.dt;
+    vel = vel + F3(0.0f, B.gravity, 0.0f) * P.dt;
 
     d.pos_final[v] = make_float4(p.x, p.y, p.z, 0.0f);
     d.vel[v] = make_float4(vel.x, vel.y, vel.z, 0.0f);

@@ -154,12 +154,15 @@ struct QParams { float dt, rdt, fr, g_dt, lo, hi, grab; int32_t grab0, grab1; ui
 // beyond those the handle's grab needs: the frame kernel has none to spare.)
 __device__ __forceinline__ QParams load_qparams(const DevParams& P, uint32_t c, uint32_t vid) {
     QParams o;
+    // (body parameters, dev_common.h: the call's values or the row of the tile's body -- a tile never spans two bodies and every lane of it
+    // carries a particle of the tile, so the row arrives through scalar loads, once per call, and nothing below holds a register more)
+    const PolarBodyParams B = body_params_polar<true>(P, vid);
     o.dt = P.dt;
     o.rdt = __builtin_amdgcn_rcpf(P.dt);
-    o.fr = fminf(1.0f, P.dt * P.friction);
-    o.g_dt = P.dt * (c == 1u ? P.gravity : 0.0f);            // F3(0, gravity, 0) * dt, :371
-    o.lo = c == 0u ? P.lo[0] : c == 1u ? P.lo[1] : P.lo[2];
-    o.hi = c == 0u ? P.hi[0] : c == 1u ? P.hi[1] : P.hi[2];
+    o.fr = fminf(1.0f, P.dt * B.friction);
+    o.g_dt = P.dt * (c == 1u ? B.gravity : 0.0f);            // F3(0, gravity, 0) * dt, :371
+    o.lo = c == 0u ? B.lo[0] : c == 1u ? B.lo[1] : B.lo[2];
+    o.hi = c == 0u ? B.hi[0] : c == 1u ? B.hi[1] : B.hi[2];
     o.grab = c == 0u ? P.grab[0] : c == 1u ? P.grab[1] : P.grab[2];
     o.grab0 = P.grab_local; o.grab1 = P.grab_local2;
     o.body_grabs = P.body_grabs;

@@ -61,10 +61,9 @@ void fill_params(const tetsim_body* h, double dt, const TetSimParams& p, DevPara
     o->gravity = static_cast<float>(p.gravity);
     o->friction = static_cast<float>(p.friction);
     const bool fixed = h->opt.solver == TETSIM_SOLVER_POLAR_JACOBI && (h->opt.flags & TETSIM_FLAG_REF_FIXED_BOUNDS);
-    const float ref_lo[3] = {-2.5f, -1.0f, -2.5f}, ref_hi[3] = {2.5f, 10.0f, 2.5f};  // SoftbodyGPU.js:347
     for (int c = 0; c < 3; c++) {
-        o->lo[c] = fixed ? ref_lo[c] : static_cast<float>(p.worldBounds[c]);
-        o->hi[c] = fixed ? ref_hi[c] : static_cast<float>(p.worldBounds[3 + c]);
+        o->lo[c] = fixed ? ref_fixed_lo(c) : static_cast<float>(p.worldBounds[c]);   // (dev_common.h: the box body_params.hip's rows use too)
+        o->hi[c] = fixed ? ref_fixed_hi(c) : static_cast<float>(p.worldBounds[3 + c]);
         o->d_lo[c] = p.worldBounds[c];
         o->d_hi[c] = p.worldBounds[3 + c];
         o->grab[c] = h->grab_pos[c];
@@ -96,6 +95,12 @@ void fill_params(const tetsim_body* h, double dt, const TetSimParams& p, DevPara
     o->bcol_count = h->d_bcol_count;
     o->bcol_f = h->d_bcol_f;
     o->bcol_d = h->d_bcol_d;
+    // body parameters (body_params.hip): likewise.  While they are on no kernel looks at the five values of `p` above; the rows live in
+    // the table, which the kernels read afresh in every launch -- new rows need no upload here
+    o->body_params = h->body_params_on ? 1u : 0u;
+    o->bp_f = h->d_bp_f;
+    o->bp_d = h->d_bp_d;
+    o->tet_body = h->d_tet_body;
     o->epoch = h->frame_epoch;
     static const int32_t poll_delay = [] { const char* e = lab_env("TETSIM_QUAD_POLL_DELAY"); return e ? atoi(e) : kQuadPollDelay; }();
     o->poll_delay = poll_delay;

@@ -82,6 +82,22 @@ def body_collider_rows(lists, per_body=None):
     return rows
 
 
+BODY_PARAM_FIELDS = ("gravity", "friction", "devCompliance", "volCompliance")   # then worldBounds: lo xyz, hi xyz
+
+
+def body_param_rows(bodies, defaults):
+    """A dict per body with the keys of physicsParams (gravity, friction, devCompliance, volCompliance, worldBounds), or None -> float64
+    [bodies, 10], the rows of setBodyParams / setBodyParamsDevice (include/tetsim.h: TETSIM_BODY_PARAMS_WIDTH -- the fields of
+    TetSimParams in its order).  A None entry, and a key a dict leaves out, come from `defaults`, a dict with all five keys.
+    torch.from_numpy(rows).to(device) is the tensor setBodyParamsDevice reads."""
+    rows = np.empty((len(bodies), capi.BODY_PARAMS_WIDTH), dtype=np.float64)
+    for b, d in enumerate(bodies):
+        d = dict(defaults, **(d or {}))
+        rows[b, :4] = [float(d[k]) for k in BODY_PARAM_FIELDS]
+        rows[b, 4:] = _vec(d["worldBounds"], 6)
+    return rows
+
+
 # tetsim_raycast_visual's records as numpy sees them (include/tetsim.h: TetSimRay, TetSimRayHit)
 RAY_DTYPE = np.dtype([("origin", "<f8", (3,)), ("direction", "<f8", (3,)), ("near", "<f8"), ("far", "<f8")])
 RAY_HIT_DTYPE = np.dtype([("hit", "<i4"), ("body", "<i4"), ("triangle", "<i4"), ("reserved", "<i4"), ("distance", "<f8"), ("point", "<f8", (3,))])
@@ -915,6 +931,43 @@ class SoftBodyHIP:
             raise ValueError("rows must be a float32 tensor on %s of shape (%d, per_body, >= %d) with a contiguous last dimension and evenly spaced rows" % (dev, n, w))
         ptr, keep = self._body_mask(torch, dev, bodies)
         capi.check(self._L.tetsim_set_body_colliders_device(self._h, rows.data_ptr(), 4 * step if n * per_body > 1 else 0, per_body, ptr, s), self._h)
+        self._mask_keep = keep   # (a converted host sequence lives until the next call: the kernel may not have read it yet)
+
+    # -- body parameters (include/tetsim.h: tetsim_set_body_params / _device) ------------------------------------------------
+    def setBodyParams(self, rows_or_dicts):
+        """Give every body its own physicsParams: [num_bodies, 10] rows (an array, a host tensor, nested lists), or a list per body of dicts (None entries and missing
+        keys come from the handle's physicsParams; body_param_rows).  Body b then steps exactly as it would alone with its row as
+        physicsParams, bit for bit; the physicsParams of the step calls are not looked at.  None switches body parameters off.  Raises
+        TetSimError(EINVAL) for a row with a non-finite value (the previous table stays in force)."""
+        if rows_or_dicts is None:
+            capi.check(self._L.tetsim_set_body_params(self._h, None), self._h)
+            return
+        n = self.info.num_bodies
+        if isinstance(rows_or_dicts, (list, tuple)) and all(d is None or isinstance(d, dict) for d in rows_or_dicts):
+            rows = body_param_rows(list(rows_or_dicts), self.physicsParams)
+        else:   # rows: an array, a host tensor, nested sequences of numbers
+            try:
+                rows = np.ascontiguousarray(rows_or_dicts, dtype=np.float64)
+            except (TypeError, ValueError):
+                raise ValueError("rows must be [%d, %d] numbers, or a list per body of dicts and None" % (n, capi.BODY_PARAMS_WIDTH)) from None
+        if rows.shape != (n, capi.BODY_PARAMS_WIDTH):
+            raise ValueError("rows must be [%d, %d]" % (n, capi.BODY_PARAMS_WIDTH))
+        capi.check(self._L.tetsim_set_body_params(self._h, rows.ctypes.data_as(capi.C.POINTER(capi.C.c_double))), self._h)
+
+    def setBodyParamsDevice(self, rows, bodies=None, stream=None):
+        """setBodyParams from a device tensor, with no host copy and no synchronisation: rows torch.float64 [num_bodies, w] with w >= 10
+        and a contiguous last dimension (a [:, :10] view of a wider tensor is fine: nothing outside a row's ten doubles is read), on the
+        handle's device and produced on `stream` (as in exportTensors; reusable on it right after the call).  bodies: a mask as in
+        setBodyGrabsDevice -- a body it leaves out keeps its row.  A row with a non-finite value leaves its body's previous row in place."""
+        import torch
+        dev, s = self._torch_stream(torch, stream)
+        n, w = self.info.num_bodies, capi.BODY_PARAMS_WIDTH
+        ok = (isinstance(rows, torch.Tensor) and rows.dtype == torch.float64 and rows.device == dev and rows.dim() == 2 and rows.shape[0] == n
+              and rows.shape[1] >= w and rows.stride(1) == 1 and (n == 1 or rows.stride(0) >= w))
+        if not ok:
+            raise ValueError("rows must be a float64 tensor on %s of shape (%d, >= %d) with a contiguous last dimension" % (dev, n, w))
+        ptr, keep = self._body_mask(torch, dev, bodies)
+        capi.check(self._L.tetsim_set_body_params_device(self._h, rows.data_ptr(), 8 * rows.stride(0) if n > 1 else 0, ptr, s), self._h)
         self._mask_keep = keep   # (a converted host sequence lives until the next call: the kernel may not have read it yet)
 
     def nearestParticlesDevice(self, points, out_ids=None, out_dist2=None, stream=None):
