@@ -407,7 +407,8 @@ int tetsim_nearest_particle(tetsim_handle h, const float xyz[3], int32_t *global
  * count works (the launches are chunked by the grid limits).  The call skins first, like tetsim_read_visual_mesh, so the answer
  * belongs to the last completed substep; it synchronises once and changes no solver state.
  * Out of scope: partitioned bodies; all hits along a ray; back-side or double-side materials; the edge wireframe's LineSegments;
- * an acceleration structure (brute force: every ray against every triangle); closest-point queries. */
+ * an acceleration structure behind THIS call (brute force: every ray against every triangle; the per-body device casts have one:
+ * tetsim_raycast_visual_bvh_device); closest-point queries. */
 typedef struct TetSimRay    { double origin[3], direction[3], near, far; } TetSimRay;       /* far may be +inf */
 typedef struct TetSimRayHit { int32_t hit, body, triangle, reserved; double distance, point[3]; } TetSimRayHit;
 int tetsim_raycast_visual(tetsim_handle h, const TetSimRay *rays, uint32_t count, TetSimRayHit *hits);
@@ -1020,7 +1021,8 @@ int tetsim_prep_pose_table(const float *verts, uint32_t nv, const int32_t *tets,
  * device, or whose rows do not fit the allocation it points into.  TETSIM_ESTATE: no visual mesh; no triangles (the ray call only); a
  * partitioned body; with ray_body != NULL a triangle whose three rows belong to different bodies (found once on the host; such a
  * mesh still casts with ray_body == NULL).  count == 0 succeeds and enqueues nothing.
- * Out of scope: partitioned bodies; an acceleration structure; all hits along a ray; back-side or double-side materials; f32 rays or
+ * Out of scope: partitioned bodies; an acceleration structure behind THIS call (tetsim_raycast_visual_bvh_device below is the same
+ * call through one); all hits along a ray; back-side or double-side materials; f32 rays or
  * hits; rays attached to a moving frame (the caller transforms them, on the device, before the call); gradients; a Node
  * binding (Node has no device tensors). */
 #define TETSIM_RAY_INVALID (-1)   /* TetSimRayHit.hit of a ray the device refused */
@@ -1032,6 +1034,55 @@ int tetsim_raycast_visual_device(tetsim_handle h,
         void *caller_stream);
 /* one row of 4 doubles per body (centre xyz, radius) into DEVICE memory; stride 0 = packed 32, else a multiple of 8, >= 32 */
 int tetsim_visual_bounding_spheres_device(tetsim_handle h, void *dst, uint64_t row_stride, void *caller_stream);
+
+/* --- range sensors through a refitted bounding-volume hierarchy --------------------------------- */
+
+/* tetsim_raycast_visual_device is brute force, every ray against every triangle of its body: a 32 x 32 depth image of a Dragon costs
+ * a hundred frames of its physics.  tetsim_raycast_visual_bvh_device is its twin -- the signature, the records, the stream contract and
+ * the list of errors are those of tetsim_raycast_visual_device, word for word -- and answers from a tree of boxes per body that is
+ * refitted on the device at every call.  An ADDITIVE extension of ABI version 5 (TETSIM_ABI_VERSION is unchanged; no existing struct
+ * changed): look the symbol up.
+ *
+ * THE DEFINITION is its own, and it does not mention the tree: a culling structure cannot promise three.js's answer for a ray that lies
+ * nearly in a triangle's plane, where step 3 of tetsim_raycast_visual may accept a "hit" whose computed point lies anywhere.  So the
+ * call is defined as brute force with two more conditions per triangle, stated so that ANY conservative tree reproduces it bit for bit;
+ * it differs from tetsim_raycast_visual_device only for hits that are numerically meaningless (tests/raycast_bvh_ref.py is the
+ * definition in numpy).  f64, every operation rounded separately.
+ *   Steps 1 and 2 of tetsim_raycast_visual -- the sphere cull and the normalised direction d -- as they are, with the sphere of the
+ *   ray's body (ray_body == NULL: of the whole mesh); o = origin.
+ *   Padding:  e = 2^-20 * (radius + sqrt(dot(o - centre, o - centre))), centre and radius of that sphere.
+ *   Padded box of a triangle with f32 corners: lo_k / hi_k = the smallest / largest of the three corners' component k (exact, taken as
+ *     doubles); L_k = lo_k - e, H_k = hi_k + e.
+ *   Slab interval: tn = -inf, tf = +inf; for k = 0, 1, 2:  inv = 1.0 / d_k;  if d_k == 0 or inv is infinite, axis k passes iff
+ *     L_k <= o_k && o_k <= H_k, and leaves tn, tf alone;  else t1 = (L_k - o_k) * inv, t2 = (H_k - o_k) * inv,
+ *     tn = max(tn, min(t1, t2)), tf = min(tf, max(t1, t2)).
+ *   The triangle is a CANDIDATE iff every axis passes and tn <= tf.  A candidate COUNTS iff step 3 of tetsim_raycast_visual accepts it,
+ *     the near / far window included, and tn <= distance && distance <= tf.
+ *   The record is the smallest (distance, triangle) among the counting hits, in lexicographic order; point and distance are step 3's for
+ *     that triangle.  Invalid rays, misses, `body` and `triangle` are those of tetsim_raycast_visual_device.
+ * Why a tree reproduces this: every comparison above is false for a NaN (none arises from finite inputs), and the operations are monotone
+ * in IEEE arithmetic -- a node's f32 box that contains a triangle's box has tn <= the triangle's tn, tf >= its tf, and its axis tests
+ * pass wherever the triangle's do.  The traversal skips a node only if its own test (same formulas, same e) fails, tn > far, tf < near,
+ * or a best hit exists and tn > its distance (tn == best is entered: a lower triangle index may tie); at a leaf every triangle gets the
+ * box of its OWN corners.  Visit order and tree shape then cannot change a bit of the answer.
+ *
+ * THE TREE.  Topology: built once per handle by its first such call, on the host, from the skinned positions of that moment -- per body
+ * the triangles of its own surface in the Morton order of their centroids, four to a leaf, under a complete binary tree in heap order
+ * (no pointers; a body without triangles or with one is a tree of one leaf).  That call may block and synchronise once, like the first
+ * tetsim_raycast_visual_device call, whose tables it extends; what it allocates counts into TetSimInfo.device_bytes from then on and does
+ * not depend on count.  The topology never changes: a body deformed beyond recognition is answered as exactly, only more slowly.
+ * Refit: at EVERY call, on the handle's stream behind the skinning -- exact f32 min / max, leaves from corners, nodes from children,
+ * all bodies together in two launches whatever their number; no host synchronisation.  Traversal: one lane per ray, near child first,
+ * stackless.  With ray_body == NULL a ray walks the bodies' trees, lowest body first, carrying its best; a triangle whose rows span bodies
+ * then belongs to the body of its first row.  Rays need NOT be grouped by body: a workgroup's rays may name any mix of bodies.
+ * When to use which: INTEGRATION.md 4f.  Out of scope: this structure behind the host calls; rebuilding the topology; and what
+ * tetsim_raycast_visual_device leaves out. */
+int tetsim_raycast_visual_bvh_device(tetsim_handle h,
+        const void *rays,     uint64_t ray_stride,   /* as tetsim_raycast_visual_device */
+        const void *ray_body,
+        uint32_t count,
+        void *hits,           uint64_t hit_stride,
+        void *caller_stream);
 
 /* --- per-tet strain on the device: deformation gradient, volume ratio, principal stretches ------ */
 
@@ -1247,6 +1298,13 @@ int tetsim_prep_tiles(const float *verts, uint32_t nv, const int32_t *tets, uint
                       uint8_t *corner_slot, uint32_t *num_tiles);
 /* Scatter table of SoftbodyGPU.js:563-577: slots[v*36 + s] = 4*tet + corner, -1 = empty.
  * ref_quirk != 0 reproduces the `<= 0.0` test.  Returns the number of dropped contributions. */
+/* The topology of that tree for any triangle list, without a device: positions [3 * nvis], tri_ids [3 * ntri], tri_body [ntri] (the
+ * body of every triangle) or NULL for one body.  tri_first [bodies + 1]: the bodies' ranges in `order`; order [ntri]: triangle ids, per
+ * body in Morton order; leaf l of body b holds order[tri_first[b] + 4 l ...] (four, fewer at the end); node_first [bodies + 1] and depth
+ * [bodies]: body b has 2^depth leaf slots and its node i (root 1, children 2 i and 2 i + 1, leaves from 2^depth) is slot
+ * node_first[b] + i.  node_range, if not NULL: [node_first[bodies]][2], per slot the range in `order` of the triangles below it. */
+int tetsim_prep_bvh(const float *positions, uint32_t nvis, const int32_t *tri_ids, uint32_t ntri, const int32_t *tri_body, uint32_t bodies,
+                    uint32_t *tri_first, uint32_t *order, uint32_t *node_first, uint32_t *depth, uint32_t *node_range);
 int tetsim_prep_slot_table(const int32_t *tets, uint32_t nt, uint32_t nv, int32_t ref_quirk,
                            int32_t *slots /*[nv*36]*/, uint32_t *dropped);
 /* The dispatch schedule of the one-launch polar call (large unpartitioned bodies, fused_particle_pass 5).  Host only.

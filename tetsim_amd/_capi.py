@@ -150,7 +150,7 @@ SYMBOLS = [
     "tetsim_snapshot_create", "tetsim_snapshot_capture", "tetsim_snapshot_restore", "tetsim_snapshot_destroy",
     "tetsim_observe_bodies_device", "tetsim_read_body_observations",
     "tetsim_body_poses_device", "tetsim_read_body_poses", "tetsim_prep_pose_table",
-    "tetsim_raycast_visual_device", "tetsim_visual_bounding_spheres_device",
+    "tetsim_raycast_visual_device", "tetsim_visual_bounding_spheres_device", "tetsim_raycast_visual_bvh_device", "tetsim_prep_bvh",
     "tetsim_tet_strain_device", "tetsim_read_tet_strain", "tetsim_body_strain_device", "tetsim_visual_strain_device", "tetsim_prep_strain_table",
     "tetsim_set_body_grabs", "tetsim_set_body_grabs_device", "tetsim_nearest_particles_device",
     "tetsim_set_body_colliders", "tetsim_set_body_colliders_device",
@@ -170,7 +170,8 @@ OPTIONAL_SYMBOLS = ("tetsim_set_colliders", "tetsim_raycast_visual", "tetsim_sta
                     "tetsim_set_body_colliders", "tetsim_set_body_colliders_device",
                     "tetsim_set_body_params", "tetsim_set_body_params_device",
                     "tetsim_place_bodies_device", "tetsim_place_bodies",
-                    "tetsim_body_poses_device", "tetsim_read_body_poses", "tetsim_prep_pose_table")
+                    "tetsim_body_poses_device", "tetsim_read_body_poses", "tetsim_prep_pose_table",
+                    "tetsim_raycast_visual_bvh_device", "tetsim_prep_bvh")
 
 _lib = None
 
@@ -257,6 +258,9 @@ def lib():
     if hasattr(L, "tetsim_raycast_visual_device"):   # (additive to ABI 5; rays, bodies, hits and the stream travel as plain addresses)
         L.tetsim_raycast_visual_device.argtypes = [H, C.c_void_p, C.c_uint64, C.c_void_p, u32, C.c_void_p, C.c_uint64, C.c_void_p]
         L.tetsim_visual_bounding_spheres_device.argtypes = [H, C.c_void_p, C.c_uint64, C.c_void_p]
+    if hasattr(L, "tetsim_raycast_visual_bvh_device"):   # (additive to ABI 5; the arguments of tetsim_raycast_visual_device)
+        L.tetsim_raycast_visual_bvh_device.argtypes = [H, C.c_void_p, C.c_uint64, C.c_void_p, u32, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.tetsim_prep_bvh.argtypes = [fp, u32, ip, u32, ip, u32] + [C.POINTER(u32)] * 5
     if hasattr(L, "tetsim_tet_strain_device"):   # (additive to ABI 5; dst and the stream travel as plain addresses)
         L.tetsim_tet_strain_device.argtypes = [H, C.c_void_p, C.c_uint64, C.c_void_p]
         L.tetsim_read_tet_strain.argtypes = [H, fp]

@@ -398,6 +398,9 @@ struct tetsim_body {
     bool qrows_ready = false, qtris_ready = false;
     bool tri_spans_bodies = false;     // some triangle's three rows belong to different bodies: no per-body cast
     RayCand* d_cast_cand = nullptr;    // [kCastCandCap]
+    // tetsim_raycast_visual_bvh_device (query_bvh.hip): the tree over every body's triangles, its topology built by the first such call
+    BvhDev bvh;
+    bool bvh_ready = false;
 
     // NEOHOOKEAN_GS
     NHDev nh;

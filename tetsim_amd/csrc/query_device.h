@@ -1,8 +1,11 @@
-// query_device.h -- range sensors on the device (include/tetsim.h: tetsim_raycast_visual_device /
+// query_device.h -- range sensors on the device (include/tetsim.h: tetsim_raycast_visual_device / tetsim_raycast_visual_bvh_device /
 // tetsim_visual_bounding_spheres_device): what tetsim_visual.hip and query_kernels.hip share beyond dev_common.h -- the one definition of
 // an invalid ray, the per-body tables of a handle's visual mesh and the launches over them.
 #pragma once
 #include "dev_common.h"
+
+#include <string>
+#include <vector>
 
 namespace tetsim {
 
@@ -50,5 +53,44 @@ void query_launch_spheres_out(hipStream_t s, const QueryBodiesDev& b, char* dst,
 void query_launch_cast_device(hipStream_t s, const QueryDev& q, const QueryBodiesDev& b, const CastIo& io, RayCand* cand);
 // into how many parts the triangle range is split over gridDim.y (few rays must not run on few compute units)
 uint32_t query_cast_splits(uint32_t tiles, uint32_t count);
+
+// ---- the refitted tree behind tetsim_raycast_visual_bvh_device (query_bvh.hip) ---------------------------------------------------------
+// Per body a COMPLETE BINARY TREE IN HEAP ORDER over its leaves: the body's triangles (its tri_first range) in the Morton order of their
+// centroids, kBvhLeaf consecutive ones to a leaf, the leaves padded to a power of two.  Node 1 is the root, node i has the children 2i and
+// 2i + 1, the leaves are the nodes [2^depth, 2^(depth + 1)); nothing else is stored: no child or parent pointers, no counters.  A node's
+// box is the exact f32 min / max of its triangles' corners; a node without triangles keeps the empty box (lo = +inf > hi = -inf).
+constexpr uint32_t kBvhLeaf = 4;            // triangles of a leaf
+constexpr uint32_t kBvhFoldLevels = 8;      // levels a workgroup of the refit folds through LDS: 2^8 leaves = its 256 lanes
+struct BvhBox { float lo[3], hi[3]; };
+struct BvhDev {
+    const uint32_t* order = nullptr;        // [ntri] position in a body's tri_first range -> triangle id, the body's Morton order
+    const uint32_t* node_first = nullptr;   // [bodies] where the body's nodes start in `box` (even; slot 0 of a body is unused)
+    const uint32_t* depth = nullptr;        // [bodies] levels below the root: 2^depth leaf slots
+    BvhBox* box = nullptr;                  // [node_first[bodies]]
+    const uint32_t* fold = nullptr;         // [folds][2] (body, subtree): what workgroup w of the refit's first pass folds
+    const uint32_t* top_body = nullptr;     // [tops] the bodies of more than 2^kBvhFoldLevels leaf slots: the second pass, a workgroup each
+    uint32_t folds = 0, tops = 0;
+    uint32_t* stats = nullptr;              // development (TETSIM_BVH_STATS builds only): [count][2] boxes and triangles tested per ray
+};
+__host__ __device__ inline uint32_t bvh_leaves(uint32_t ntri) { return ntri / kBvhLeaf + (ntri % kBvhLeaf ? 1u : 0u); }
+__host__ __device__ inline uint32_t bvh_depth(uint32_t leaves) { uint32_t d = 0; while ((1u << d) < leaves) d++; return d; }
+__host__ __device__ inline uint32_t bvh_level(uint32_t node) { return 31u - static_cast<uint32_t>(__builtin_clz(node)); }
+// the leaves [first, end) below node `node` of a tree of `depth` levels (the padding included: clip with the body's leaf count)
+__host__ __device__ inline void bvh_node_leaves(uint32_t node, uint32_t depth, uint32_t* first, uint32_t* end) {
+    const uint32_t level = bvh_level(node), span = depth - level;
+    *first = (node - (1u << level)) << span;
+    *end = *first + (1u << span);
+}
+// The topology, built once on the host (no device needed: tetsim_prep_bvh returns it).  pos: xyz at pos + pos_stride * row; tri: three
+// rows at tri + tri_stride * id; tri_sorted / tri_first as in QueryBodiesDev.  "" or what is wrong.
+struct BvhTopology {
+    std::vector<uint32_t> order, node_first /* [bodies + 1] */, depth, fold, top_body;
+};
+std::string bvh_build_topology(const float* pos, uint32_t pos_stride, const int32_t* tri, uint32_t tri_stride, const uint32_t* tri_sorted,
+                               const uint32_t* tri_first, uint32_t bodies, BvhTopology* out);
+// the refit, in stream order behind the skinning: two launches whatever the number of bodies (the second only if some body has tops)
+void query_launch_bvh_refit(hipStream_t s, const QueryDev& q, const QueryBodiesDev& b, const BvhDev& v);
+// The cast: q.sphere (io.ray_body null) or b.spheres (else) and the boxes must be current.
+void query_launch_cast_bvh(hipStream_t s, const QueryDev& q, const QueryBodiesDev& b, const BvhDev& v, const CastIo& io);
 
 }  // namespace tetsim

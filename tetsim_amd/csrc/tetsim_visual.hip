@@ -502,8 +502,45 @@ int tetsim_start_grab_ray(tetsim_handle h, const TetSimRay* ray, TetSimRayHit* h
 }
 
 // ---- range sensors: the same casts and spheres per body, from and into the caller's device memory (query_device.h) -------------------
-int tetsim_raycast_visual_device(tetsim_handle h, const void* rays, uint64_t ray_stride, const void* ray_body, uint32_t count, void* hits, uint64_t hit_stride,
-                                 void* caller_stream) {
+namespace {
+// The topology of the tree (query_device.h), built once from the positions of this moment: the call skins, waits and reads the positions and
+// the tables back -- as the first tetsim_raycast_visual_device call blocks for its tables.  Boxes are not made here: every call refits them.
+int ensure_bvh(tetsim_body* h) {
+    if (h->bvh_ready) return 0;
+    if (int rc = ensure_triangle_tables(h)) return rc;
+    QueryDev q;
+    if (int rc = skin_for_query(h, &q)) return rc;
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const QueryBodiesDev& b = h->qbodies;
+    std::vector<float4> pos(q.nvis);
+    std::vector<int4> tri(q.ntri);
+    std::vector<uint32_t> sorted(q.ntri), first(b.bodies + 1u);
+    HIPCHK(h, hipMemcpy(pos.data(), q.pos, pos.size() * sizeof(float4), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(tri.data(), q.tri, tri.size() * sizeof(int4), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(sorted.data(), b.tri_sorted, sorted.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(first.data(), b.tri_first, first.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    BvhTopology topo;
+    const std::string why = bvh_build_topology(&pos[0].x, 4u, &tri[0].x, 4u, sorted.data(), first.data(), b.bodies, &topo);
+    if (!why.empty()) return fail(h, TETSIM_EINVAL, why);
+    uint32_t *d_order = nullptr, *d_node_first = nullptr, *d_depth = nullptr, *d_fold = nullptr, *d_top = nullptr;
+    BvhBox* d_box = nullptr;
+    int rc;
+    if ((rc = dev_alloc(h, &d_order, topo.order.size())) || (rc = dev_alloc(h, &d_node_first, topo.node_first.size())) ||
+        (rc = dev_alloc(h, &d_depth, topo.depth.size())) || (rc = dev_alloc(h, &d_fold, topo.fold.size())) ||
+        (rc = dev_alloc(h, &d_top, topo.top_body.size())) || (rc = dev_alloc(h, &d_box, topo.node_first[b.bodies]))) return rc;
+    if ((rc = upload(h, d_order, topo.order)) || (rc = upload(h, d_node_first, topo.node_first)) || (rc = upload(h, d_depth, topo.depth)) ||
+        (rc = upload(h, d_fold, topo.fold)) || (rc = upload(h, d_top, topo.top_body))) return rc;
+    BvhDev& v = h->bvh;
+    v.order = d_order; v.node_first = d_node_first; v.depth = d_depth; v.box = d_box; v.fold = d_fold; v.top_body = d_top;
+    v.folds = static_cast<uint32_t>(topo.fold.size() / 2u); v.tops = static_cast<uint32_t>(topo.top_body.size());
+    h->bvh_ready = true;
+    return 0;
+}
+
+// tetsim_raycast_visual_device and tetsim_raycast_visual_bvh_device: one signature, one list of errors, one handshake; `bvh` chooses the kernels
+int raycast_device(tetsim_handle h, const void* rays, uint64_t ray_stride, const void* ray_body, uint32_t count, void* hits, uint64_t hit_stride,
+                   void* caller_stream, bool bvh) {
     if (!h) return TETSIM_EINVAL;
     if (count && (!rays || !hits)) return fail(h, TETSIM_EINVAL, "null argument");
     constexpr uint64_t ray_row = sizeof(TetSimRay), hit_row = sizeof(TetSimRayHit);
@@ -524,14 +561,90 @@ int tetsim_raycast_visual_device(tetsim_handle h, const void* rays, uint64_t ray
     if (ray_body) { if (int rc = check_device_records(h, ray_body, 4u, count, 4u, 4u, "ray_body")) return rc; }
     // ---- every argument is good: from here on only allocation and HIP itself can fail
     if (int rc = ensure_triangle_tables(h)) return rc;
+    if (bvh) { if (int rc = ensure_bvh(h)) return rc; }
     return on_caller_stream(h, caller_stream, [&]() -> int {
         QueryDev q;
         if (int rc = skin_for_query(h, &q)) return rc;
         if (ray_body) query_launch_body_spheres(h->stream, q, h->qbodies);
         else query_launch_sphere(h->stream, q);
-        query_launch_cast_device(h->stream, q, h->qbodies, io, h->d_cast_cand);
+        if (bvh) {
+            query_launch_bvh_refit(h->stream, q, h->qbodies, h->bvh);
+            query_launch_cast_bvh(h->stream, q, h->qbodies, h->bvh, io);
+        } else {
+            query_launch_cast_device(h->stream, q, h->qbodies, io, h->d_cast_cand);
+        }
         return launched(h);
     });
+}
+}  // namespace
+
+int tetsim_raycast_visual_device(tetsim_handle h, const void* rays, uint64_t ray_stride, const void* ray_body, uint32_t count, void* hits, uint64_t hit_stride,
+                                 void* caller_stream) {
+    return raycast_device(h, rays, ray_stride, ray_body, count, hits, hit_stride, caller_stream, false);
+}
+
+// the same casts through the refitted tree (query_bvh.hip); its own definition: include/tetsim.h
+int tetsim_raycast_visual_bvh_device(tetsim_handle h, const void* rays, uint64_t ray_stride, const void* ray_body, uint32_t count, void* hits,
+                                     uint64_t hit_stride, void* caller_stream) {
+    return raycast_device(h, rays, ray_stride, ray_body, count, hits, hit_stride, caller_stream, true);
+}
+
+#ifdef TETSIM_BVH_STATS
+// development builds only (tools/raycast_bvh_cost.py): the next tree casts count, per ray, the boxes and the triangles they test into
+// stats [count][2] uint32 in DEVICE memory; NULL turns the counting off again
+int tetsim_debug_bvh_stats(tetsim_handle h, void* stats) {
+    if (!h) return TETSIM_EINVAL;
+    h->bvh.stats = static_cast<uint32_t*>(stats);
+    return 0;
+}
+// ... and the refit alone, with the call's handshake around it: no skinning, no spheres, no cast (the tree must exist)
+int tetsim_debug_bvh_refit(tetsim_handle h, void* caller_stream) {
+    if (!h || !h->bvh_ready) return TETSIM_EINVAL;
+    return on_caller_stream(h, caller_stream, [&]() -> int {
+        QueryDev q;
+        q.nvis = h->skin.nvis; q.ntri = h->skin.ntri; q.pos = h->skin.out_pos; q.tri = h->skin.tri; q.sphere = h->d_sphere;
+        query_launch_bvh_refit(h->stream, q, h->qbodies, h->bvh);
+        return launched(h);
+    });
+}
+#endif
+
+// The tree's topology without a device (query_device.h: bvh_build_topology, what the first tetsim_raycast_visual_bvh_device call builds from
+// the positions of that moment).  positions [3 * nvis]; tri_ids [3 * ntri]; tri_body [ntri] or NULL (one body).  Out: tri_first [bodies + 1],
+// order [ntri], node_first [bodies + 1], depth [bodies]; node_range, if not NULL, [node_first[bodies]][2]: the range in `order` of the
+// triangles below every node (slot 0 of a body: 0, 0) -- call once with NULL to learn node_first[bodies].
+int tetsim_prep_bvh(const float* positions, uint32_t nvis, const int32_t* tri_ids, uint32_t ntri, const int32_t* tri_body, uint32_t bodies,
+                    uint32_t* tri_first, uint32_t* order, uint32_t* node_first, uint32_t* depth, uint32_t* node_range) {
+    if ((nvis && !positions) || (ntri && !tri_ids) || bodies == 0 || !tri_first || (ntri && !order) || !node_first || !depth) return TETSIM_EINVAL;
+    for (uint32_t t = 0; t < ntri; t++) {
+        for (int k = 0; k < 3; k++)
+            if (tri_ids[3 * static_cast<size_t>(t) + k] < 0 || static_cast<uint32_t>(tri_ids[3 * static_cast<size_t>(t) + k]) >= nvis) return TETSIM_EINVAL;
+        if (tri_body && (tri_body[t] < 0 || static_cast<uint32_t>(tri_body[t]) >= bodies)) return TETSIM_EINVAL;
+    }
+    std::vector<uint32_t> first(bodies + 1u, 0u), sorted(ntri);
+    for (uint32_t t = 0; t < ntri; t++) first[(tri_body ? tri_body[t] : 0) + 1u]++;
+    for (uint32_t k = 0; k < bodies; k++) first[k + 1u] += first[k];
+    std::vector<uint32_t> fill(first.begin(), first.end() - 1);
+    for (uint32_t t = 0; t < ntri; t++) sorted[fill[tri_body ? tri_body[t] : 0]++] = t;
+    BvhTopology topo;
+    if (!bvh_build_topology(positions, 3u, tri_ids, 3u, sorted.data(), first.data(), bodies, &topo).empty()) return TETSIM_EINVAL;
+    std::copy(first.begin(), first.end(), tri_first);
+    std::copy(topo.order.begin(), topo.order.end(), order);
+    std::copy(topo.node_first.begin(), topo.node_first.end(), node_first);
+    std::copy(topo.depth.begin(), topo.depth.end(), depth);
+    if (node_range)
+        for (uint32_t b = 0; b < bodies; b++) {
+            const uint32_t n = first[b + 1u] - first[b], slots = 1u << topo.depth[b];
+            uint32_t* const r = node_range + 2ull * topo.node_first[b];
+            r[0] = r[1] = 0u;
+            for (uint32_t i = 1; i < 2u * slots; i++) {
+                uint32_t lo, hi;
+                bvh_node_leaves(i, topo.depth[b], &lo, &hi);
+                r[2ull * i] = first[b] + static_cast<uint32_t>(std::min<uint64_t>(static_cast<uint64_t>(lo) * kBvhLeaf, n));
+                r[2ull * i + 1u] = first[b] + static_cast<uint32_t>(std::min<uint64_t>(static_cast<uint64_t>(hi) * kBvhLeaf, n));
+            }
+        }
+    return 0;
 }
 
 int tetsim_visual_bounding_spheres_device(tetsim_handle h, void* dst, uint64_t row_stride, void* caller_stream) {

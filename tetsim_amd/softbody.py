@@ -795,6 +795,17 @@ class SoftBodyHIP:
         like the export tensors, or `out`, whose rows may be strided): hit, body, triangle (int32 [count]), distance (float64 [count]),
         point (float64 [count, 3]).  An invalid ray or body gets hit = _capi.RAY_INVALID instead of an exception.  Rays grouped by body
         are the fast case.  Valid for work enqueued on `stream` (as in exportTensors) after this returns."""
+        return self._raycastDevice(self._L.tetsim_raycast_visual_device, rays, bodies, out, stream)
+
+    def raycastVisualBvhDevice(self, rays, bodies=None, out=None, stream=None):
+        """raycastVisualDevice through a tree of boxes per body that is refitted on the device at every call (include/tetsim.h:
+        tetsim_raycast_visual_bvh_device): the same arguments and the same views.  Many rays cost orders of magnitude less, and they need
+        not be grouped by body.  The answer has a definition of its own (tests/raycast_bvh_ref.py), which differs from raycastVisualDevice's
+        only for hits that are numerically meaningless -- a ray nearly in a triangle's plane.  The handle's first such call builds the
+        tree's topology on the host and may block."""
+        return self._raycastDevice(self._L.tetsim_raycast_visual_bvh_device, rays, bodies, out, stream)
+
+    def _raycastDevice(self, call, rays, bodies, out, stream):
         import torch
         dev, s = self._torch_stream(torch, stream)
         if (not isinstance(rays, torch.Tensor) or rays.dtype != torch.float64 or rays.device != dev or rays.dim() != 2 or rays.shape[1] != 8
@@ -811,9 +822,8 @@ class SoftBodyHIP:
         elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != dev or tuple(out.shape) != (n, 48)
               or (n and out.stride(1) != 1) or (n > 1 and (out.stride(0) < 48 or out.stride(0) % 8)) or (n and out.data_ptr() % 8)):
             raise ValueError("out must be a uint8 tensor on %s of shape (%d, 48) with contiguous, non-overlapping, 8-byte aligned rows" % (dev, n))
-        capi.check(self._L.tetsim_raycast_visual_device(self._h, rays.data_ptr() if n else None, 8 * rays.stride(0) if n > 1 else 0,
-                                                        bodies.data_ptr() if bodies is not None and n else None, n,
-                                                        out.data_ptr() if n else None, out.stride(0) if n > 1 else 0, s), self._h)
+        capi.check(call(self._h, rays.data_ptr() if n else None, 8 * rays.stride(0) if n > 1 else 0, bodies.data_ptr() if bodies is not None and n else None, n,
+                        out.data_ptr() if n else None, out.stride(0) if n > 1 else 0, s), self._h)
         i32, f64 = out.view(torch.int32), out.view(torch.float64)   # (rows of 12 / 6 of them; a strided `out` keeps its row stride)
         return {"hit": i32[:, 0], "body": i32[:, 1], "triangle": i32[:, 2], "distance": f64[:, 2], "point": f64[:, 3:6], "raw": out}
 
