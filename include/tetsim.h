@@ -572,7 +572,7 @@ int tetsim_nearest_particles_device(tetsim_handle h, const void *points, uint64_
  * substep); 64 Dragons Neo-Hookean FAST x207 (2.49 s against 12 ms: 43,520 level launches in place of one workgroup per body -- a
  * batch of small Neo-Hookean bodies pays dearly for the table); the set kernel takes 37 us for 64 bodies and 45 us for 4,096.
  * Out of scope: more than eight colliders per body; f64 rows; colliders
- * between bodies; partitioned bodies; contact read-back; a Node binding. */
+ * between bodies; partitioned bodies; a Node binding.  Contact read-back: tetsim_touch_bodies_device ("touch sensing", below). */
 #define TETSIM_BODY_COLLIDER_FLOATS 24
 /* rows: num_bodies * per_body rows of 24 f32, body-major (row of body b, slot k at index b * per_body + k), packed.
  * rows == NULL: body colliders OFF (per_body ignored). */
@@ -977,6 +977,93 @@ int tetsim_read_body_poses(tetsim_handle h, double *out);
 int tetsim_prep_pose_table(const float *verts, uint32_t nv, const int32_t *tets, uint32_t nt,
                            const uint32_t *body_first_vert, const uint32_t *body_first_tet, uint32_t num_bodies,
                            double density, void *records_out, double *centres_out);
+
+/* --- touch sensing on the device: per-body contacts with the colliders ------------------------- */
+
+/* Whether a body rests on its tray, is pinched by a jaw or has slipped off a paddle: the contacts of every body with the colliders
+ * ITS substeps meet -- per body and collider slot the touching particles, the least distance, the centroid, the mean normal and the mean
+ * relative velocity (tetsim_touch_bodies_device; tetsim_read_body_touch on the host), or per particle the nearest collider
+ * (tetsim_touch_particles_device: a tactile skin, a channel to colour by).  A read-only, GEOMETRIC query of the stored state: no solver
+ * state changes, no stepping kernel knows of it, held particles are included, and nothing is recorded inside a substep.  An ADDITIVE
+ * extension of ABI version 5 (TETSIM_ABI_VERSION is unchanged; no existing struct changed): look the symbols up.
+ *
+ * THE LIST of a body is the one its substeps walk: while body colliders are ON (tetsim_set_body_colliders) the body's compacted table
+ * entries -- slot k is its k-th non-empty row -- otherwise the handle's list (tetsim_set_colliders), slot k = collider k.  Its values are
+ * the ones the substeps read -- the f32 view of a POLAR_JACOBI or FAST NEOHOOKEAN_GS handle, the f64 view of a PRECISE NEOHOOKEAN_GS
+ * handle, normalised as described there -- widened to f64.
+ *
+ * DEFINITIONS.  p = a stored f32 position widened to f64 (what tetsim_read_positions returns).  All arithmetic is f64, every operation
+ * rounded on its own (no fused multiply-add), / and sqrt correctly rounded; dot(u,v) = (u.x*v.x + u.y*v.y) + u.z*v.z.  The signed
+ * distance sd and the outward unit normal n of p against one collider continue the hit test of tetsim_set_colliders to the outside:
+ *   sphere   d = p - a, L = sqrt(dot(d, d)); sd = L - radius; n = d / L if L > 0, else n = 0
+ *   capsule  ab = b - a, t = dot(p - a, ab) / dot(ab, ab) (0 if dot(ab, ab) == 0), t = min(max(t, 0), 1); d = p - (a + ab*t), as the sphere
+ *   plane    sd = dot(p - a, b); n = b
+ *   box      l_k = dot(p - a, u_k), g_k = e_k - |l_k| (e = b, the half-extents).  If g_k >= 0 for every k (inside or on the box):
+ *            k = argmin g_k (lowest k on ties), sd = -g_k, n = l_k >= 0 ? u_k : -u_k.  Otherwise o_k = max(-g_k, 0) (NaN for a NaN g_k),
+ *            sd = sqrt((o_0*o_0 + o_1*o_1) + o_2*o_2), w = the sum over k = 0, 1, 2 of (l_k >= 0 ? o_k : -o_k) * u_k, added component by
+ *            component from 0.0, n = w / sd.
+ * WHERE THE STEP WOULD PUSH: wherever the f64 hit test of tetsim_set_colliders hits p, sd < 0, -sd is bit for bit the depth and n bit for
+ * bit the normal of that push.  (A particle at rest on a collider was pushed OUT by its last substep and stored in f32, so it sits within
+ * a few f32 roundings of sd = 0, on either side (measured: -1e-7 .. 0): that is what `margin` is for.)
+ * A particle TOUCHES a slot when sd < margin (metres; any finite value, negative ones too).  A NaN sd never touches and is never a
+ * minimum; minima are taken over ALL particles of the body, touching or not (the distance still to go), by fmin.
+ *
+ * THE BODY ROW, TETSIM_TOUCH_WIDTH doubles:
+ *   [0] TOUCHING  particles that touch at least one slot          [1] MIN_SD    the least sd over all slots and particles, +inf if none
+ *   [2] MIN_SLOT  the first slot whose MIN_SD is below every      [3] SLOTS     the length of the body's list
+ *                 earlier one's (ascending scan with <), or -1
+ *   [4 + 12k ..] slot k, TETSIM_TOUCH_SLOT_WIDTH doubles:
+ *   [0] KIND      0..3                [1] COUNT   touching particles         [2] MIN_SD   the slot's least sd, +inf if none
+ *   [3..5] CENTROID = (S p) / COUNT   [6..8] NORMAL = (S n) / COUNT          [9..11] REL_VEL = (S (v - V)) / COUNT
+ *   S: the sum over the slot's touching particles, v the stored f32 velocity widened, V the collider's velocity; COUNT == 0 gives nine
+ *   zeros.  A slot k >= SLOTS reads KIND -1, MIN_SD +inf and ten zeros.  Counts are reduced as integers and stored as doubles.
+ * REPRODUCIBLE AND POSITION INDEPENDENT, as the observation: a body's particles are cut into chunks of 256 counted from its own first
+ * particle, a chunk is reduced by the fixed tree, the chunks' rows are folded in index order by the same tree; particles that do not
+ * touch contribute 0.0 to the sums; no atomics.  Two calls give the same bits, a body of a batch the bits it gives alone with
+ * tetsim_set_colliders of the same rows.
+ * THE PARTICLE ROW, TETSIM_TOUCH_PARTICLE_WIDTH f32 for each of the handle's particles in the caller's numbering, every value the f64
+ * result rounded once:
+ *   [0] sd of the nearest slot (ascending scan with <: ties go to the lower slot; +inf without a slot or with NaN everywhere)
+ *   [1..3] that slot's n (0 without one)      [4] the slot as a value, or -1      [5] the number of slots the particle touches      [6..7] 0
+ *
+ * Body rows: row b of dst = body b (tetsim_get_batch_layout) at dst + b * row_stride, 8-byte aligned, the stride 0 (packed: 800) or a
+ * multiple of 8 of at least 800.  Particle rows: row i at dst + i * row_stride, 4-byte aligned, the stride 0 (packed: 32) or a multiple
+ * of 4 of at least 32.  Only the rows' own values are written -- not the padding of a wider row, not a byte outside the rows.  THE
+ * STREAM CONTRACT is that of tetsim_observe_bodies_device: the handle's stream waits for caller_stream, the launches (two for the
+ * body rows, one for the particle rows) run behind every substep and every set call enqueued so far, caller_stream waits for them.
+ * Only the handle's first touch call may block: it allocates the scratch of the chunk rows (90 doubles per chunk of 256 particles)
+ * and the rows of the host read and, unless another per-body call made it, uploads the handle's particle chunk table; all of it
+ * counts into TetSimInfo.device_bytes from then on.  tetsim_read_body_touch writes the body rows to host memory,
+ * out[num_bodies * TETSIM_TOUCH_WIDTH], and synchronises.  A handle without colliders is legal: SLOTS 0, MIN_SD +inf, MIN_SLOT -1,
+ * every particle's slot -1.
+ * THE KERNELS.  One workgroup per chunk of 256 particles, which belong to one body: its list arrives by scalar loads (the handle's
+ * list travels as a kernel argument), a lane holds one particle and walks the slots, ten f64 accumulators and a count per slot go
+ * through the tree and leave through the first lane; one workgroup per body folds the chunk rows slot by slot and its first lane
+ * divides.  No scratch memory (94 / 112 / 72 VGPRs for the chunk, finish and particle kernels).  Cost, measured on an MI355X against the
+ * observation on the same batch in the same run (tools/touch_cost.py, profiles/touch_cost.txt): 64 Dragons (78,976
+ * particles) in one batch, per call, the observation 41.5 us; the body rows 32.5 us with no slot (x0.78), 56.1 us with four slots per
+ * body (x1.35), 79.2 us with eight (x1.91) -- about 6 us per slot; the particle rows 28.2, 30.1 and 33.1 us (x0.68, x0.72, x0.80).
+ *
+ * Every error is found before anything is enqueued and leaves `dst` as it was.  TETSIM_EINVAL: a NULL handle, dst or out; a margin
+ * that is not finite; a dst that is not aligned as above; such a row_stride; a dst that hipPointerGetAttributes does not report as
+ * device memory of the handle's device, or whose rows do not fit the allocation it points into.  TETSIM_ESTATE: a partitioned body.
+ * Out of scope: contact forces or impulses recorded inside the substep; contacts between bodies; per-body margins; a body mask;
+ * partitioned bodies; a Node binding; gradients. */
+#define TETSIM_TOUCH_WIDTH 100           /* doubles per body row: 800 bytes */
+#define TETSIM_TOUCH_SLOT_WIDTH 12       /* doubles per slot of a body row */
+#define TETSIM_TOUCH_PARTICLE_WIDTH 8    /* floats per particle row: 32 bytes */
+enum { TETSIM_TOUCH_TOUCHING = 0, TETSIM_TOUCH_MIN_SD = 1, TETSIM_TOUCH_MIN_SLOT = 2, TETSIM_TOUCH_SLOTS = 3,
+       TETSIM_TOUCH_SLOT0 = 4 /* slot k at SLOT0 + k * TETSIM_TOUCH_SLOT_WIDTH */ };
+enum { TETSIM_TOUCH_SLOT_KIND = 0, TETSIM_TOUCH_SLOT_COUNT = 1, TETSIM_TOUCH_SLOT_MIN_SD = 2, TETSIM_TOUCH_SLOT_CENTROID = 3 /*..5*/,
+       TETSIM_TOUCH_SLOT_NORMAL = 6 /*..8*/, TETSIM_TOUCH_SLOT_REL_VEL = 9 /*..11*/ };
+enum { TETSIM_TOUCH_P_SD = 0, TETSIM_TOUCH_P_NORMAL = 1 /*..3*/, TETSIM_TOUCH_P_SLOT = 4, TETSIM_TOUCH_P_TOUCHES = 5,
+       TETSIM_TOUCH_P_RESERVED = 6 /*..7, written as 0*/ };
+/* row b of dst (DEVICE memory, f64) = body b of the handle; ordered against caller_stream exactly as tetsim_observe_bodies_device */
+int tetsim_touch_bodies_device(tetsim_handle h, double margin, void *dst, uint64_t row_stride, void *caller_stream);
+/* the same rows into host memory [num_bodies * TETSIM_TOUCH_WIDTH]; synchronises */
+int tetsim_read_body_touch(tetsim_handle h, double margin, double *out);
+/* row i of dst (DEVICE memory, f32) = particle i of the caller's numbering; ordered against caller_stream likewise */
+int tetsim_touch_particles_device(tetsim_handle h, double margin, void *dst, uint64_t row_stride, void *caller_stream);
 
 /* --- range sensors on the device: per-body ray casts from device memory ------------------------- */
 

@@ -33,6 +33,12 @@ OBS_WIDTH = 20
 POSE_WIDTH, POSE_SWEEPS = 48, 5
 (POSE_MASS, POSE_MX, POSE_MV, POSE_A, POSE_L0, POSE_G, POSE_Q0, POSE_COM, POSE_VCOM, POSE_Q, POSE_OMEGA, POSE_L, POSE_RESIDUAL, POSE_GAP,
  POSE_RESERVED) = 0, 1, 4, 7, 16, 19, 25, 26, 29, 32, 36, 39, 42, 43, 44
+# doubles of a body's row of tetsim_touch_bodies_device and of a slot in it, floats of a particle's row of tetsim_touch_particles_device,
+# and where each quantity starts: in the body row (slot k at TOUCH_SLOT0 + k * TOUCH_SLOT_WIDTH), in a slot, in a particle row
+TOUCH_WIDTH, TOUCH_SLOT_WIDTH, TOUCH_PARTICLE_WIDTH = 100, 12, 8
+TOUCH_TOUCHING, TOUCH_MIN_SD, TOUCH_MIN_SLOT, TOUCH_SLOTS, TOUCH_SLOT0 = 0, 1, 2, 3, 4
+TOUCH_SLOT_KIND, TOUCH_SLOT_COUNT, TOUCH_SLOT_MIN_SD, TOUCH_SLOT_CENTROID, TOUCH_SLOT_NORMAL, TOUCH_SLOT_REL_VEL = 0, 1, 2, 3, 6, 9
+TOUCH_P_SD, TOUCH_P_NORMAL, TOUCH_P_SLOT, TOUCH_P_TOUCHES, TOUCH_P_RESERVED = 0, 1, 4, 5, 6
 # floats of a tet's row of tetsim_tet_strain_device (and where each quantity starts in it), doubles of a body's row of tetsim_body_strain_device
 STRAIN_WIDTH, STRAIN_BODY_WIDTH, STRAIN_SWEEPS = 16, 8, 4
 STRAIN_F, STRAIN_J, STRAIN_DEV, STRAIN_STRETCH, STRAIN_GREEN, STRAIN_RESERVED = 0, 9, 10, 11, 14, 15
@@ -150,6 +156,7 @@ SYMBOLS = [
     "tetsim_snapshot_create", "tetsim_snapshot_capture", "tetsim_snapshot_restore", "tetsim_snapshot_destroy",
     "tetsim_observe_bodies_device", "tetsim_read_body_observations",
     "tetsim_body_poses_device", "tetsim_read_body_poses", "tetsim_prep_pose_table",
+    "tetsim_touch_bodies_device", "tetsim_read_body_touch", "tetsim_touch_particles_device",
     "tetsim_raycast_visual_device", "tetsim_visual_bounding_spheres_device", "tetsim_raycast_visual_bvh_device", "tetsim_prep_bvh",
     "tetsim_tet_strain_device", "tetsim_read_tet_strain", "tetsim_body_strain_device", "tetsim_visual_strain_device", "tetsim_prep_strain_table",
     "tetsim_set_body_grabs", "tetsim_set_body_grabs_device", "tetsim_nearest_particles_device",
@@ -171,7 +178,8 @@ OPTIONAL_SYMBOLS = ("tetsim_set_colliders", "tetsim_raycast_visual", "tetsim_sta
                     "tetsim_set_body_params", "tetsim_set_body_params_device",
                     "tetsim_place_bodies_device", "tetsim_place_bodies",
                     "tetsim_body_poses_device", "tetsim_read_body_poses", "tetsim_prep_pose_table",
-                    "tetsim_raycast_visual_bvh_device", "tetsim_prep_bvh")
+                    "tetsim_raycast_visual_bvh_device", "tetsim_prep_bvh",
+                    "tetsim_touch_bodies_device", "tetsim_read_body_touch", "tetsim_touch_particles_device")
 
 _lib = None
 
@@ -284,6 +292,10 @@ def lib():
         L.tetsim_body_poses_device.argtypes = [H, C.c_void_p, C.c_uint64, C.c_void_p]
         L.tetsim_read_body_poses.argtypes = [H, dp]
         L.tetsim_prep_pose_table.argtypes = [fp, u32, ip, u32, C.POINTER(u32), C.POINTER(u32), u32, dbl, C.c_void_p, dp]
+    if hasattr(L, "tetsim_touch_bodies_device"):   # (additive to ABI 5; dst and the stream travel as plain addresses)
+        L.tetsim_touch_bodies_device.argtypes = [H, dbl, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.tetsim_read_body_touch.argtypes = [H, dbl, dp]
+        L.tetsim_touch_particles_device.argtypes = [H, dbl, C.c_void_p, C.c_uint64, C.c_void_p]
     L.tetsim_profile.argtypes = [H, u32, dbl, PP, C.POINTER(TetSimProfile)]
     L.tetsim_time_kernels.argtypes = [H, u32, dbl, PP, C.POINTER(TetSimProfile)]
     L.tetsim_time_step_n.argtypes = [H, u32, dbl, PP, dp]

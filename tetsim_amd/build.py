@@ -43,6 +43,8 @@ UNITS = {
     "strain.hip": ["-ffp-contract=off"],
     # f64 moments whose error bound counts every rounding, and a derived procedure of + - * / sqrt that tests/pose_ref.py reproduces bit for bit
     "pose.hip": ["-ffp-contract=off"],
+    # signed distances and normals in f64, each operation rounded on its own: tests/touch_ref.py reproduces every row bit for bit in numpy
+    "touch.hip": ["-ffp-contract=off"],
     # the nearest query's f64 squared distance is tetsim_nearest_particle's, compared bit for bit: every multiply and add rounded on its own
     "body_grabs.hip": ["-ffp-contract=off"],
     # the set kernel normalises plane normals and box axes in f64 exactly as tetsim_set_colliders does on the host: every operation rounded on its own

@@ -15,6 +15,8 @@
 //                      gradient, stretches, Green strain -- one lane per tet over a constant 64-byte record
 //   pose.hip           per-body pose on the device (tetsim_body_poses_device): mass moments over a constant per-particle table, the best-fit
 //                      rotation (Horn's quaternion by a fixed Jacobi procedure), angular velocity and momentum
+//   touch.hip          touch sensing on the device (tetsim_touch_bodies_device / _particles_device): signed distance and normal of every
+//                      particle against its body's colliders, per body and slot or per particle -- read-only, over the particle chunks
 //   body_grabs.hip     one held particle per body of a batch, set from host or device memory (tetsim_set_body_grabs / _device): the table the
 //                      particle passes read; the nearest particle of every body on the device (tetsim_nearest_particles_device)
 //   body_params.hip   physics parameters per body of a batch, set from host or device memory (tetsim_set_body_params / _device)
@@ -205,6 +207,14 @@ struct PoseDev {
     bool ready = false;
 };
 
+// tetsim_touch_bodies_device / tetsim_read_body_touch / tetsim_touch_particles_device (touch.hip): the scratch of a handle's touch calls,
+// made by its first one
+struct TouchDev {
+    double* partial = nullptr;         // [particle chunks][90] chunk rows
+    double* rows = nullptr;            // [bodies][TETSIM_TOUCH_WIDTH]: the device side of tetsim_read_body_touch
+    bool ready = false;
+};
+
 }  // namespace tetsim
 
 using namespace tetsim;  // (private header of the ABI's own translation units; the handle type lives in the global namespace)
@@ -386,6 +396,7 @@ struct tetsim_body {
     ObsDev obs;                    // tetsim_observe_bodies_device / tetsim_read_body_observations (observe.hip)
     StrainDev strain;              // tetsim_tet_strain_device / tetsim_body_strain_device / tetsim_visual_strain_device (strain.hip)
     PoseDev pose;                  // tetsim_body_poses_device / tetsim_read_body_poses (pose.hip)
+    TouchDev touch;                // tetsim_touch_bodies_device / tetsim_read_body_touch / tetsim_touch_particles_device (touch.hip)
     double* d_best = nullptr; uint32_t* d_best_id = nullptr;  // tetsim_start_grab candidates
     // tetsim_raycast_visual / tetsim_read_visual_bounding_sphere (query_kernels.hip): allocated by the first query, grown on demand
     uint32_t* d_sphere = nullptr;

@@ -617,6 +617,42 @@ class SoftBodyHIP:
         capi.check(self._L.tetsim_read_body_poses(self._h, out.ctypes.data_as(C.POINTER(C.c_double))), self._h)
         return out
 
+    # -- touch sensing (include/tetsim.h: tetsim_touch_bodies_device / _particles_device): the bodies' contacts with their colliders --
+    def touchBodies(self, margin, out=None, stream=None):
+        """torch.float64 [num_bodies, 100] on the handle's device: per body the particles that touch a collider of the list its substeps
+        walk (signed distance below `margin`, metres), the least distance and its slot, the list's length, and per slot its kind, the
+        touching particles, the least distance, the centroid, the mean normal and the mean velocity relative to the collider (columns:
+        _capi.TOUCH_*; definitions: include/tetsim.h).  Read-only.  `out` and `stream` as in observeBodies: no host copy, no
+        synchronisation, the tensor allocated once and reused unless `out` supplies it."""
+        import torch
+        dev, s = self._torch_stream(torch, stream)
+        n = self.info.num_bodies
+        out = self._strain_out(torch, dev, "touch", out, n, capi.TOUCH_WIDTH, torch.float64)
+        capi.check(self._L.tetsim_touch_bodies_device(self._h, float(margin), out.data_ptr(), 8 * out.stride(0) if n > 1 else 0, s), self._h)
+        return out
+
+    def bodyTouch(self, margin):
+        """touchBodies(margin) on the host: a numpy float64 [num_bodies, 100] array.  Synchronises."""
+        out = np.empty((self.info.num_bodies, capi.TOUCH_WIDTH), dtype=np.float64)
+        capi.check(self._L.tetsim_read_body_touch(self._h, float(margin), out.ctypes.data_as(C.POINTER(C.c_double))), self._h)
+        return out
+
+    def touchParticlesDevice(self, margin, out=None, stream=None):
+        """torch.float32 [num_particles, 8] on the handle's device, row i = particle i of the caller's numbering: the signed distance to
+        the nearest collider of its body's list, that collider's outward normal, its slot (-1: none) and the number of slots the
+        particle touches (columns: _capi.TOUCH_P_*).  `margin`, `out` and `stream` as in touchBodies."""
+        import torch
+        dev, s = self._torch_stream(torch, stream)
+        n, w = self.info.owned_particles, capi.TOUCH_PARTICLE_WIDTH
+        if out is None:
+            out = self._export_cache.get("touch_particles")
+            if out is None:
+                out = self._export_cache["touch_particles"] = torch.empty((n, w), dtype=torch.float32, device=dev)
+        else:
+            _check_rows(torch, out, dev, n, w, "out")
+        capi.check(self._L.tetsim_touch_particles_device(self._h, float(margin), out.data_ptr(), 4 * out.stride(0) if n > 1 else 0, s), self._h)
+        return out
+
     # -- per-tet strain (include/tetsim.h: tetsim_tet_strain_device / _body_strain_device / _visual_strain_device) -----------------
     def _strain_out(self, torch, dev, key, out, n, w, dtype):
         """The cached tensor of a strain call, or the caller's `out` behind the checks of observeBodies."""
