@@ -408,7 +408,7 @@ int tetsim_nearest_particle(tetsim_handle h, const float xyz[3], int32_t *global
  * belongs to the last completed substep; it synchronises once and changes no solver state.
  * Out of scope: partitioned bodies; all hits along a ray; back-side or double-side materials; the edge wireframe's LineSegments;
  * an acceleration structure behind THIS call (brute force: every ray against every triangle; the per-body device casts have one:
- * tetsim_raycast_visual_bvh_device); closest-point queries. */
+ * tetsim_raycast_visual_bvh_device); closest-point queries (tetsim_closest_visual_device, below, answers them). */
 typedef struct TetSimRay    { double origin[3], direction[3], near, far; } TetSimRay;       /* far may be +inf */
 typedef struct TetSimRayHit { int32_t hit, body, triangle, reserved; double distance, point[3]; } TetSimRayHit;
 int tetsim_raycast_visual(tetsim_handle h, const TetSimRay *rays, uint32_t count, TetSimRayHit *hits);
@@ -1170,6 +1170,76 @@ int tetsim_raycast_visual_bvh_device(tetsim_handle h,
         uint32_t count,
         void *hits,           uint64_t hit_stride,
         void *caller_stream);
+
+/* --- closest-point queries through the refitted tree -------------------------------------------- */
+
+/* How far is this point from that body's surface, and where on the surface is the nearest point: what a distance reward, a proximity
+ * sensor, a marker fixed to the surface and contact generation for another engine ask.  Queries, the body each belongs to and the
+ * records live in the caller's DEVICE memory, nothing synchronises the host, and a query is answered by ITS OWN body through the tree
+ * of tetsim_raycast_visual_bvh_device.  An ADDITIVE extension of ABI version 5 (TETSIM_ABI_VERSION is unchanged; no existing struct
+ * changed): look the symbols up.  The stream contract, the pointer, stride and allocation checks, "every error is found before anything
+ * is enqueued and leaves `out` as it was", "count == 0 succeeds" and the TETSIM_ESTATE cases are those of
+ * tetsim_raycast_visual_bvh_device, word for word, with queries / query_body / out in the places of rays / ray_body / hits (strides:
+ * 0 = packed 32 / 64, else a multiple of 8 of at least that).  Only the 64 bytes of a record are written.
+ *
+ * THE DEFINITION is brute force and does not mention the tree (tests/closest_ref.py is the definition in numpy).  f64, every operation
+ * rounded separately, sums left to right.  queries: count TetSimPointQuery records; query_body: count int32, packed, or NULL.
+ *   A query is INVALID if a component of its point is not finite, its max_distance is NaN or < 0 (+infinity is allowed), or its
+ *     query_body value is outside [0, num_bodies): found = TETSIM_CLOSEST_INVALID, body = triangle = region = -1 and zeros elsewhere.
+ *     It disturbs no other query.  (The host variant sees its queries and refuses such a one with TETSIM_EINVAL.)
+ *   The triangles: with query_body, those whose rows belong to body b = query_body[i], and the bounding sphere of b's visual rows; without,
+ *     all of them and the sphere of the whole mesh -- the spheres of the ray casts.  A single body accepts query_body values of 0.
+ *   Per triangle (a, b, c: the f32 corners taken as doubles; p: the point) the closest point q is three.js r160
+ *     Triangle.closestPointToPoint, in the order of its operations:  ab = b - a, ac = c - a, ap = p - a, d1 = ab.ap, d2 = ac.ap;
+ *     d1 <= 0 && d2 <= 0: q = a.  bp = p - b, d3 = ab.bp, d4 = ac.bp;  d3 >= 0 && d4 <= d3: q = b.  vc = d1*d4 - d3*d2;
+ *     vc <= 0 && d1 >= 0 && d3 <= 0: v = d1 / (d1 - d3), q = a + ab*v.  cp = p - c, d5 = ab.cp, d6 = ac.cp;  d6 >= 0 && d5 <= d6: q = c.
+ *     vb = d5*d2 - d1*d6;  vb <= 0 && d2 >= 0 && d6 <= 0: w = d2 / (d2 - d6), q = a + ac*w.  va = d3*d6 - d5*d4;
+ *     va <= 0 && d4 - d3 >= 0 && d5 - d6 >= 0: w = (d4 - d3) / ((d4 - d3) + (d5 - d6)), q = b + (c - b)*w.  Otherwise
+ *     denom = 1 / ((va + vb) + vc), v = vb*denom, w = vc*denom, q = (a + ab*v) + ac*w.  (x.y = x0*y0 + x1*y1 + x2*y2.)
+ *   region and (v, w), with q = a + v*ab + w*ac in exact terms:  1 vertex a (0, 0);  2 vertex b (1, 0);  3 vertex c (0, 1);  4 edge ab
+ *     (v, 0);  5 edge ac (0, w);  6 edge bc (1.0 - w, w), w the method's;  0 the face (v, w).
+ *   d2 = dot(p - q, p - q).
+ *   Padding:  e = 2^-20 * (radius + sqrt(dot(p - centre, p - centre))), centre and radius of the sphere above.
+ *   Box bound of a triangle:  lo_k / hi_k = the smallest / largest of the three corners' component k;  L_k = lo_k - e, H_k = hi_k + e;
+ *     g_k = the largest of L_k - p_k, p_k - H_k and 0;  lb = g_0*g_0 + g_1*g_1 + g_2*g_2.
+ *   A triangle COUNTS iff lb <= d2 && d2 <= max_distance * max_distance.  (A zero-area triangle whose q is NaN never counts.)
+ *   The record is the smallest (d2, triangle) among the counting triangles, in lexicographic order: found = 1, distance = sqrt(d2);
+ *     point, region, v, w are that triangle's; triangle is the position in THIS handle's list; body is the query's body, or without
+ *     query_body the body of the triangle's first row.  When none counts: found = 0, body = triangle = region = -1, zeros elsewhere.
+ * Why a tree reproduces this bit for bit: every comparison above is false for a NaN, and lb is monotone in the box in IEEE arithmetic -- a
+ * node's f32 box that contains a triangle's box has lb_node <= lb_triangle (same formulas, same e).  The traversal skips a node only if
+ * it is empty, lb_node > max_distance^2, or a best exists and lb_node > d2_best -- strictly: a node with lb_node == d2_best is entered,
+ * because a lower triangle index may tie.  At a leaf every triangle is tested with the box of its OWN corners.  The running best is
+ * never below the winner's d2 and the winner counts (lb <= d2), so no ancestor of the winner is skipped, whatever the visit order and
+ * the tree's shape.  (lb <= d2 holds for every triangle in exact arithmetic -- q lies in the triangle's box --, and e dwarfs the
+ * rounding: the predicate removes nothing, tests/test_closest_cpu.py counts 0; it is there so that the argument needs no error analysis.)
+ *
+ * THE TREE is that of tetsim_raycast_visual_bvh_device: built once per handle by its first tree call -- ray cast or closest point,
+ * whichever comes first; only that call may block --, refitted at EVERY call on the handle's stream behind the skinning and the spheres.
+ * What the first call allocates counts into TetSimInfo.device_bytes from then on and does not depend on count.  THE KERNEL: one lane per
+ * query, 256 per workgroup, stackless as the ray cast's; both children's boxes in one 48-byte read, the child with the smaller bound
+ * first; the lanes of a wave reach their leaves together before a leaf's four triangles are gathered and tested.  With query_body ==
+ * NULL a lane walks the bodies' trees, lowest body first, carrying its best.  Queries need not be grouped by body.  No scratch memory,
+ * 138 VGPRs (three waves a SIMD, as the ray cast).  Cost, measured on an MI355X beside the ray cast through the same tree in the same run
+ * (tools/closest_cost.py, profiles/closest_cost.txt): 64 Dragons (59,657 triangles each) in one batch, 65,536 queries
+ * scattered within one bounding radius of their bodies' surfaces and shuffled over the bodies, 4.05 ms per call against 1.95 ms for
+ * as many rays (x2.08); the refit is 0.18 ms of it (4.4 %); a query tests 365 boxes and 185 triangles on average.
+ *
+ * tetsim_closest_visual: the same records for host arrays -- staged through buffers that grow on demand, the same kernel, one
+ * synchronisation.  TETSIM_EINVAL for a query the device variant would mark invalid (the message names the first).
+ * Out of scope: an inside / outside sign (it needs pseudo-normals; `region` tells the caller when the face normal can be trusted: 0);
+ * the k nearest; queries against the tet mesh itself; a Node binding; partitioned bodies; gradients. */
+typedef struct TetSimPointQuery { double point[3], max_distance; } TetSimPointQuery;          /* 32 B; max_distance may be +inf */
+typedef struct TetSimClosest    { int32_t found, body, triangle, region;
+                                  double distance, point[3], v, w; } TetSimClosest;           /* 64 B */
+#define TETSIM_CLOSEST_INVALID (-1)   /* TetSimClosest.found of a query the device refused */
+int tetsim_closest_visual_device(tetsim_handle h,
+        const void *queries,  uint64_t query_stride,   /* DEVICE; stride 0 = packed 32, else a multiple of 8, >= 32 */
+        const void *query_body,                        /* DEVICE: count int32, or NULL */
+        uint32_t count,
+        void *out,            uint64_t out_stride,     /* DEVICE; stride 0 = packed 64, else a multiple of 8, >= 64 */
+        void *caller_stream);
+int tetsim_closest_visual(tetsim_handle h, const TetSimPointQuery *queries, const int32_t *query_body, uint32_t count, TetSimClosest *out);  /* host arrays; synchronises */
 
 /* --- per-tet strain on the device: deformation gradient, volume ratio, principal stretches ------ */
 

@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get("TETSIM_HIP_LIB") or os.path.join(_HERE, "libtetsim_hi
 
 OK, EINVAL, ENODEVICE, EHIP, ENOMEM, ECOMM, ESTATE = range(7)
 RAY_INVALID = -1   # TetSimRayHit.hit of a ray tetsim_raycast_visual_device refused
+CLOSEST_INVALID = -1   # TetSimClosest.found of a query tetsim_closest_visual_device refused
 SOLVER_POLAR_JACOBI, SOLVER_NEOHOOKEAN_GS = 0, 1
 PRECISE, FAST = 0, 1
 ORDER_ORIGINAL, ORDER_COLOURED, ORDER_CLUSTERED = 0, 1, 2
@@ -131,6 +132,15 @@ class TetSimRayHit(C.Structure):
                 ("point", C.c_double * 3)]
 
 
+class TetSimPointQuery(C.Structure):
+    _fields_ = [("point", C.c_double * 3), ("max_distance", C.c_double)]
+
+
+class TetSimClosest(C.Structure):
+    _fields_ = [("found", C.c_int32), ("body", C.c_int32), ("triangle", C.c_int32), ("region", C.c_int32), ("distance", C.c_double),
+                ("point", C.c_double * 3), ("v", C.c_double), ("w", C.c_double)]
+
+
 class TetSimDeviceField(C.Structure):
     _fields_ = [("field", C.c_int32), ("reserved", C.c_int32), ("dst", C.c_void_p), ("row_stride", C.c_uint64)]
 
@@ -158,6 +168,7 @@ SYMBOLS = [
     "tetsim_body_poses_device", "tetsim_read_body_poses", "tetsim_prep_pose_table",
     "tetsim_touch_bodies_device", "tetsim_read_body_touch", "tetsim_touch_particles_device",
     "tetsim_raycast_visual_device", "tetsim_visual_bounding_spheres_device", "tetsim_raycast_visual_bvh_device", "tetsim_prep_bvh",
+    "tetsim_closest_visual_device", "tetsim_closest_visual",
     "tetsim_tet_strain_device", "tetsim_read_tet_strain", "tetsim_body_strain_device", "tetsim_visual_strain_device", "tetsim_prep_strain_table",
     "tetsim_set_body_grabs", "tetsim_set_body_grabs_device", "tetsim_nearest_particles_device",
     "tetsim_set_body_colliders", "tetsim_set_body_colliders_device",
@@ -179,6 +190,7 @@ OPTIONAL_SYMBOLS = ("tetsim_set_colliders", "tetsim_raycast_visual", "tetsim_sta
                     "tetsim_place_bodies_device", "tetsim_place_bodies",
                     "tetsim_body_poses_device", "tetsim_read_body_poses", "tetsim_prep_pose_table",
                     "tetsim_raycast_visual_bvh_device", "tetsim_prep_bvh",
+                    "tetsim_closest_visual_device", "tetsim_closest_visual",
                     "tetsim_touch_bodies_device", "tetsim_read_body_touch", "tetsim_touch_particles_device")
 
 _lib = None
@@ -269,6 +281,9 @@ def lib():
     if hasattr(L, "tetsim_raycast_visual_bvh_device"):   # (additive to ABI 5; the arguments of tetsim_raycast_visual_device)
         L.tetsim_raycast_visual_bvh_device.argtypes = [H, C.c_void_p, C.c_uint64, C.c_void_p, u32, C.c_void_p, C.c_uint64, C.c_void_p]
         L.tetsim_prep_bvh.argtypes = [fp, u32, ip, u32, ip, u32] + [C.POINTER(u32)] * 5
+    if hasattr(L, "tetsim_closest_visual_device"):   # (additive to ABI 5; queries, bodies, records and the stream travel as plain addresses)
+        L.tetsim_closest_visual_device.argtypes = [H, C.c_void_p, C.c_uint64, C.c_void_p, u32, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.tetsim_closest_visual.argtypes = [H, C.c_void_p, C.c_void_p, u32, C.c_void_p]
     if hasattr(L, "tetsim_tet_strain_device"):   # (additive to ABI 5; dst and the stream travel as plain addresses)
         L.tetsim_tet_strain_device.argtypes = [H, C.c_void_p, C.c_uint64, C.c_void_p]
         L.tetsim_read_tet_strain.argtypes = [H, fp]

@@ -79,6 +79,8 @@ UNITS = {
     "query_kernels.hip": ["-ffp-contract=off"],
     # the slab test of the refitted tree is defined in f64 with every operation rounded on its own, and shares tri_test with the unit above
     "query_bvh.hip": ["-ffp-contract=off"],
+    # closest points through that tree: three.js's closestPointToPoint and the box bound in f64, each operation rounded on its own (tests/closest_ref.py)
+    "query_closest.hip": ["-ffp-contract=off"],
     "build_info.cpp": ["-x", "hip"],
 }
 HEADERS = ["body.h", "body_reduce.h", "dev_common.h", "dev_store.h", "host_prep.h", "mesh_file.h", "pj_kernels.inc", "pj_math.inc", "pj_lab.h", "pj_blocked_lab.inc", "nh_kernels.inc", "collide.h", "query_device.h", "query_rays.h", os.path.join("..", "..", "include", "tetsim.h")]

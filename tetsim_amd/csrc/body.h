@@ -412,6 +412,9 @@ struct tetsim_body {
     // tetsim_raycast_visual_bvh_device (query_bvh.hip): the tree over every body's triangles, its topology built by the first such call
     BvhDev bvh;
     bool bvh_ready = false;
+    // tetsim_closest_visual (query_closest.hip): where the host variant's queries, bodies and records wait, grown on demand
+    PointQueryIn* d_point_queries = nullptr; int32_t* d_point_bodies = nullptr; ClosestOut* d_closest = nullptr;
+    size_t point_query_cap = 0, point_body_cap = 0, closest_cap = 0;
 
     // NEOHOOKEAN_GS
     NHDev nh;

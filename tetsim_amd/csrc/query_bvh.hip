@@ -24,10 +24,6 @@ namespace {
 constexpr uint32_t kFoldLeaves = 1u << kBvhFoldLevels;
 static_assert(kFoldLeaves == 256u, "a lane of the fold kernel is one leaf");
 
-__device__ inline void box_add(float lo[3], float hi[3], const float4 p) {
-    const float v[3] = {p.x, p.y, p.z};
-    for (int k = 0; k < 3; k++) { lo[k] = v[k] < lo[k] ? v[k] : lo[k]; hi[k] = v[k] > hi[k] ? v[k] : hi[k]; }
-}
 __device__ inline BvhBox box_join(const BvhBox& a, const BvhBox& b) {
     BvhBox o;
     for (int k = 0; k < 3; k++) { o.lo[k] = b.lo[k] < a.lo[k] ? b.lo[k] : a.lo[k]; o.hi[k] = b.hi[k] > a.hi[k] ? b.hi[k] : a.hi[k]; }

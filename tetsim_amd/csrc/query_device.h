@@ -93,4 +93,27 @@ void query_launch_bvh_refit(hipStream_t s, const QueryDev& q, const QueryBodiesD
 // The cast: q.sphere (io.ray_body null) or b.spheres (else) and the boxes must be current.
 void query_launch_cast_bvh(hipStream_t s, const QueryDev& q, const QueryBodiesDev& b, const BvhDev& v, const CastIo& io);
 
+// ---- closest-point queries through the same tree (include/tetsim.h: tetsim_closest_visual_device; query_closest.hip) ----------------
+struct PointQueryIn { double p[3], max_distance; };                                                   // = TetSimPointQuery
+struct ClosestOut { int32_t found, body, triangle, region; double distance, point[3], v, w; };      // = TetSimClosest
+// Why a query is refused, 0 = it is good: the host variant turns the code into TETSIM_EINVAL and a message, the device into
+// TETSIM_CLOSEST_INVALID.
+enum : int { kPointGood = 0, kPointNonFinite, kPointNanLimit, kPointNegativeLimit };
+__host__ __device__ inline int point_query_defect(const double p[3], double max_distance) {
+    for (int k = 0; k < 3; k++)
+        if (!(p[k] - p[k] == 0.0)) return kPointNonFinite;   // (x - x: NaN for an infinity or a NaN)
+    if (max_distance != max_distance) return kPointNanLimit;
+    if (max_distance < 0.0) return kPointNegativeLimit;
+    return kPointGood;
+}
+// the caller's records: query i at queries + i * query_stride, its body at query_body[i] (null: the whole mesh), its record at out + i * out_stride
+struct ClosestIo {
+    const char* queries; uint64_t query_stride;
+    const int32_t* query_body;
+    char* out; uint64_t out_stride;
+    uint32_t count;
+};
+// The queries: q.sphere (io.query_body null) or b.spheres (else) and the boxes must be current.
+void query_launch_closest_bvh(hipStream_t s, const QueryDev& q, const QueryBodiesDev& b, const BvhDev& v, const ClosestIo& io);
+
 }  // namespace tetsim

@@ -28,6 +28,12 @@ __host__ __device__ inline void sphere_centre(const uint32_t* w, double c[3]) {
     }
 }
 
+// a box grown by a point: the exact f32 min / max (the refit's leaves, a triangle's own box in both traversals)
+__device__ inline void box_add(float lo[3], float hi[3], const float4 p) {
+    const float v[3] = {p.x, p.y, p.z};
+    for (int k = 0; k < 3; k++) { lo[k] = v[k] < lo[k] ? v[k] : lo[k]; hi[k] = v[k] > hi[k] ? v[k] : hi[k]; }
+}
+
 __device__ inline double dot3(const double* u, const double* v) { return u[0] * v[0] + u[1] * v[1] + u[2] * v[2]; }
 
 // Mesh.raycast up to the triangles: the bounding-sphere cull (ray recast by `near`, direction as given), then the ray in the

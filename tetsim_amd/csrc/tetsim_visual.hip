@@ -589,6 +589,85 @@ int tetsim_raycast_visual_bvh_device(tetsim_handle h, const void* rays, uint64_t
     return raycast_device(h, rays, ray_stride, ray_body, count, hits, hit_stride, caller_stream, true);
 }
 
+// ---- closest-point queries through the same tree (query_closest.hip); the definition: include/tetsim.h ------------------------------
+namespace {
+static_assert(sizeof(TetSimPointQuery) == sizeof(PointQueryIn) && sizeof(TetSimClosest) == sizeof(ClosestOut), "the ABI's query records are the kernel's records");
+
+// what tetsim_closest_visual_device checks before it enqueues anything, the list of tetsim_raycast_visual_bvh_device; *io: the resolved records
+int closest_check(tetsim_handle h, const void* queries, uint64_t query_stride, const void* query_body, uint32_t count, void* out, uint64_t out_stride, ClosestIo* io) {
+    if (count && (!queries || !out)) return fail(h, TETSIM_EINVAL, "null argument");
+    constexpr uint64_t query_row = sizeof(TetSimPointQuery), out_row = sizeof(TetSimClosest);
+    if (!record_stride_ok(query_stride, query_row, 8u)) return fail(h, TETSIM_EINVAL, "query_stride must be 0 or a multiple of 8 of at least 32");
+    if (!record_stride_ok(out_stride, out_row, 8u)) return fail(h, TETSIM_EINVAL, "out_stride must be 0 or a multiple of 8 of at least 64");
+    if (int rc = check_query_state(h, true)) return rc;
+    if (query_body && h->tri_spans_bodies)
+        return fail(h, TETSIM_ESTATE, "a triangle of the visual mesh has rows of different bodies: it belongs to no body's own surface (query without query_body)");
+    io->queries = static_cast<const char*>(queries); io->query_stride = query_stride ? query_stride : query_row;
+    io->query_body = static_cast<const int32_t*>(query_body);
+    io->out = static_cast<char*>(out); io->out_stride = out_stride ? out_stride : out_row;
+    io->count = count;
+    return 0;
+}
+
+// behind the checks: the tables and the tree (only a handle's first tree call blocks), then skinning, spheres, refit and the queries on the handle's stream
+int closest_enqueue(tetsim_handle h, const ClosestIo& io, void* caller_stream) {
+    if (int rc = ensure_triangle_tables(h)) return rc;
+    if (int rc = ensure_bvh(h)) return rc;
+    return on_caller_stream(h, caller_stream, [&]() -> int {
+        QueryDev q;
+        if (int rc = skin_for_query(h, &q)) return rc;
+        if (io.query_body) query_launch_body_spheres(h->stream, q, h->qbodies);
+        else query_launch_sphere(h->stream, q);
+        query_launch_bvh_refit(h->stream, q, h->qbodies, h->bvh);
+        query_launch_closest_bvh(h->stream, q, h->qbodies, h->bvh, io);
+        return launched(h);
+    });
+}
+}  // namespace
+
+int tetsim_closest_visual_device(tetsim_handle h, const void* queries, uint64_t query_stride, const void* query_body, uint32_t count, void* out,
+                                 uint64_t out_stride, void* caller_stream) {
+    if (!h) return TETSIM_EINVAL;
+    ClosestIo io;
+    if (int rc = closest_check(h, queries, query_stride, query_body, count, out, out_stride, &io)) return rc;
+    if (count == 0) return 0;
+    if (int rc = device_call_guard(h)) return rc;
+    if (int rc = check_device_records(h, queries, io.query_stride, count, sizeof(TetSimPointQuery), 8u, "queries")) return rc;
+    if (int rc = check_device_records(h, out, io.out_stride, count, sizeof(TetSimClosest), 8u, "out")) return rc;
+    if (query_body) { if (int rc = check_device_records(h, query_body, 4u, count, 4u, 4u, "query_body")) return rc; }
+    // ---- every argument is good: from here on only allocation and HIP itself can fail
+    return closest_enqueue(h, io, caller_stream);
+}
+
+// host arrays: staged through buffers that grow on demand, the same kernel, then a synchronisation; a query the host can see is bad is refused
+int tetsim_closest_visual(tetsim_handle h, const TetSimPointQuery* queries, const int32_t* query_body, uint32_t count, TetSimClosest* out) {
+    if (!h) return TETSIM_EINVAL;
+    ClosestIo io;
+    if (int rc = closest_check(h, queries, 0u, query_body, count, out, 0u, &io)) return rc;
+    for (uint32_t i = 0; i < count; i++) {
+        static const char* const why[] = {"", "non-finite point", "max_distance is NaN", "max_distance < 0"};
+        if (const int defect = point_query_defect(queries[i].point, queries[i].max_distance)) return fail(h, TETSIM_EINVAL, "query " + std::to_string(i) + ": " + why[defect]);
+        if (query_body && (query_body[i] < 0 || static_cast<uint32_t>(query_body[i]) >= h->info.num_bodies))
+            return fail(h, TETSIM_EINVAL, "query " + std::to_string(i) + ": query_body is outside [0, num_bodies)");
+    }
+    if (count == 0) return 0;
+    if (int rc = device_call_guard(h)) return rc;
+    const size_t want = std::max<size_t>(count, 64);
+    int rc;
+    if ((rc = dev_grow(h, &h->d_point_queries, &h->point_query_cap, want)) || (rc = dev_grow(h, &h->d_closest, &h->closest_cap, want)) ||
+        (query_body && (rc = dev_grow(h, &h->d_point_bodies, &h->point_body_cap, want)))) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));   // (a previous call's kernel may still read the staging buffers)
+    HIPCHK(h, hipMemcpy(h->d_point_queries, queries, count * sizeof(PointQueryIn), hipMemcpyHostToDevice));
+    if (query_body) HIPCHK(h, hipMemcpy(h->d_point_bodies, query_body, count * sizeof(int32_t), hipMemcpyHostToDevice));
+    io.queries = reinterpret_cast<const char*>(h->d_point_queries);
+    io.query_body = query_body ? h->d_point_bodies : nullptr;
+    io.out = reinterpret_cast<char*>(h->d_closest);
+    if ((rc = closest_enqueue(h, io, nullptr))) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(out, h->d_closest, count * sizeof(ClosestOut), hipMemcpyDeviceToHost));
+    return 0;
+}
+
 #ifdef TETSIM_BVH_STATS
 // development builds only (tools/raycast_bvh_cost.py): the next tree casts count, per ray, the boxes and the triangles they test into
 // stats [count][2] uint32 in DEVICE memory; NULL turns the counting off again

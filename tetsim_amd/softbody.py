@@ -120,6 +120,28 @@ def rays_tensor(origins, directions, near=0.0, far=np.inf, device="cuda"):
     return torch.from_numpy(rays.view(np.float64).reshape(-1, 8).copy()).to(device)
 
 
+# tetsim_closest_visual's records as numpy sees them (include/tetsim.h: TetSimPointQuery, TetSimClosest)
+POINT_QUERY_DTYPE = np.dtype([("point", "<f8", (3,)), ("max_distance", "<f8")])
+CLOSEST_DTYPE = np.dtype([("found", "<i4"), ("body", "<i4"), ("triangle", "<i4"), ("region", "<i4"), ("distance", "<f8"), ("point", "<f8", (3,)),
+                          ("v", "<f8"), ("w", "<f8")])
+
+
+def make_point_queries(points, max_distance=np.inf):
+    """[n, 3] points, max_distance a scalar or [n] -> TetSimPointQuery records."""
+    p = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    queries = np.empty(len(p), dtype=POINT_QUERY_DTYPE)
+    queries["point"], queries["max_distance"] = p, max_distance
+    return queries
+
+
+def point_queries_tensor(points, max_distance=np.inf, device="cuda"):
+    """make_point_queries on a torch device: the float64 [count, 4] tensor closestPointsDevice reads (columns: point xyz, max_distance --
+    a TetSimPointQuery per row)."""
+    import torch
+    queries = make_point_queries(points, max_distance)
+    return torch.from_numpy(queries.view(np.float64).reshape(-1, 4).copy()).to(device)
+
+
 def place_rows(q, pivot=(0.0, 0.0, 0.0), offset=(0.0, 0.0, 0.0), linear=(0.0, 0.0, 0.0), angular=(0.0, 0.0, 0.0)):
     """float32 [bodies, 16] rows of placeBodies / placeBodiesDevice (include/tetsim.h: TETSIM_PLACE_*): q [bodies, 4] xyzw (any length
     but 0), pivot, offset, linear, angular [bodies, 3] -- each of them may be a single vector for all bodies.  torch.from_numpy(rows)
@@ -862,6 +884,50 @@ class SoftBodyHIP:
                         out.data_ptr() if n else None, out.stride(0) if n > 1 else 0, s), self._h)
         i32, f64 = out.view(torch.int32), out.view(torch.float64)   # (rows of 12 / 6 of them; a strided `out` keeps its row stride)
         return {"hit": i32[:, 0], "body": i32[:, 1], "triangle": i32[:, 2], "distance": f64[:, 2], "point": f64[:, 3:6], "raw": out}
+
+    # -- closest points (include/tetsim.h: tetsim_closest_visual_device / tetsim_closest_visual) --------------------
+    def closestPointsDevice(self, queries, bodies=None, out=None, stream=None):
+        """The nearest point of a body's skinned surface to every query point, from and into device memory, with no host copy and no
+        synchronisation, through the refitted tree of raycastVisualBvhDevice.  queries: torch.float64 [count, 4] on the handle's device
+        (point_queries_tensor: point xyz, max_distance; the rows may be strided); bodies: torch.int32 [count] -- query i is answered by
+        body bodies[i] ALONE, `triangle` counted in this handle's list -- or None: by the whole mesh.  Returns views onto one torch.uint8
+        [count, 64] buffer of TetSimClosest records (`raw`: cached like the export tensors, or `out`, whose rows may be strided): found,
+        body, triangle, region (int32 [count]), distance (float64 [count]), point (float64 [count, 3]), v, w (float64 [count]).  An invalid
+        query or body gets found = _capi.CLOSEST_INVALID instead of an exception.  The handle's first tree call builds the topology on the
+        host and may block.  Valid for work enqueued on `stream` (as in exportTensors) after this returns."""
+        import torch
+        dev, s = self._torch_stream(torch, stream)
+        if (not isinstance(queries, torch.Tensor) or queries.dtype != torch.float64 or queries.device != dev or queries.dim() != 2 or queries.shape[1] != 4
+                or (queries.shape[0] and queries.stride(1) != 1) or (queries.shape[0] > 1 and queries.stride(0) < 4)):
+            raise ValueError("queries must be a float64 tensor on %s of shape (count, 4) with contiguous, non-overlapping rows" % (dev,))
+        n = int(queries.shape[0])
+        if bodies is not None and (not isinstance(bodies, torch.Tensor) or bodies.dtype != torch.int32 or bodies.device != dev
+                                   or tuple(bodies.shape) != (n,) or not bodies.is_contiguous()):
+            raise ValueError("bodies must be a contiguous int32 tensor on %s of shape (%d,)" % (dev, n))
+        if out is None:
+            out = self._export_cache.get("closestPoints")
+            if out is None or out.shape[0] != n:
+                out = self._export_cache["closestPoints"] = torch.empty((n, 64), dtype=torch.uint8, device=dev)
+        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != dev or tuple(out.shape) != (n, 64)
+              or (n and out.stride(1) != 1) or (n > 1 and (out.stride(0) < 64 or out.stride(0) % 8)) or (n and out.data_ptr() % 8)):
+            raise ValueError("out must be a uint8 tensor on %s of shape (%d, 64) with contiguous, non-overlapping, 8-byte aligned rows" % (dev, n))
+        capi.check(self._L.tetsim_closest_visual_device(self._h, queries.data_ptr() if n else None, 8 * queries.stride(0) if n > 1 else 0,
+                                                        bodies.data_ptr() if bodies is not None and n else None, n,
+                                                        out.data_ptr() if n else None, out.stride(0) if n > 1 else 0, s), self._h)
+        i32, f64 = out.view(torch.int32), out.view(torch.float64)   # (rows of 16 / 8 of them; a strided `out` keeps its row stride)
+        return {"found": i32[:, 0], "body": i32[:, 1], "triangle": i32[:, 2], "region": i32[:, 3], "distance": f64[:, 2], "point": f64[:, 3:6],
+                "v": f64[:, 6], "w": f64[:, 7], "raw": out}
+
+    def closestPoints(self, points, max_distance=np.inf, bodies=None):
+        """closestPointsDevice for host arrays: points [n, 3], max_distance a scalar or [n], bodies [n] int or None -> a structured array
+        (CLOSEST_DTYPE).  Synchronises; an invalid query raises TetSimError(EINVAL)."""
+        queries = make_point_queries(points, max_distance)
+        b = None if bodies is None else np.ascontiguousarray(bodies, dtype=np.int32)
+        if b is not None and b.shape != (len(queries),):
+            raise ValueError("bodies must have one entry per point")
+        out = np.zeros(len(queries), dtype=CLOSEST_DTYPE)
+        capi.check(self._L.tetsim_closest_visual(self._h, queries.ctypes.data, None if b is None else b.ctypes.data, len(queries), out.ctypes.data), self._h)
+        return out
 
     def visualBoundingSpheresDevice(self, out=None, stream=None):
         """torch.float64 [num_bodies, 4] on the handle's device: (centre x, y, z, radius) of every body's visual rows -- what
