@@ -1453,6 +1453,21 @@ int tetsim_prep_clusters(const int32_t *tets, uint32_t nt, uint32_t nv, int32_t 
 int tetsim_prep_tiles(const float *verts, uint32_t nv, const int32_t *tets, uint32_t nt, const uint32_t *body_first_tet,
                       const uint32_t *body_first_vert, uint32_t bodies, int32_t *tile_tets, uint32_t *tile_off,
                       uint8_t *corner_slot, uint32_t *num_tiles);
+/* The tables behind a tile's fixed reduction order, for a mesh tiled as tetsim_prep_tiles tiles one body (ref_table != 0: with the
+ * reference's 36-slot scatter table deciding which (tet, corner) pairs count, quirk and cap included; 0: all of them).  sizes =
+ * {tiles, tile slots}; pass NULL arrays to query them first.  tile_tets [nt], tile_off [tiles + 1] and corner_slot [4 * nt] as
+ * tetsim_prep_tiles gives them; slot_off [tiles + 1] and slot_particle [slots]: the particles of each tile's slots.  The order in two
+ * forms.  (1) entries [4 * nt] and ranges [slots], what the four-lane kernels of small bodies read: tile b's entries start at
+ * 4 * tile_off[b]; slot g adds entries [ranges[g] & 0x7ff, ranges[g] >> 16) of its tile, an entry being corner * 256 + tet (the tet's
+ * position in the tile); bit 15 of ranges[g]: the slot is the first on its particle's list (it writes the particle back).  Only pairs
+ * that count have an entry.  (2) tet_pos [2 * nt] and run_first [slots + tiles], what the 256-tet kernels read: a tile's LIST holds
+ * every pair of the tile, sorted by slot -- a slot's counted pairs first and in the order of (1), the others behind them; tet
+ * position i has corner k at list position (tet_pos[2 i] | (uint64_t)tet_pos[2 i + 1] << 32) >> 10 k & 1023, bit 40 + k set if that
+ * pair does not count (the kernels add +0 for it); slot g of tile b has the run [run_first[g + b] & 0x7ff, run_first[g + b + 1] &
+ * 0x7ff), the tile's last entry being the list's length, and bit 15 as in (1). */
+int tetsim_prep_tile_tables(const float *verts, uint32_t nv, const int32_t *tets, uint32_t nt, int32_t ref_table, uint32_t sizes[2],
+                            int32_t *tile_tets, uint32_t *tile_off, uint32_t *slot_off, int32_t *slot_particle, uint8_t *corner_slot,
+                            uint16_t *entries, uint32_t *ranges, uint32_t *tet_pos, uint16_t *run_first);
 /* Scatter table of SoftbodyGPU.js:563-577: slots[v*36 + s] = 4*tet + corner, -1 = empty.
  * ref_quirk != 0 reproduces the `<= 0.0` test.  Returns the number of dropped contributions. */
 /* The topology of that tree for any triangle list, without a device: positions [3 * nvis], tri_ids [3 * ntri], tri_body [ntri] (the

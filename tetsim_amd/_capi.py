@@ -158,7 +158,7 @@ SYMBOLS = [
     "tetsim_comm_unique_id", "tetsim_comm_init", "tetsim_comm_info", "tetsim_comm_selftest", "tetsim_comm_probe", "tetsim_group_step_n", "tetsim_halo_exchange_local", "tetsim_get_halo_plan",
     "tetsim_halo_p2p_export", "tetsim_halo_p2p_connect",
     "tetsim_halo_export", "tetsim_halo_import", "tetsim_prep_levels", "tetsim_prep_colours", "tetsim_prep_clusters",
-    "tetsim_prep_tiles", "tetsim_prep_slot_table", "tetsim_prep_call_tiles", "tetsim_prep_call_schedule", "tetsim_prep_check_call_schedule", "tetsim_prep_ref_grab_texels", "tetsim_prep_rest", "tetsim_prep_partition", "tetsim_prep_partition_quality", "tetsim_plan_create", "tetsim_plan_destroy", "tetsim_plan_sizes",
+    "tetsim_prep_tiles", "tetsim_prep_tile_tables", "tetsim_prep_slot_table", "tetsim_prep_call_tiles", "tetsim_prep_call_schedule", "tetsim_prep_check_call_schedule", "tetsim_prep_ref_grab_texels", "tetsim_prep_rest", "tetsim_prep_partition", "tetsim_prep_partition_quality", "tetsim_plan_create", "tetsim_plan_destroy", "tetsim_plan_sizes",
     "tetsim_plan_arrays", "tetsim_plan_neighbour", "tetsim_plan_neighbour_ids",
     "tetsim_plan_create_deep", "tetsim_plan_layers", "tetsim_plan_neighbour_layer2", "tetsim_plan_neighbour_layer2_ids",
     "tetsim_raycast_visual", "tetsim_start_grab_ray", "tetsim_read_visual_bounding_sphere", "tetsim_prep_boundary_surface",
@@ -333,6 +333,7 @@ def lib():
     L.tetsim_prep_tiles.argtypes = [fp, u32, ip, u32, C.POINTER(u32), C.POINTER(u32), u32, ip, C.POINTER(u32), C.POINTER(C.c_uint8), C.POINTER(u32)]
     L.tetsim_prep_slot_table.argtypes = [ip, u32, u32, i32, ip, C.POINTER(u32)]
     up = C.POINTER(u32)
+    L.tetsim_prep_tile_tables.argtypes = [fp, u32, ip, u32, C.c_int32, up, ip, up, up, ip, C.POINTER(C.c_uint8), C.POINTER(C.c_uint16), up, up, C.POINTER(C.c_uint16)]
     L.tetsim_prep_call_tiles.argtypes = [fp, u32, ip, u32, up, up, ip, up]
     L.tetsim_prep_call_schedule.argtypes = [ip, up, u32, up, u32, u32, u32, u32, up, u32, up, up, ip]
     L.tetsim_prep_check_call_schedule.argtypes = [ip, up, u32, up, u32, u32, u32, up, u32, u32]

@@ -162,12 +162,13 @@ struct PJDev {
 // positions are staged in LDS, the 4 goals of every tet are reduced IN LDS to one partial sum per tile
 // particle (fixed order: deterministic), and the per-particle pass adds the few partial sums of the tiles
 // that touch it.
+struct PJTetRow { uint32_t pos_lo, pos_hi, vol; };   // (BlockPlan::tet_pos's two words, the bits of the f32 rest volume: one 12-byte load)
 struct PJBlk {
     uint32_t nb = 0, nb_interior = 0, nt = 0, nv_local = 0, nv_owned = 0, nv_boundary = 0;  // tiles >= nb_interior touch ghosts
     const uint32_t* blk_tet_off = nullptr;   // [nb+1]
     const uint32_t* blk_vert_off = nullptr;  // [nb+1]
     const int32_t* blk_verts = nullptr;      // particle id of every tile slot
-    const uchar4* tet_lidx = nullptr;        // [nt] LDS slot of the 4 corners
+    const uchar4* tet_lidx = nullptr;        // [nt] LDS slot of the 4 corners (the four-lane kernels of small bodies, pj_quad.hip: with vol, lc_range and lc_ent)
     float4* rest_a = nullptr;                // [nt] carried rest corners, 12 floats packed in 3 x 16 B:
     float4* rest_b = nullptr;                //      a = r0.xyz r1.x | b = r1.yz r2.xy | c = r2.z r3.xyz
     float4* rest_c = nullptr;
@@ -176,6 +177,9 @@ struct PJBlk {
     float4* quat = nullptr;                  // [nt]
     const uint32_t* lc_range = nullptr;      // per tile slot: first | end << 16 into the tile's entry list
     const uint2* lc_ent = nullptr;           // [nt] 4 x u16 per tet position: (tetLocal*4 + corner), grouped by slot
+    // ... and what the 256-tet kernels (pj_blocked.hip) read instead of those four: the tile's reduction list by POSITION (host_prep.h)
+    const PJTetRow* tet_row = nullptr;       // [nt] one 12-byte row per tet: list positions of its 4 corners (10 bits each) | dropped corners << 40, rest volume
+    const uint16_t* lc_first = nullptr;      // per tile slot (+ one sentinel per tile: slot g of tile b at g + b): first | owner << 15
     float4* partial = nullptr;               // per tile slot: sum V*goal over the slot's entries (w unused)
     const float* wsum = nullptr;             // per owned particle: sum of V over all its entries -- constant, summed on the host in the device's order
     const uint32_t* vp_ell = nullptr;        // ELL [vp_cols][nv_pad]: partial-sum indices of each owned particle,

@@ -444,6 +444,7 @@ void build_blocks(const float* verts, const int32_t* tets, uint32_t nt, uint32_t
     // 3. emit per-tile tables
     B.tet_lidx.resize(4ull * nt);
     B.lc_ent.resize(4ull * nt);
+    B.tet_pos.assign(2ull * nt, 0u);
     B.blk_tet_off.push_back(0);
     B.blk_vert_off.push_back(0);
     std::vector<std::vector<uint32_t>> vert_partials(nv_sum);
@@ -482,6 +483,25 @@ void build_blocks(const float* verts, const int32_t* tets, uint32_t nt, uint32_t
                     const uint32_t u = B.tet_lidx[4ull * (t0 + j) + k];
                     B.lc_ent[4ull * t0 + fillp[u]++] = static_cast<uint16_t>(kMaxTets * k + j);  // word offset into the [corner][tet] goal planes
                 }
+        {   // the same order as the 256-tet kernels read it (host_prep.h: tet_pos, lc_first): EVERY pair of the tile by slot, a slot's live
+            // pairs first and in the order just emitted, the dropped ones behind them
+            std::vector<uint32_t> all(nu + 1, 0);
+            for (uint32_t j = 0; j < ntb; j++)
+                for (int k = 0; k < 4; k++) all[B.tet_lidx[4ull * (t0 + j) + k] + 1]++;
+            for (uint32_t u = 0; u < nu; u++) all[u + 1] += all[u];
+            for (uint32_t u = 0; u <= nu; u++) B.lc_first.push_back(static_cast<uint16_t>(all[u]));   // (all[nu] = 4 * ntb: the tile's sentinel)
+            std::vector<uint32_t> at(all.begin(), all.end() - 1);
+            for (int pass = 0; pass < 2; pass++)
+                for (uint32_t j = 0; j < ntb; j++)
+                    for (int k = 0; k < 4; k++) {
+                        const bool dropped = !live[4ull * B.tet_perm[t0 + j] + k];
+                        if (dropped != (pass == 1)) continue;
+                        const uint64_t p = static_cast<uint64_t>(at[B.tet_lidx[4ull * (t0 + j) + k]]++) << (10 * k);
+                        uint32_t* w = &B.tet_pos[2ull * (t0 + j)];
+                        w[0] |= static_cast<uint32_t>(p);
+                        w[1] |= static_cast<uint32_t>(p >> 32) | (dropped ? 1u << (8 + k) : 0u);
+                    }
+        }
         for (uint32_t u = 0; u < nu; u++) {
             const int32_t v = touched[u];
             B.blk_verts.push_back(v);
@@ -527,7 +547,7 @@ void build_blocks(const float* verts, const int32_t* tets, uint32_t nt, uint32_t
             const std::vector<uint32_t>& list = vert_partials[v];
             for (size_t j = 0; j < list.size(); j++) B.slot_src[j * B.ns_pad + g] = list[j];
             B.blk_maxsrc[b] = std::max<uint32_t>(B.blk_maxsrc[b], static_cast<uint32_t>(list.size()));
-            if (!list.empty() && list[0] == g) B.lc_range[g] |= 1u << 15;
+            if (!list.empty() && list[0] == g) { B.lc_range[g] |= 1u << 15; B.lc_first[g + b] |= 1u << 15; }
         }
 }
 

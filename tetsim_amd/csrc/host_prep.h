@@ -123,6 +123,16 @@ struct BlockPlan {
     std::vector<uint32_t> lc_range;      // per tile vertex: first | owner << 15 | (last+1) << 16 into the tile's lc_ent (first, last+1 <= 1024);
                                          //   owner = this slot is the FIRST of its particle's partial sums (the fused kernel's one writer)
     std::vector<uint16_t> lc_ent;        // [4*nt] per tile: corner*256 + tetLocal (word offset into the goal planes) grouped by LDS slot, tet order inside
+    // The same reduction order as the 256-tet kernels read it (pj_blocked.hip; the four-lane kernels of small bodies keep the three tables
+    // above): the tile's LIST is every (corner, tet) pair of the tile, sorted by slot -- inside a slot's run the live pairs in lc_ent's
+    // order (ascending tet, then corner), behind them the pairs the incidence table dropped (same order; the kernel adds +0 for them).
+    //   tet_pos   per tet, the list positions of its four corners, 10 bits each, and which of them are dropped:
+    //             word 0 = pos0 | pos1 << 10 | pos2 << 20 | (pos3 & 3) << 30, word 1 = pos3 >> 2 | dropped << 8 (bit k: corner k)
+    //             -- the inverse permutation of the list; tetsim_create.hip stores it with the rest volume as one 12-byte row
+    //   lc_first  per tile nu + 1 entries (slot g of tile b at g + b): where the slot's run starts | owner << 15; a run ends where the
+    //             next one starts, the tile's last entry is the list's length 4 * ntb
+    std::vector<uint32_t> tet_pos;       // [2*nt]
+    std::vector<uint16_t> lc_first;      // [slots + num_blocks]
     std::vector<uint32_t> vp_off;        // [nv_sum+1] per summed vertex: range into vp_idx
     std::vector<uint32_t> vp_idx;        // indices into the partial-sum array, ascending tile
     std::vector<uint32_t> vp_ell;        // the same lists as ELL [vp_cols][nv_pad], 0xffffffff = none, followed by the particle's ZERO sums: tile

@@ -12,7 +12,9 @@
 //        (V*goal, V) for its 4 corners in LDS;
 //     3. lanes switch roles -- one lane per tile PARTICLE -- and add up the corner goals of that particle in
 //        LDS, in a fixed host-built order (deterministic, no atomics), storing ONE partial sum per
-//        (tile, particle), coalesced.
+//        (tile, particle), coalesced.  The order is a LIST of the tile's (corner, tet) pairs sorted by particle
+//        (host_prep.h): a tet lane leaves each corner's goal at the corner's list position, a particle lane adds
+//        up its run of the list front to back.
 //   pjb_vertex_kernel  one lane per particle: adds the 1..9 (2.9 on average; irregular meshes: more) partial sums of the tiles that touch
 //        it instead of gathering ~23 goals, then collides / integrates exactly like the gather formulation.
 //
@@ -107,7 +109,7 @@ __device__ __forceinline__ VertexOut pjb_vertex_update(f3 acc, float wsum, f3 pr
 
 constexpr uint32_t kTile = kBlockTile;   // tets (= threads) per workgroup tile; host_prep.cpp cuts the tiles with the same constant
 
-// LDS per workgroup is 18 KB (4 + 12 + 2) so that 8 workgroups fit a CU's 160 KB: with 22.5 KB only 7
+// LDS per workgroup is 17 KB (4 + 12 + 1) so that 8 workgroups fit a CU's 160 KB: with 22.5 KB only 7
 // fit and the 3900 tiles of the 1 M-tet lattice need 2.18 "rounds" of the chip instead of 1.9.
 // Timing ablations (fewer rotation iterations, no rest-shape write-back, unpeeled first iteration), per-tile phase stamps and the
 // rotation-iteration histogram change the physics or the timing and exist only in the separate development build
@@ -145,10 +147,10 @@ template <int kMode, bool kFused, bool kAlt = false, bool kHaloWait = false, boo
 __device__ __forceinline__ void pjb_tet_body(const PJBlk& d, uint32_t tile_first, uint32_t tile_count, uint32_t tiles_per_xcd TETSIM_DBG_PARAM,
                                              [[maybe_unused]] const PJHaloWait* hw = nullptr, const uint32_t stamp = 0u, [[maybe_unused]] const PJPoll* poll = nullptr) {
     __shared__ float4 s_pos[kTile];        // staged particle positions
-    __shared__ float s_gx[4 * kTile];      // V*goal per corner, plane-major [corner][tet], one plane per component
+    __shared__ float s_gx[4 * kTile];      // V*goal per corner in LIST order (a particle's corners are one run), one plane per component
     __shared__ float s_gy[4 * kTile];
     __shared__ float s_gz[4 * kTile];
-    __shared__ uint2 s_ent[kTile];         // the tile's reduction order, 4 x u16 per tet position
+    __shared__ uint8_t s_slot[4 * kTile];  // the slot whose run a list position belongs to: where a tet finds its corners' particles
 
     constexpr bool kLean = kMode == kModeConstantRest;
     uint32_t block_index = blockIdx.x;
@@ -174,7 +176,15 @@ __device__ __forceinline__ void pjb_tet_body(const PJBlk& d, uint32_t tile_first
     const bool has_slot = tid < nu, has_tet = tid < ntb;
     const uint32_t slot = v0 + (has_slot ? tid : 0u), e = t0 + (has_tet ? tid : 0u);
     const uint32_t vid = static_cast<uint32_t>(d.blk_verts[slot]);   // (unsigned: no sign extension right behind the load)
-    const uint32_t range = has_slot ? d.lc_range[slot] : 0u;
+    // the slot's run of the tile's list: [first, the next slot's first) -- one more entry per tile closes its last run
+    const uint32_t range = has_slot ? d.lc_first[slot + b] : 0u, range_end = has_slot ? d.lc_first[slot + b + 1u] : 0u;
+    const uint32_t first = range & 0x7ffu, last = range_end & 0x7ffu;   // (bit 15: owner flag)
+    // Every list position gets the slot of its run, written by the slot's lane as soon as its two starts are there (they come with
+    // the particle ids, a trip before the positions): the tet lanes read their corners' slots from it behind the staging barrier.
+    auto fill_slots = [&]() {
+        if (has_slot)
+            for (uint32_t i = first; i < last; i++) s_slot[i] = static_cast<uint8_t>(tid);
+    };
     // kFused: the particle update of the PREVIOUS substep happens here, for this tile's own particles (a particle in k tiles is
     // updated k times, identically; the tile holding the first of its partial sums -- `owner` -- writes the result back): the
     // slot's list of partial sums is requested together with its particle id (round trip 1), then the sums themselves, the
@@ -191,7 +201,6 @@ __device__ __forceinline__ void pjb_tet_body(const PJBlk& d, uint32_t tile_first
         for (uint32_t j = 0; j < 8u; j++) src[j] = (j < maxsrc) ? col[static_cast<size_t>(j) * d.ns_pad] : 0xffffffffu;   // (uniform)
         if (maxsrc > 8u) src8 = col[8ull * d.ns_pad];
     }
-    const uchar4 li = d.tet_lidx[e];
     // (kPoll: the record was written by this tile's workgroup of the PREVIOUS substep of the same launch -- no kernel boundary has emptied
     // this CU's first-level cache of the line it may have read two substeps ago: memory-side loads, like the looks at the predictions)
     // ... and only AFTER the looks at the predictions have succeeded (sub > 0): a tile stores its partial sums behind the completion of its
@@ -208,8 +217,12 @@ __device__ __forceinline__ void pjb_tet_body(const PJBlk& d, uint32_t tile_first
     bool record_late = false;
     if constexpr (kPoll) record_late = poll->want != 0u;   // (uniform)
     if (!record_late) load_record();
-    const float V = d.vol[e];
-    const uint2 ent_row = d.lc_ent[e];
+    // the tet's constants, one 12-byte row: the list positions of its four corners (10 bits each), which corners the incidence table
+    // dropped (they have a place in the list and leave +0 there: the sums keep their bits), the rest volume
+    const PJTetRow row = d.tet_row[e];
+    const float V = __uint_as_float(row.vol);
+    const uint32_t lp[4] = {row.pos_lo & 1023u, (row.pos_lo >> 10) & 1023u, (row.pos_lo >> 20) & 1023u, (row.pos_lo >> 30) | ((row.pos_hi & 255u) << 2)};
+    const uint32_t dropped = row.pos_hi >> 8;
     float4 pos_stage;
     if constexpr (kFused) {
         // (a ghost would keep its received prediction; fused bodies have none)
@@ -222,6 +235,7 @@ __device__ __forceinline__ void pjb_tet_body(const PJBlk& d, uint32_t tile_first
         const float4 t8 = d.partial_prev[src8 == 0xffffffffu ? 0u : src8];
         const float4 prev4 = d.fin_in[vid];
         const float wsum = d.wsum[vid];
+        fill_slots();
         f3 acc = F3(0.0f, 0.0f, 0.0f);
 #pragma unroll
         for (uint32_t j = 0; j < 8u; j++) { acc.x += g[j].x; acc.y += g[j].y; acc.z += g[j].z; }
@@ -257,15 +271,18 @@ __device__ __forceinline__ void pjb_tet_body(const PJBlk& d, uint32_t tile_first
         __syncthreads();
         const bool ghost = vid >= d.nv_owned;
         const float4 own = load_coherent(d.pos_pred, ghost ? 0u : vid), gh = load_coherent(hw->ghosts, ghost ? vid - d.nv_owned : 0u);
+        fill_slots();
         pos_stage = ghost ? gh : own;
     } else if constexpr (kAlt) {
         const uint32_t g = vid - d.nv_owned;   // (ghost index; two-layer regions keep the layers in separate buffers)
         const float4* src = vid >= d.nv_owned ? (g < d.n_ghost1 ? d.ghost_alt + g : d.ghost2 + (g - d.n_ghost1)) : d.pos_pred + vid;
         pos_stage = *src;
+        fill_slots();
     } else if constexpr (kPoll) {
         TETSIM_POLL_BEGIN();
         TETSIM_POLL_TILE(1);
         pos_stage = load_coherent(d.pos_pred, vid);
+        fill_slots();   // (under the first look's trip)
         if (poll->want != 0u) {
             bool pend = has_slot && __float_as_uint(pos_stage.w) != poll->want;
             if (__builtin_amdgcn_ballot_w64(pend) != 0ull) {
@@ -286,9 +303,9 @@ __device__ __forceinline__ void pjb_tet_body(const PJBlk& d, uint32_t tile_first
         TETSIM_POLL_TILE_SAVE();
     } else {
         pos_stage = d.pos_pred[vid];
+        fill_slots();
     }
     if (has_slot) s_pos[tid] = pos_stage;
-    if (has_tet) s_ent[tid] = ent_row;
     TETSIM_STAMP(1);  // loads issued (and landed, for this wave)
     // Every load above has been consumed by now on the path that has tets; say so for ALL paths.  Without this, the
     // wait-count model keeps "load into v[..] pending" alive through the path that skips the solve, and protects the reuse
@@ -301,7 +318,10 @@ __device__ __forceinline__ void pjb_tet_body(const PJBlk& d, uint32_t tile_first
     // 2. solve
     if (has_tet) {
         f3 cur[4], rest[4], goal[4];
-        cur[0] = xyz(s_pos[li.x]); cur[1] = xyz(s_pos[li.y]); cur[2] = xyz(s_pos[li.z]); cur[3] = xyz(s_pos[li.w]);
+        {
+            const uint32_t l0 = s_slot[lp[0]], l1 = s_slot[lp[1]], l2 = s_slot[lp[2]], l3 = s_slot[lp[3]];
+            cur[0] = xyz(s_pos[l0]); cur[1] = xyz(s_pos[l1]); cur[2] = xyz(s_pos[l2]); cur[3] = xyz(s_pos[l3]);
+        }
         rest[0] = F3(ra.x, ra.y, ra.z); rest[1] = F3(ra.w, rb.x, rb.y);
         rest[2] = F3(rb.z, rb.w, rc.x); rest[3] = F3(rc.y, rc.z, rc.w);
         if constexpr (kMode == kModeLeanState) rest[3] = lean_fourth_corner(rest);
@@ -315,10 +335,11 @@ __device__ __forceinline__ void pjb_tet_body(const PJBlk& d, uint32_t tile_first
         // LDS staging first, global results after it: nothing below may have to wait for the write-through stores
         const f3 vcc = cc * V;
 #pragma unroll
-        for (int k = 0; k < 4; k++) {  // V * (goal + cc)
-            s_gx[k * kTile + tid] = fmaf(goal[k].x, V, vcc.x);
-            s_gy[k * kTile + tid] = fmaf(goal[k].y, V, vcc.y);
-            s_gz[k * kTile + tid] = fmaf(goal[k].z, V, vcc.z);
+        for (int k = 0; k < 4; k++) {  // V * (goal + cc), at the corner's place in the list
+            const bool live = ((dropped >> k) & 1u) == 0u;
+            s_gx[lp[k]] = live ? fmaf(goal[k].x, V, vcc.x) : 0.0f;
+            s_gy[lp[k]] = live ? fmaf(goal[k].y, V, vcc.y) : 0.0f;
+            s_gz[lp[k]] = live ? fmaf(goal[k].z, V, vcc.z) : 0.0f;
         }
         if constexpr (kMode != kModeLeanState) store_wt(d.quat, e, q_new);
         if (!kLean && TETSIM_DBG_STORE_REST) {  // constant-rest-shape bodies never write the shape back
@@ -335,33 +356,23 @@ __device__ __forceinline__ void pjb_tet_body(const PJBlk& d, uint32_t tile_first
 
     // 3. one lane per tile particle: fixed-order sum of its corner goals -> one partial per (tile, particle)
     if (tid < nu) {
-        const uint32_t first = range & 0x7ffu, last = range >> 16;   // (bit 15: owner flag)
-        const uint16_t* ent = reinterpret_cast<const uint16_t*>(s_ent);
-        // An entry is the word offset corner * kTile + tet of a corner goal in the planes (host_prep.cpp), so its byte offset
-        // and the byte offset of its tet's weight are one shift and one mask.  4 entries per trip: the 4 index reads, then
-        // the 16 value reads, are independent LDS ops in flight together (one entry at a time is a ~9-deep chain of
-        // dependent LDS round trips: 4.9k cycles per tile in the s_memtime trace); whole groups of 4 run unmasked, the
-        // 0-3 left over one by one.  Accumulation order stays entry order, i.e. deterministic.
-        auto plane = [](const float* base, uint32_t byte_off) { return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_off); };
+        // The slot's run of the list, front to back: the values sit where they are added, no index in front of them.  4 entries per
+        // trip: their 12 reads are independent LDS ops in flight together (one entry at a time is a chain of dependent LDS round
+        // trips); whole groups of 4 run unmasked, the 0-3 left over one by one.  Accumulation order is list order, i.e.
+        // deterministic -- and the order the tiles have always added in (host_prep.cpp).
         // The weight sum of a particle (sum of V over its entries, then over its tiles) never changes -- rest volumes are
         // constants -- so it is not reduced here at all: the host adds it up once, in this very order (tetsim_create.hip ->
         // PJBlk::wsum), and the particle pass reads it.  Three planes per entry instead of four.
         float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         uint32_t i = first;
         for (; i + 4u <= last; i += 4u) {
-            uint32_t o[4];
             float gx[4], gy[4], gz[4];
 #pragma unroll
-            for (uint32_t j = 0; j < 4u; j++) o[j] = static_cast<uint32_t>(ent[i + j]) << 2;
-#pragma unroll
-            for (uint32_t j = 0; j < 4u; j++) { gx[j] = plane(s_gx, o[j]); gy[j] = plane(s_gy, o[j]); gz[j] = plane(s_gz, o[j]); }
+            for (uint32_t j = 0; j < 4u; j++) { gx[j] = s_gx[i + j]; gy[j] = s_gy[i + j]; gz[j] = s_gz[i + j]; }
 #pragma unroll
             for (uint32_t j = 0; j < 4u; j++) { acc.x += gx[j]; acc.y += gy[j]; acc.z += gz[j]; }
         }
-        for (; i < last; i++) {
-            const uint32_t o = static_cast<uint32_t>(ent[i]) << 2;
-            acc.x += plane(s_gx, o); acc.y += plane(s_gy, o); acc.z += plane(s_gz, o);
-        }
+        for (; i < last; i++) { acc.x += s_gx[i]; acc.y += s_gy[i]; acc.z += s_gz[i]; }
         acc.w = __uint_as_float(stamp);
         store_wt(d.partial, v0 + tid, acc);
     }
@@ -459,10 +470,10 @@ template <int kMode, bool kLocal>
 __device__ __forceinline__ void pjb_frame_body(const PJBlk& d, const DevParams& P, const uint32_t n, const int32_t* const block_tile, float4* const pbuf0, float4* const pbuf1,
                                                uint32_t* const err, const uint32_t timeout_ms) {
     __shared__ float4 s_pos[kTile];
-    __shared__ float s_gx[4 * kTile];
+    __shared__ float s_gx[4 * kTile];      // (list order, like pjb_tet_body's)
     __shared__ float s_gy[4 * kTile];
     __shared__ float s_gz[4 * kTile];
-    __shared__ uint2 s_ent[kTile];
+    __shared__ uint8_t s_slot[4 * kTile];
 
     constexpr bool kLean = kMode == kModeConstantRest;
     const int32_t bt = block_tile[blockIdx.x];
@@ -476,7 +487,7 @@ __device__ __forceinline__ void pjb_frame_body(const PJBlk& d, const DevParams& 
     const uint32_t slot = v0 + (has_slot ? tid : 0u), e = t0 + (has_tet ? tid : 0u);
     // everything that stays for the whole call, requested together (ids first: the particle loads depend on them)
     const uint32_t vid = static_cast<uint32_t>(d.blk_verts[slot]);
-    const uint32_t range = has_slot ? d.lc_range[slot] : 0u;
+    const uint32_t range = has_slot ? d.lc_first[slot + b] : 0u, range_end = has_slot ? d.lc_first[slot + b + 1u] : 0u;
     const uint32_t maxsrc = d.blk_maxsrc[b];
     uint32_t src[9];
     {
@@ -484,13 +495,14 @@ __device__ __forceinline__ void pjb_frame_body(const PJBlk& d, const DevParams& 
 #pragma unroll
         for (uint32_t j = 0; j < 9u; j++) src[j] = (has_slot && j < maxsrc) ? col[static_cast<size_t>(j) * d.ns_pad] : 0xffffffffu;
     }
-    const uchar4 li = d.tet_lidx[e];
+    const PJTetRow row = d.tet_row[e];   // (list positions, dropped corners, rest volume: pjb_tet_body)
     const float4 ra = d.rest_a[e], rb = d.rest_b[e];
     float4 rc = make_float4(0.0f, 0.0f, 0.0f, 0.0f), q = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
     if constexpr (kMode == kModeLeanState) rc.x = d.rest_c1[e];   // (lean state: three corners, no quaternion -- pjb_tet_body)
     else { rc = d.rest_c[e]; q = d.quat[e]; }
-    const float V = d.vol[e];
-    s_ent[tid] = has_tet ? d.lc_ent[e] : make_uint2(0u, 0u);
+    const float V = __uint_as_float(row.vol);
+    const uint32_t lp[4] = {row.pos_lo & 1023u, (row.pos_lo >> 10) & 1023u, (row.pos_lo >> 20) & 1023u, (row.pos_lo >> 30) | ((row.pos_hi & 255u) << 2)};
+    const uint32_t dropped = row.pos_hi >> 8;
     f3 rest[4];
     rest[0] = F3(ra.x, ra.y, ra.z); rest[1] = F3(ra.w, rb.x, rb.y);
     rest[2] = F3(rb.z, rb.w, rc.x); rest[3] = F3(rc.y, rc.z, rc.w);
@@ -498,8 +510,13 @@ __device__ __forceinline__ void pjb_frame_body(const PJBlk& d, const DevParams& 
     const float wsum = d.wsum[vid];
     f3 stage = xyz(d.pos_pred[vid]);     // substep 0 starts from the prediction the previous call left
     const uint32_t epoch = d.epoch ? d.epoch : P.epoch;   // (a direct launch -- tetsim_step -- brings its own block of sequence numbers)
-    const uint32_t first = range & 0x7ffu, last = range >> 16;
+    const uint32_t first = range & 0x7ffu, last = range_end & 0x7ffu;
     const bool owner = has_slot && ((range >> 15) & 1u);
+    // the slots of the tet's corners stay in registers for the call: read once from the table the slot lanes fill (pjb_tet_body)
+    if (has_slot)
+        for (uint32_t i = first; i < last; i++) s_slot[i] = static_cast<uint8_t>(tid);
+    __syncthreads();
+    const uint32_t li[4] = {s_slot[lp[0]], s_slot[lp[1]], s_slot[lp[2]], s_slot[lp[3]]};
     float4* const pbuf[2] = {pbuf0, pbuf1};
     const long long limit = 100000ll * timeout_ms;   // 100 MHz ticks; 0 = unbounded
 
@@ -568,7 +585,7 @@ __device__ __forceinline__ void pjb_frame_body(const PJBlk& d, const DevParams& 
         FRAME_STAMP(2);
         if (has_tet) {
             f3 cur[4], r[4], goal[4];
-            cur[0] = xyz(s_pos[li.x]); cur[1] = xyz(s_pos[li.y]); cur[2] = xyz(s_pos[li.z]); cur[3] = xyz(s_pos[li.w]);
+            cur[0] = xyz(s_pos[li[0]]); cur[1] = xyz(s_pos[li[1]]); cur[2] = xyz(s_pos[li[2]]); cur[3] = xyz(s_pos[li[3]]);
 #pragma unroll
             for (int k = 0; k < 4; k++) r[k] = rest[k];
             if constexpr (kMode == kModeLeanState) r[3] = lean_fourth_corner(rest);
@@ -583,33 +600,26 @@ __device__ __forceinline__ void pjb_frame_body(const PJBlk& d, const DevParams& 
             const f3 vcc = cc * V;
 #pragma unroll
             for (int k = 0; k < 4; k++) {
-                s_gx[k * kTile + tid] = fmaf(goal[k].x, V, vcc.x);
-                s_gy[k * kTile + tid] = fmaf(goal[k].y, V, vcc.y);
-                s_gz[k * kTile + tid] = fmaf(goal[k].z, V, vcc.z);
+                const bool live = ((dropped >> k) & 1u) == 0u;
+                s_gx[lp[k]] = live ? fmaf(goal[k].x, V, vcc.x) : 0.0f;
+                s_gy[lp[k]] = live ? fmaf(goal[k].y, V, vcc.y) : 0.0f;
+                s_gz[lp[k]] = live ? fmaf(goal[k].z, V, vcc.z) : 0.0f;
             }
         }
         FRAME_STAMP(3);
         __syncthreads();
         FRAME_STAMP(4);
         if (has_slot) {   // the tet kernel's reduction, entry for entry
-            const uint16_t* ent = reinterpret_cast<const uint16_t*>(s_ent);
-            auto plane = [](const float* base, uint32_t byte_off) { return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_off); };
             float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             uint32_t i = first;
             for (; i + 4u <= last; i += 4u) {
-                uint32_t o[4];
                 float gx[4], gy[4], gz[4];
 #pragma unroll
-                for (uint32_t j = 0; j < 4u; j++) o[j] = static_cast<uint32_t>(ent[i + j]) << 2;
-#pragma unroll
-                for (uint32_t j = 0; j < 4u; j++) { gx[j] = plane(s_gx, o[j]); gy[j] = plane(s_gy, o[j]); gz[j] = plane(s_gz, o[j]); }
+                for (uint32_t j = 0; j < 4u; j++) { gx[j] = s_gx[i + j]; gy[j] = s_gy[i + j]; gz[j] = s_gz[i + j]; }
 #pragma unroll
                 for (uint32_t j = 0; j < 4u; j++) { acc.x += gx[j]; acc.y += gy[j]; acc.z += gz[j]; }
             }
-            for (; i < last; i++) {
-                const uint32_t o = static_cast<uint32_t>(ent[i]) << 2;
-                acc.x += plane(s_gx, o); acc.y += plane(s_gy, o); acc.z += plane(s_gz, o);
-            }
+            for (; i < last; i++) { acc.x += s_gx[i]; acc.y += s_gy[i]; acc.z += s_gz[i]; }
             acc.w = __uint_as_float(epoch + s);   // data and "substep s is here" in one 16-byte store
             if constexpr (kLocal) store_plain(pbuf[s & 1u], v0 + tid, acc);
             else store_wt(pbuf[s & 1u], v0 + tid, acc);

@@ -202,18 +202,22 @@ int create_polar(tetsim_body* h, const float* verts, uint32_t nv, const int32_t*
         k.lean = (o.flags & TETSIM_FLAG_CONSTANT_REST_SHAPE) != 0;
         k.lean_state = lean_state;
         k.rot_exit_w2 = d.rot_exit_w2;
-        uint32_t *bto, *bvo, *lcr, *vpe;
+        // (the tile's reduction order: the four-lane kernels read slots, volumes, ranges and entries, the 256-tet kernels one row per tet
+        // and the runs' starts -- host_prep.h; a body uploads what its kernels read)
+        uint32_t *bto, *bvo, *lcr = nullptr, *vpe, *trow = nullptr;
         int32_t* bv;
-        uchar4* lidx;
-        float* vol;
-        uint2* lce;
+        uchar4* lidx = nullptr;
+        float* vol = nullptr;
+        uint2* lce = nullptr;
+        uint16_t* lcf = nullptr;
         const size_t nslots = B.blk_verts.size();
         if ((rc = dev_alloc(h, &bto, B.blk_tet_off.size()))) return rc;
         if ((rc = dev_alloc(h, &bvo, B.blk_vert_off.size()))) return rc;
         if ((rc = dev_alloc(h, &bv, nslots))) return rc;
         if (ntl >= kStoreWtMaxIndex || nslots >= kStoreWtMaxIndex || nvl >= kStoreWtMaxIndex)
             return fail(h, TETSIM_EINVAL, "body too large for one handle (2^27 tets / particles / partial sums: 32-bit store offsets, dev_store.h); partition it");
-        if ((rc = dev_alloc(h, &lidx, ntl))) return rc;
+        if (quad && (rc = dev_alloc(h, &lidx, ntl))) return rc;
+        if (!quad && (rc = dev_alloc(h, &trow, 3ull * ntl))) return rc;
         if ((rc = dev_alloc(h, &k.rest_a, ntl))) return rc;
         if ((rc = dev_alloc(h, &k.rest_b, ntl))) return rc;
         if (lean_state) {   // three carried corners (a, b, c1); the constant rest shape stays beside them for the quaternion's recovery
@@ -222,16 +226,18 @@ int create_polar(tetsim_body* h, const float* verts, uint32_t nv, const int32_t*
             if ((rc = dev_alloc(h, &h->rest0_b, ntl))) return rc;
             if ((rc = dev_alloc(h, &h->rest0_c, ntl))) return rc;
         } else if ((rc = dev_alloc(h, &k.rest_c, ntl))) return rc;
-        if ((rc = dev_alloc(h, &vol, ntl))) return rc;
+        if (quad && (rc = dev_alloc(h, &vol, ntl))) return rc;
         if ((rc = dev_alloc(h, &k.quat, ntl))) return rc;
-        if ((rc = dev_alloc(h, &lcr, nslots))) return rc;
-        if ((rc = dev_alloc(h, &lce, ntl))) return rc;
+        if (quad && (rc = dev_alloc(h, &lcr, nslots))) return rc;
+        if (quad && (rc = dev_alloc(h, &lce, ntl))) return rc;
+        if (!quad && (rc = dev_alloc(h, &lcf, B.lc_first.size()))) return rc;
         if ((rc = dev_alloc(h, &k.partial, nslots))) return rc;
         if ((rc = dev_alloc(h, &vpe, B.vp_ell.size()))) return rc;
         std::vector<float4> ra(ntl), rb(ntl), rcv(ntl), quat(ntl, make_float4(0, 0, 0, 1));
         std::vector<float> volh(ntl);
         std::vector<uchar4> lidxh(ntl);
         std::vector<uint2> lceh(ntl);
+        std::vector<uint32_t> trowh(3ull * ntl);
         for (uint32_t i = 0; i < ntl; i++) {
             const uint32_t lt = static_cast<uint32_t>(B.tet_perm[i]);
             const int32_t* c = &ltets[4 * lt];
@@ -250,6 +256,8 @@ int create_polar(tetsim_body* h, const float* verts, uint32_t nv, const int32_t*
             lidxh[i] = make_uchar4(B.tet_lidx[4ull * i], B.tet_lidx[4ull * i + 1], B.tet_lidx[4ull * i + 2], B.tet_lidx[4ull * i + 3]);
             const uint16_t* en = &B.lc_ent[4ull * i];
             lceh[i] = make_uint2(en[0] | (static_cast<uint32_t>(en[1]) << 16), en[2] | (static_cast<uint32_t>(en[3]) << 16));
+            trowh[3ull * i] = B.tet_pos[2ull * i]; trowh[3ull * i + 1] = B.tet_pos[2ull * i + 1];
+            memcpy(&trowh[3ull * i + 2], &volh[i], sizeof(float));
         }
         // Weight sums (PJBlk::wsum): rest volumes are constants, so the denominator of the volume-weighted average
         // (SoftbodyGPU.js:306-319) is added up HERE, once, in exactly the order the kernels add the numerator: a tile slot's
@@ -401,7 +409,8 @@ int create_polar(tetsim_body* h, const float* verts, uint32_t nv, const int32_t*
         if ((rc = upload(h, bto, B.blk_tet_off))) return rc;
         if ((rc = upload(h, bvo, B.blk_vert_off))) return rc;
         if ((rc = upload(h, bv, B.blk_verts))) return rc;
-        if ((rc = upload(h, lidx, lidxh))) return rc;
+        if (quad && (rc = upload(h, lidx, lidxh))) return rc;
+        if (!quad && (rc = upload(h, trow, trowh))) return rc;
         if ((rc = upload(h, k.rest_a, ra))) return rc;
         if ((rc = upload(h, k.rest_b, rb))) return rc;
         if (lean_state) {
@@ -412,13 +421,15 @@ int create_polar(tetsim_body* h, const float* verts, uint32_t nv, const int32_t*
             if ((rc = upload(h, h->rest0_b, rb))) return rc;
             if ((rc = upload(h, h->rest0_c, rcv))) return rc;
         } else if ((rc = upload(h, k.rest_c, rcv))) return rc;
-        if ((rc = upload(h, vol, volh))) return rc;
+        if (quad && (rc = upload(h, vol, volh))) return rc;
         if ((rc = upload(h, k.quat, quat))) return rc;
-        if ((rc = upload(h, lcr, B.lc_range))) return rc;
-        if ((rc = upload(h, lce, lceh))) return rc;
+        if (quad && (rc = upload(h, lcr, B.lc_range))) return rc;
+        if (quad && (rc = upload(h, lce, lceh))) return rc;
+        if (!quad && (rc = upload(h, lcf, B.lc_first))) return rc;
         if ((rc = upload(h, vpe, B.vp_ell))) return rc;
         HIPCHK(h, hipMemset(k.partial, 0, std::max<size_t>(nslots, 1) * sizeof(float4)));
         k.blk_tet_off = bto; k.blk_vert_off = bvo; k.blk_verts = bv; k.tet_lidx = lidx; k.vol = vol;
+        k.tet_row = reinterpret_cast<const PJTetRow*>(trow); k.lc_first = lcf;
         k.lc_range = lcr; k.lc_ent = lce; k.vp_ell = vpe; k.vp_cols = B.vp_cols; k.nv_pad = B.nv_pad;
         d.quat = k.quat;  // tetsim_read_quats
 #ifdef TETSIM_ABLATION

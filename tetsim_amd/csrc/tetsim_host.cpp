@@ -140,6 +140,27 @@ int tetsim_prep_tiles(const float* verts, uint32_t nv, const int32_t* tets, uint
     if (corner_slot) std::copy(B.tet_lidx.begin(), B.tet_lidx.end(), corner_slot);
     return 0;
 }
+int tetsim_prep_tile_tables(const float* verts, uint32_t nv, const int32_t* tets, uint32_t nt, int32_t ref_table, uint32_t sizes[2], int32_t* tile_tets,
+                            uint32_t* tile_off, uint32_t* slot_off, int32_t* slot_particle, uint8_t* corner_slot, uint16_t* entries, uint32_t* ranges,
+                            uint32_t* tet_pos, uint16_t* run_first) {
+    if (!sizes) return TETSIM_EINVAL;
+    std::string e = validate_mesh(verts, nv, tets, nt, false);
+    if (!e.empty()) return fail(nullptr, TETSIM_EINVAL, e);
+    const Incidence inc = build_incidence(tets, nt, nv, ref_table != 0, ref_table != 0);
+    BlockPlan B;
+    build_blocks(verts, tets, nt, nv, nv, inc, &B);
+    sizes[0] = B.num_blocks; sizes[1] = static_cast<uint32_t>(B.blk_verts.size());
+    if (tile_tets) std::copy(B.tet_perm.begin(), B.tet_perm.end(), tile_tets);
+    if (tile_off) std::copy(B.blk_tet_off.begin(), B.blk_tet_off.end(), tile_off);
+    if (slot_off) std::copy(B.blk_vert_off.begin(), B.blk_vert_off.end(), slot_off);
+    if (slot_particle) std::copy(B.blk_verts.begin(), B.blk_verts.end(), slot_particle);
+    if (corner_slot) std::copy(B.tet_lidx.begin(), B.tet_lidx.end(), corner_slot);
+    if (entries) std::copy(B.lc_ent.begin(), B.lc_ent.end(), entries);
+    if (ranges) std::copy(B.lc_range.begin(), B.lc_range.end(), ranges);
+    if (tet_pos) std::copy(B.tet_pos.begin(), B.tet_pos.end(), tet_pos);
+    if (run_first) std::copy(B.lc_first.begin(), B.lc_first.end(), run_first);
+    return 0;
+}
 int tetsim_prep_slot_table(const int32_t* tets, uint32_t nt, uint32_t nv, int32_t ref_quirk, int32_t* slots, uint32_t* dropped) {
     if ((nt && !tets) || !slots) return TETSIM_EINVAL;
     std::string e = validate_mesh(reinterpret_cast<const float*>(tets), nv ? nv : 1, tets, nt, false);
