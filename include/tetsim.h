@@ -1468,6 +1468,15 @@ int tetsim_prep_tiles(const float *verts, uint32_t nv, const int32_t *tets, uint
 int tetsim_prep_tile_tables(const float *verts, uint32_t nv, const int32_t *tets, uint32_t nt, int32_t ref_table, uint32_t sizes[2],
                             int32_t *tile_tets, uint32_t *tile_off, uint32_t *slot_off, int32_t *slot_particle, uint8_t *corner_slot,
                             uint16_t *entries, uint32_t *ranges, uint32_t *tet_pos, uint16_t *run_first);
+/* The routine behind tetsim_set_colliders and tetsim_set_body_colliders, without a device, for tests (as_rows != 0: every field rounded to
+ * f32 first and taken from there, as a row of tetsim_set_body_colliders holds it): per collider codes[k] = 0, or why
+ * it is refused -- 1 unknown kind, 2 non-finite value, 3 negative radius or friction, 4 zero-length plane normal, 5 negative half-extent,
+ * 6 zero-length box axis, 7 box axes not orthogonal, the first that applies (`reserved` is not looked at) -- and the bytes of the two views
+ * the kernels read, zeros for a refused collider: views_f64 [count] records of a[3], b[3], u[9], radius, friction, v[3] as double, then
+ * kind and 0 as int32; views_f32 [count] the same with float. */
+#define TETSIM_COLLIDER_VIEW_F64_BYTES 168
+#define TETSIM_COLLIDER_VIEW_F32_BYTES 88
+int tetsim_prep_collider_views(const TetSimCollider *colliders, uint32_t count, int32_t as_rows, int32_t *codes, void *views_f64, void *views_f32);
 /* Scatter table of SoftbodyGPU.js:563-577: slots[v*36 + s] = 4*tet + corner, -1 = empty.
  * ref_quirk != 0 reproduces the `<= 0.0` test.  Returns the number of dropped contributions. */
 /* The topology of that tree for any triangle list, without a device: positions [3 * nvis], tri_ids [3 * ntri], tri_body [ntri] (the

@@ -48,31 +48,58 @@ def _unit(v):
     return v / np.sqrt(l2)
 
 
+# why a collider is refused, in the order the library checks (body_rows.h: ColliderRefusal); 0 = accepted
+REFUSALS = ("", "unknown kind", "non-finite value", "negative radius or friction", "zero-length plane normal", "negative half-extent", "zero-length box axis",
+            "box axes are not orthogonal")
+
+
+def views(w):
+    """The library's one collider routine (body_rows.h: collider_view, collider_f32) on 21 doubles -- kind as a value, a, b, axes, radius,
+    friction, velocity, a row's order -- in numpy: (code, the f64 view's 168 bytes, the f32 view's 88 bytes), the views None for a refused
+    collider.  Every operation is an f64 one rounded on its own: (x*x + y*y) + z*z, sqrt, /; the f32 view is astype(float32)."""
+    w = np.asarray(w, np.float64)
+    if w[0] not in (0.0, 1.0, 2.0, 3.0):
+        return 1, None, None
+    if not np.isfinite(w[1:21]).all():
+        return 2, None, None
+    kind = int(w[0])
+    round_ = kind in (0, 1)
+    if w[17] < 0.0 or (round_ and w[16] < 0.0):
+        return 3, None, None
+    a, b, v = w[1:4].copy(), w[4:7].copy(), w[18:21].copy()
+    u = np.zeros(9)
+    if kind == 3:
+        b = _unit(w[4:7])
+        if b is None:
+            return 4, None, None
+    if kind == 2:
+        for j in range(3):
+            if w[4 + j] < 0.0:
+                return 5, None, None
+            uj = _unit(w[7 + 3 * j:10 + 3 * j])
+            if uj is None:
+                return 6, None, None
+            u[3 * j:3 * j + 3] = uj
+        for i in range(3):
+            for j in range(i + 1, 3):
+                ui, uj = u[3 * i:3 * i + 3], u[3 * j:3 * j + 3]
+                if abs((ui[0] * uj[0] + ui[1] * uj[1]) + ui[2] * uj[2]) > 1e-5:
+                    return 7, None, None
+    d = np.concatenate([a, b, u, [w[16] if round_ else 0.0, w[17]], v])
+    tail = np.array([kind, 0], "<i4").tobytes()
+    return 0, d.astype("<f8").tobytes() + tail, d.astype("<f4").tobytes() + tail
+
+
+def refusal(r):
+    """views' code for one row of 24 floats (f64 arithmetic on the f32 values); an empty slot (kind -1) is not a collider: None"""
+    r = np.asarray(r, np.float32).astype(np.float64)
+    return None if r[0] == -1.0 else views(r[:21])[0]
+
+
 def row_ok(r):
     """tetsim_set_colliders' validity rules on one row of 24 floats (f64 arithmetic on the f32 values, in the host's order).  An empty
     slot (kind -1) is not a collider: False."""
-    r = np.asarray(r, np.float32).astype(np.float64)
-    if r[0] not in (0.0, 1.0, 2.0, 3.0):
-        return False
-    if not np.isfinite(r[:21]).all():
-        return False
-    kind = int(r[0])
-    round_ = kind in (0, 1)
-    if r[17] < 0.0 or (round_ and r[16] < 0.0):
-        return False
-    if kind == 3 and _unit(r[4:7]) is None:
-        return False
-    if kind == 2:
-        if (r[4:7] < 0.0).any():
-            return False
-        u = [_unit(r[7 + 3 * j:10 + 3 * j]) for j in range(3)]
-        if any(x is None for x in u):
-            return False
-        for i in range(3):
-            for j in range(i + 1, 3):
-                if abs((u[i][0] * u[j][0] + u[i][1] * u[j][1]) + u[i][2] * u[j][2]) > 1e-5:
-                    return False
-    return True
+    return refusal(r) == 0
 
 
 def lists_from_rows(rws):

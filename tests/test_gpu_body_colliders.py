@@ -15,7 +15,7 @@ import crowd
 from test_gpu_body_grabs import BATCH_CASES, LARGE_CASES, _code, _hip_runtime, _path, _same, _same_bodies, _state, _target, _three
 from test_gpu_colliders import DT, GRAB_ID, PP, SUB, _mesh
 from test_gpu_crowd import Sampled
-from tetsim_amd import SoftBodyHIP, TetSimError, body_collider_rows
+from tetsim_amd import SoftBodyHIP, TetSimError, body_collider_rows, make_lattice
 from tetsim_amd import _capi as capi
 
 pytestmark = pytest.mark.gpu
@@ -368,3 +368,47 @@ def test_states_and_errors():
     assert _same(_state(a), _state(twin))
     torch.cuda.synchronize()
     assert hip.hipFree(short) == 0
+
+
+# ---- 9. the seven refusals, from both set calls ------------------------------------------------------------------------------------------------
+# (what is wrong with the collider, tetsim_set_colliders' text, tetsim_set_body_colliders' text) in the order the library checks
+_REFUSALS = [
+    (dict(kind=7), "unknown kind", "unknown kind (0, 1, 2, 3, or -1 for an empty slot)"),
+    (dict(kind="sphere", axes=[[1.0, 0.0, 0.0], [0.0, float("inf"), 0.0], [0.0, 0.0, 1.0]]), "non-finite value", "non-finite value"),
+    (dict(kind="capsule", radius=-0.1), "negative radius or friction", "negative radius or friction"),
+    (dict(kind="plane", b=[0.0, 0.0, 0.0]), "zero-length plane normal", "zero-length plane normal"),
+    (dict(kind="box", b=[0.1, -0.1, 0.1]), "negative half-extent", "negative half-extent"),
+    (dict(kind="box", b=[0.1, 0.1, 0.1], axes=[[1.0, 0.0, 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, 0.0]]), "zero-length box axis", "zero-length box axis"),
+    (dict(kind="box", b=[0.1, 0.1, 0.1], axes=[[1.0, 0.0, 0.0], [0.01, 1.0, 0.0], [0.0, 0.0, 1.0]]), "box axes are not orthogonal", "box axes are not orthogonal"),
+]
+
+
+def test_both_set_calls_refuse_the_seven_reasons_in_their_own_words_and_keep_what_was_set():
+    """For each of the seven reasons a collider is refused, setColliders on a solo handle and setBodyColliders on a batch raise EINVAL with
+    the text commit 50eac02 gives -- recorded there, not derived from the routine the two calls now share -- and the list / the table set
+    before stays in force: after every refusal one substep equals, on bits, the twin's that never saw the refused call."""
+    v, t = make_lattice(5, y0=0.3)
+    kw = dict(solver="polar", precision="fast")
+    lo = float(v[:, 1].min())
+    good = ref.lists_from_rows(ref.rows([[dict(kind="plane", a=[0.0, lo + 0.02, 0.0], b=[0.1, 1.0, 0.05], friction=5.0)]]))[0]   # cuts the body's lowest layer: met at once
+    solo, solo_twin, free = (SoftBodyHIP(v, t, None, dict(PP), **kw) for _ in range(3))
+    batch, batch_twin = (SoftBodyHIP.batch([(v, t)] * 2, dict(PP), **kw) for _ in range(2))
+    rows = ref.rows([good, good], 2)
+    for body in (solo, solo_twin):
+        body.setColliders(good)
+    for body in (batch, batch_twin):
+        body.setBodyColliders(rows)
+    for k, (bad, solo_text, row_text) in enumerate(_REFUSALS):
+        assert ref.refusal(ref.row(bad)) == k + 1
+        with pytest.raises(TetSimError) as e:
+            solo.setColliders(good + [bad])
+        assert e.value.code == capi.EINVAL and str(e.value) == "tetsim error 1: collider 1: " + solo_text
+        wrong = rows.copy()
+        wrong[1, 1] = ref.row(bad)
+        with pytest.raises(TetSimError) as e:
+            batch.setBodyColliders(wrong)
+        assert e.value.code == capi.EINVAL and str(e.value) == "tetsim error 1: body 1, slot 1: " + row_text
+        for body in (solo, solo_twin, batch, batch_twin, free):
+            body.simulate(DT, PP)
+        assert _same(_state(solo), _state(solo_twin)) and _same(_state(batch), _state(batch_twin)), k
+    assert _same_bodies(batch, [solo, solo]) == [] and not _same(_state(solo), _state(free))   # ... and the list was met

@@ -158,7 +158,7 @@ SYMBOLS = [
     "tetsim_comm_unique_id", "tetsim_comm_init", "tetsim_comm_info", "tetsim_comm_selftest", "tetsim_comm_probe", "tetsim_group_step_n", "tetsim_halo_exchange_local", "tetsim_get_halo_plan",
     "tetsim_halo_p2p_export", "tetsim_halo_p2p_connect",
     "tetsim_halo_export", "tetsim_halo_import", "tetsim_prep_levels", "tetsim_prep_colours", "tetsim_prep_clusters",
-    "tetsim_prep_tiles", "tetsim_prep_tile_tables", "tetsim_prep_slot_table", "tetsim_prep_call_tiles", "tetsim_prep_call_schedule", "tetsim_prep_check_call_schedule", "tetsim_prep_ref_grab_texels", "tetsim_prep_rest", "tetsim_prep_partition", "tetsim_prep_partition_quality", "tetsim_plan_create", "tetsim_plan_destroy", "tetsim_plan_sizes",
+    "tetsim_prep_tiles", "tetsim_prep_tile_tables", "tetsim_prep_collider_views", "tetsim_prep_slot_table", "tetsim_prep_call_tiles", "tetsim_prep_call_schedule", "tetsim_prep_check_call_schedule", "tetsim_prep_ref_grab_texels", "tetsim_prep_rest", "tetsim_prep_partition", "tetsim_prep_partition_quality", "tetsim_plan_create", "tetsim_plan_destroy", "tetsim_plan_sizes",
     "tetsim_plan_arrays", "tetsim_plan_neighbour", "tetsim_plan_neighbour_ids",
     "tetsim_plan_create_deep", "tetsim_plan_layers", "tetsim_plan_neighbour_layer2", "tetsim_plan_neighbour_layer2_ids",
     "tetsim_raycast_visual", "tetsim_start_grab_ray", "tetsim_read_visual_bounding_sphere", "tetsim_prep_boundary_surface",
@@ -191,7 +191,7 @@ OPTIONAL_SYMBOLS = ("tetsim_set_colliders", "tetsim_raycast_visual", "tetsim_sta
                     "tetsim_body_poses_device", "tetsim_read_body_poses", "tetsim_prep_pose_table",
                     "tetsim_raycast_visual_bvh_device", "tetsim_prep_bvh",
                     "tetsim_closest_visual_device", "tetsim_closest_visual",
-                    "tetsim_touch_bodies_device", "tetsim_read_body_touch", "tetsim_touch_particles_device")
+                    "tetsim_touch_bodies_device", "tetsim_read_body_touch", "tetsim_touch_particles_device", "tetsim_prep_collider_views")
 
 _lib = None
 
@@ -257,6 +257,8 @@ def lib():
     L.tetsim_set_grab.argtypes = [H, i32, fp]
     if hasattr(L, "tetsim_set_colliders"):   # (additive to ABI 5: a library built before it lacks the symbol and still loads)
         L.tetsim_set_colliders.argtypes = [H, C.POINTER(TetSimCollider), u32]
+    if hasattr(L, "tetsim_prep_collider_views"):   # (host only: the routine behind both collider set calls, for tests)
+        L.tetsim_prep_collider_views.argtypes = [C.POINTER(TetSimCollider), u32, i32, ip, C.c_void_p, C.c_void_p]
     L.tetsim_start_grab.argtypes = [H, fp, ip]
     if hasattr(L, "tetsim_raycast_visual"):   # (additive to ABI 5, like the colliders)
         L.tetsim_raycast_visual.argtypes = [H, C.c_void_p, u32, C.c_void_p]

@@ -17,6 +17,8 @@
 //                      rotation (Horn's quaternion by a fixed Jacobi procedure), angular velocity and momentum
 //   touch.hip          touch sensing on the device (tetsim_touch_bodies_device / _particles_device): signed distance and normal of every
 //                      particle against its body's colliders, per body and slot or per particle -- read-only, over the particle chunks
+//   body_rows.h        what the three per-body tables below share: the one collider routine (also tetsim_set_colliders') and the one conversion
+//                      of a row of parameters (also fill_params'), compiled for both sides; the host steps of a set call
 //   body_grabs.hip     one held particle per body of a batch, set from host or device memory (tetsim_set_body_grabs / _device): the table the
 //                      particle passes read; the nearest particle of every body on the device (tetsim_nearest_particles_device)
 //   body_params.hip   physics parameters per body of a batch, set from host or device memory (tetsim_set_body_params / _device)

@@ -2,8 +2,10 @@
 // device (tetsim_nearest_particles_device).  The table the particle passes read (dev_common.h: grab_pick; nh_kernels.inc: post_vertex;
 // pj_quad.hip: load_qparams) is made here: the body of every particle in DEVICE particle order, a constant, and one 16-byte row per body,
 // {device particle or -1, target xyz}, written by one small kernel per set call.  Built with -ffp-contract=off: the nearest query's squared
-// distance is tetsim_nearest_particle's (util_kernels.hip: nearest_kernel), every multiply and add rounded on its own.  See body.h.
+// distance is tetsim_nearest_particle's (util_kernels.hip: nearest_kernel), every multiply and add rounded on its own.  The host steps of
+// the set calls are body_rows.h's (set_rows_device, launch_row_chunks), shared with the other per-body tables.  See body.h.
 #include "body_reduce.h"
+#include "body_rows.h"
 
 #include <cfloat>
 
@@ -70,11 +72,10 @@ __global__ __launch_bounds__(256) void grab_rows_kernel(const int32_t* __restric
 }
 // The host variant's rows travel as kernel arguments, a chunk per launch (checked and translated on the host); `none`: every row to "none"
 constexpr uint32_t kRowsPerLaunch = 128;
-struct RowChunk { int4 row[kRowsPerLaunch]; };
-static_assert(sizeof(RowChunk) + 64 <= kKernelArgLimit, "a chunk of rows is a kernel argument");
-__global__ __launch_bounds__(kRowsPerLaunch) void grab_rows_value_kernel(RowChunk c, int4* __restrict__ rows, uint32_t first, uint32_t count, uint32_t none) {
+using Chunk = RowChunk<int4, 1u, kRowsPerLaunch>;
+__global__ __launch_bounds__(kRowsPerLaunch) void grab_rows_value_kernel(Chunk c, int4* __restrict__ rows, uint32_t first, uint32_t count, uint32_t none) {
     const uint32_t i = threadIdx.x;
-    if (i < count) rows[first + i] = none ? make_int4(-1, 0, 0, 0) : c.row[i];
+    if (i < count) rows[first + i] = none ? make_int4(-1, 0, 0, 0) : c.row[i][0];
 }
 
 // ---- nearest particle per body: argmin of Softbody.js:279-291 over each body's particles -------------------------------------------------
@@ -146,13 +147,9 @@ int check_grab_state(tetsim_body* h) {
 
 // rows [first, first + count) from the host, or "none" for all of them, on h->stream
 int launch_value_rows(tetsim_body* h, const std::vector<int4>* rows, uint32_t nb) {
-    for (uint32_t f = 0; f < nb; f += kRowsPerLaunch) {
-        const uint32_t count = std::min(kRowsPerLaunch, nb - f);
-        RowChunk c{};
-        if (rows) std::memcpy(c.row, rows->data() + f, count * sizeof(int4));
-        hipLaunchKernelGGL(grab_rows_value_kernel, dim3(1), dim3(kRowsPerLaunch), 0, h->stream, c, h->d_grab_rows, f, count, rows ? 0u : 1u);
-    }
-    return launched(h);
+    return launch_row_chunks<Chunk>(h, rows ? rows->data() : nullptr, nb, 1u, [&](const Chunk& c, uint32_t first, uint32_t count) {
+        hipLaunchKernelGGL(grab_rows_value_kernel, dim3(1), dim3(kRowsPerLaunch), 0, h->stream, c, h->d_grab_rows, first, count, rows ? 0u : 1u);
+    });
 }
 
 }  // namespace
@@ -200,34 +197,24 @@ int tetsim_set_body_grabs_device(tetsim_handle h, const void* particles, const v
         return tetsim_set_body_grabs(h, nullptr, nullptr);
     }
     if (!targets) return fail(h, TETSIM_EINVAL, "targets is null");
-    if (int rc = check_grab_state(h)) return rc;
-    if (!record_stride_ok(target_stride, 12u, 4u)) return fail(h, TETSIM_EINVAL, "target_stride must be 0 or a multiple of 4 of at least 12");
-    if (int rc = device_call_guard(h)) return rc;
     const uint32_t nb = num_bodies(h);
-    const uint64_t stride = target_stride ? target_stride : 12u;
-    if (int rc = check_device_records(h, particles, 4u, nb, 4u, 4u, "particles")) return rc;
-    if (int rc = check_device_records(h, targets, stride, nb, 12u, 4u, "targets")) return rc;
-    if (body_mask) {
-        if (int rc = check_device_span(h, body_mask, nb, "body_mask", std::to_string(nb) + " bytes (one per body) do not fit the allocation it points into")) return rc;
-    }
-    // ---- every argument is good
-    if (int rc = ensure_grab_table(h)) return rc;
-    const int rc = on_caller_stream(h, caller_stream, [&]() -> int {
-        hipLaunchKernelGGL(grab_rows_kernel, dim3((nb + 255u) / 256u), dim3(256), 0, h->stream, static_cast<const int32_t*>(particles), static_cast<const char*>(targets),
-                           stride, static_cast<const uint8_t*>(body_mask), h->d_body_first, h->d_api2dev, h->d_grab_rows, nb);
-        return launched(h);
-    });
-    if (rc == 0) h->body_grabs_on = true;
-    return rc;
+    return set_rows_device(
+        h, [&] { return check_grab_state(h); }, {{particles, "particles", nb, 4u, 4u, 0u, nullptr}, {targets, "targets", nb, 12u, 4u, target_stride, "target_stride"}}, body_mask,
+        caller_stream, [&] { return ensure_grab_table(h); },
+        [&] {
+            return launch_per_body(h, nb, grab_rows_kernel, static_cast<const int32_t*>(particles), static_cast<const char*>(targets), resolved_stride(target_stride, 12u),
+                                   static_cast<const uint8_t*>(body_mask), h->d_body_first, h->d_api2dev, h->d_grab_rows, nb);
+        },
+        &h->body_grabs_on);
 }
 
 int tetsim_nearest_particles_device(tetsim_handle h, const void* points, uint64_t point_stride, void* ids, void* dist2, void* caller_stream) {
     if (!h) return TETSIM_EINVAL;
     if (!points || !ids) return fail(h, TETSIM_EINVAL, "null argument");
-    if (!record_stride_ok(point_stride, 12u, 4u)) return fail(h, TETSIM_EINVAL, "point_stride must be 0 or a multiple of 4 of at least 12");
+    if (int rc = check_record_stride(h, "point_stride", point_stride, 12u, 4u)) return rc;
     if (int rc = device_call_guard(h)) return rc;
     const uint32_t nb = num_bodies(h);
-    const uint64_t stride = point_stride ? point_stride : 12u;
+    const uint64_t stride = resolved_stride(point_stride, 12u);
     if (int rc = check_device_records(h, points, stride, nb, 12u, 4u, "points")) return rc;
     if (int rc = check_device_records(h, ids, 4u, nb, 4u, 4u, "ids")) return rc;
     if (dist2) { if (int rc = check_device_records(h, dist2, 8u, nb, 8u, 8u, "dist2")) return rc; }

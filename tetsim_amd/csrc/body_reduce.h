@@ -5,7 +5,7 @@
 #pragma once
 #include <type_traits>
 
-#include "body.h"
+#include "body_rows.h"
 
 namespace tetsim {
 
@@ -105,10 +105,9 @@ inline int ensure_chunk_table(tetsim_body* h, ChunkKind kind) {
 // then the records (device_io.hip: check_device_records).  *stride: the resolved stride.
 inline int check_dst_rows(tetsim_body* h, const void* dst, uint64_t row_stride, uint32_t rows, uint64_t row_bytes, uint32_t align, uint64_t* stride) {
     if (!dst) return fail(h, TETSIM_EINVAL, "dst is null");
-    if (!record_stride_ok(row_stride, row_bytes, align))
-        return fail(h, TETSIM_EINVAL, "row_stride must be 0 or a multiple of " + std::to_string(align) + " of at least " + std::to_string(row_bytes));
+    if (int rc = check_record_stride(h, "row_stride", row_stride, row_bytes, align)) return rc;
     if (int rc = device_call_guard(h)) return rc;
-    *stride = row_stride ? row_stride : row_bytes;
+    *stride = resolved_stride(row_stride, row_bytes);
     return check_device_records(h, dst, *stride, rows, row_bytes, align, "dst");
 }
 

@@ -4,7 +4,7 @@
 // stream as the device import is (body.h: on_caller_stream).  Rows and mask are device memory that the host never reads; a row finds its
 // body through the snapshots' tables (snapshot.hip: ensure_body_tables).  Built with -ffp-contract=off: the definition in the header is f64 with
 // every operation rounded on its own, and tests/place_ref.py reproduces it value for value in numpy.  See body.h.
-#include "body.h"
+#include "body_rows.h"
 
 using namespace tetsim;
 
@@ -261,14 +261,12 @@ int tetsim_place_bodies_device(tetsim_handle h, const void* rows, uint64_t row_s
     if (!rows) return fail(h, TETSIM_EINVAL, "rows is null");
     if (flags & ~static_cast<uint32_t>(TETSIM_PLACE_KEEP_VELOCITY)) return fail(h, TETSIM_EINVAL, "unknown flag bits (TETSIM_PLACE_KEEP_VELOCITY is the only one)");
     constexpr uint64_t kRowBytes = 4ull * TETSIM_PLACE_WIDTH;
-    if (!record_stride_ok(row_stride, kRowBytes, 4u)) return fail(h, TETSIM_EINVAL, "row_stride must be 0 or a multiple of 4 of at least 64");
+    if (int rc = check_record_stride(h, "row_stride", row_stride, kRowBytes, 4u)) return rc;
     if (int rc = device_call_guard(h)) return rc;
     const uint32_t nb = h->info.num_bodies;
-    const uint64_t stride = row_stride ? row_stride : kRowBytes;
+    const uint64_t stride = resolved_stride(row_stride, kRowBytes);
     if (int rc = check_device_records(h, rows, stride, nb, kRowBytes, 4u, "rows")) return rc;
-    if (body_mask) {
-        if (int rc = check_device_span(h, body_mask, nb, "body_mask", std::to_string(nb) + " bytes (one per body) do not fit the allocation it points into")) return rc;
-    }
+    if (int rc = check_body_mask(h, body_mask, nb)) return rc;
     PlaceTable t = make_table(h, rows, stride, body_mask, flags);
     if (int rc = check_sections(h, t)) return rc;
     // ---- every argument is good: from here on only allocation and HIP itself can fail

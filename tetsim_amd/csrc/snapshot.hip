@@ -2,7 +2,7 @@
 // buffer per entry of state_sections() (tetsim_state.hip), what a checkpoint keeps on the host -- captured and restored for CHOSEN bodies of a
 // batch by ONE copy kernel on the handle's stream, ordered against the caller's stream as the device export and import are (body.h:
 // on_caller_stream).  The mask of the chosen bodies is device memory that the host never reads.  See body.h.
-#include "body.h"
+#include "body_rows.h"
 
 using namespace tetsim;
 
@@ -187,11 +187,7 @@ int check_call(tetsim_body* h, tetsim_snapshot_s* s, const void* mask) {
     if (h->partitioned) return fail(h, TETSIM_ESTATE, kPartitionedIo);
     if (s->owner != h) return fail(h, TETSIM_EINVAL, "the snapshot belongs to another handle");
     HIPCHK(h, hipSetDevice(h->opt.device));
-    if (mask) {
-        const uint32_t nb = h->info.num_bodies;
-        if (int rc = check_device_span(h, mask, nb, "body_mask", std::to_string(nb) + " bytes (one per body) do not fit the allocation it points into")) return rc;
-    }
-    return 0;
+    return check_body_mask(h, mask, h->info.num_bodies);
 }
 
 void free_snapshot(tetsim_snapshot_s* s) {

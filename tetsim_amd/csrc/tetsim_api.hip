@@ -3,7 +3,7 @@
 // measurement: tetsim_measure.hip.  See body.h for all translation units.
 #include <mutex>
 
-#include "body.h"
+#include "body_rows.h"
 
 using namespace tetsim;
 
@@ -58,12 +58,15 @@ void ref_grab_texels(int32_t grab_id, uint32_t num_elems, uint32_t num_particles
 void fill_params(const tetsim_body* h, double dt, const TetSimParams& p, DevParams* o) {
     std::memset(o, 0, sizeof(*o));
     o->dt = static_cast<float>(dt);
-    o->gravity = static_cast<float>(p.gravity);
-    o->friction = static_cast<float>(p.friction);
-    const bool fixed = h->opt.solver == TETSIM_SOLVER_POLAR_JACOBI && (h->opt.flags & TETSIM_FLAG_REF_FIXED_BOUNDS);
+    // the f32 view of the call's parameters: the conversion body_params.hip's rows get too (body_rows.h), as they are -- nothing is refused here
+    BodyParamsD pd;
+    BodyParamsF pf;
+    params_views(reinterpret_cast<const double*>(&p), fixed_bounds(h), &pd, &pf);
+    o->gravity = pf.gravity;
+    o->friction = pf.friction;
     for (int c = 0; c < 3; c++) {
-        o->lo[c] = fixed ? ref_fixed_lo(c) : static_cast<float>(p.worldBounds[c]);   // (dev_common.h: the box body_params.hip's rows use too)
-        o->hi[c] = fixed ? ref_fixed_hi(c) : static_cast<float>(p.worldBounds[3 + c]);
+        o->lo[c] = pf.lo[c];
+        o->hi[c] = pf.hi[c];
         o->d_lo[c] = p.worldBounds[c];
         o->d_hi[c] = p.worldBounds[3 + c];
         o->grab[c] = h->grab_pos[c];

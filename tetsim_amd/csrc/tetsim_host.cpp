@@ -1,5 +1,5 @@
 // tetsim_host.cpp -- entry points that never touch a device: preprocessing, partition plans, the .tetsim container.
-#include "body.h"
+#include "body_rows.h"
 
 using namespace tetsim;
 
@@ -159,6 +159,29 @@ int tetsim_prep_tile_tables(const float* verts, uint32_t nv, const int32_t* tets
     if (ranges) std::copy(B.lc_range.begin(), B.lc_range.end(), ranges);
     if (tet_pos) std::copy(B.tet_pos.begin(), B.tet_pos.end(), tet_pos);
     if (run_first) std::copy(B.lc_first.begin(), B.lc_first.end(), run_first);
+    return 0;
+}
+int tetsim_prep_collider_views(const TetSimCollider* colliders, uint32_t count, int32_t as_rows, int32_t* codes, void* views_f64, void* views_f32) {
+    if ((count && !colliders) || !codes || !views_f64 || !views_f32) return TETSIM_EINVAL;
+    static_assert(sizeof(DevColliderD) == TETSIM_COLLIDER_VIEW_F64_BYTES && sizeof(DevColliderF) == TETSIM_COLLIDER_VIEW_F32_BYTES, "the views' sizes are in the header");
+    for (uint32_t k = 0; k < count; k++) {
+        const TetSimCollider& c = colliders[k];
+        DevColliderD d;
+        DevColliderF f;
+        std::memset(&d, 0, sizeof d);
+        std::memset(&f, 0, sizeof f);
+        if (as_rows) {   // the collider as a row of tetsim_set_body_colliders holds it: every field an f32
+            float r[21] = {static_cast<float>(c.kind)};
+            for (int j = 0; j < 3; j++) { r[1 + j] = static_cast<float>(c.a[j]); r[4 + j] = static_cast<float>(c.b[j]); r[18 + j] = static_cast<float>(c.velocity[j]); }
+            for (int j = 0; j < 9; j++) r[7 + j] = static_cast<float>(c.axes[j]);
+            r[16] = static_cast<float>(c.radius); r[17] = static_cast<float>(c.friction);
+            codes[k] = collider_view(r[0], r + 1, r + 4, r + 7, r[16], r[17], r + 18, &d);
+        } else codes[k] = collider_view(static_cast<double>(c.kind), c.a, c.b, c.axes, c.radius, c.friction, c.velocity, &d);
+        if (codes[k] == kColliderOk) f = collider_f32(d);
+        else std::memset(&d, 0, sizeof d);
+        std::memcpy(static_cast<char*>(views_f64) + static_cast<size_t>(k) * sizeof d, &d, sizeof d);
+        std::memcpy(static_cast<char*>(views_f32) + static_cast<size_t>(k) * sizeof f, &f, sizeof f);
+    }
     return 0;
 }
 int tetsim_prep_slot_table(const int32_t* tets, uint32_t nt, uint32_t nv, int32_t ref_quirk, int32_t* slots, uint32_t* dropped) {

@@ -1,6 +1,6 @@
 // tetsim_visual.hip -- C ABI, part 3 (include/tetsim.h): the embedded visual mesh (skinning, three.js computeVertexNormals; its rows
 // leave through device_io.hip) and the grab interface (pin a particle; nearest-particle query on the device).  See body.h.
-#include "body.h"
+#include "body_rows.h"
 
 using namespace tetsim;
 
@@ -248,56 +248,25 @@ int tetsim_set_grab(tetsim_handle h, int32_t id, const float xyz[3]) {
     return 0;
 }
 
-// Kinematic colliders: checked and normalised in f64 as a whole, then they replace the list (a rejected call leaves the old one).
+// Kinematic colliders: checked and normalised in f64 as a whole (body_rows.h: collider_view, the routine the body colliders' set kernel
+// runs per row), then they replace the list (a rejected call leaves the old one).
 int tetsim_set_colliders(tetsim_handle h, const TetSimCollider* colliders, uint32_t count) {
     if (!h) return TETSIM_EINVAL;
     if (count > TETSIM_MAX_COLLIDERS) return fail(h, TETSIM_EINVAL, "more than TETSIM_MAX_COLLIDERS colliders");
     if (count && !colliders) return fail(h, TETSIM_EINVAL, "colliders is null");
     if (count && h->body_colliders_on) return fail(h, TETSIM_ESTATE, kBodyCollidersOn);   // (clearing the handle's list, count 0, stays legal)
+    static const char* const kRefusal[] = {"unknown kind", "non-finite value", "negative radius or friction", "zero-length plane normal", "negative half-extent",
+                                           "zero-length box axis", "box axes are not orthogonal"};
     DevColliderD d[kMaxColliders] = {};
     DevColliderF f[kMaxColliders] = {};
     for (uint32_t k = 0; k < count; k++) {
         const TetSimCollider& c = colliders[k];
         const std::string at = "collider " + std::to_string(k) + ": ";
-        if (c.kind < TETSIM_COLLIDER_SPHERE || c.kind > TETSIM_COLLIDER_PLANE) return fail(h, TETSIM_EINVAL, at + "unknown kind");
+        const int why = collider_view(static_cast<double>(c.kind), c.a, c.b, c.axes, c.radius, c.friction, c.velocity, &d[k]);
+        if (why == kColliderKind) return fail(h, TETSIM_EINVAL, at + kRefusal[why - 1]);
         if (c.reserved != 0) return fail(h, TETSIM_EINVAL, at + "reserved must be 0");
-        const bool box = c.kind == TETSIM_COLLIDER_BOX, plane = c.kind == TETSIM_COLLIDER_PLANE, round = !box && !plane;
-        bool finite = std::isfinite(c.radius) && std::isfinite(c.friction);   // every value, used by the kind or not
-        for (int j = 0; j < 3; j++) finite = finite && std::isfinite(c.a[j]) && std::isfinite(c.b[j]) && std::isfinite(c.velocity[j]);
-        for (int j = 0; j < 9; j++) finite = finite && std::isfinite(c.axes[j]);
-        if (!finite) return fail(h, TETSIM_EINVAL, at + "non-finite value");
-        if (c.friction < 0.0 || (round && c.radius < 0.0)) return fail(h, TETSIM_EINVAL, at + "negative radius or friction");
-        DevColliderD& o = d[k];
-        o.kind = c.kind;
-        o.radius = round ? c.radius : 0.0;
-        o.friction = c.friction;
-        for (int j = 0; j < 3; j++) { o.a[j] = c.a[j]; o.b[j] = c.b[j]; o.v[j] = c.velocity[j]; }
-        auto unit = [](const double* v, double* out) {   // v / sqrt(v . v); false for a zero vector
-            const double l2 = (v[0] * v[0] + v[1] * v[1]) + v[2] * v[2];
-            if (!(l2 > 0.0)) return false;
-            const double l = std::sqrt(l2);
-            for (int j = 0; j < 3; j++) out[j] = v[j] / l;
-            return true;
-        };
-        if (plane && !unit(c.b, o.b)) return fail(h, TETSIM_EINVAL, at + "zero-length plane normal");
-        if (box) {
-            for (int j = 0; j < 3; j++) {
-                if (c.b[j] < 0.0) return fail(h, TETSIM_EINVAL, at + "negative half-extent");
-                if (!unit(c.axes + 3 * j, o.u + 3 * j)) return fail(h, TETSIM_EINVAL, at + "zero-length box axis");
-            }
-            for (int i = 0; i < 3; i++)
-                for (int j = i + 1; j < 3; j++) {
-                    const double* ui = o.u + 3 * i;
-                    const double* uj = o.u + 3 * j;
-                    if (std::fabs((ui[0] * uj[0] + ui[1] * uj[1]) + ui[2] * uj[2]) > 1e-5) return fail(h, TETSIM_EINVAL, at + "box axes are not orthogonal");
-                }
-        }
-        DevColliderF& g = f[k];   // the f32 view: every value rounded once
-        g.kind = o.kind;
-        g.radius = static_cast<float>(o.radius);
-        g.friction = static_cast<float>(o.friction);
-        for (int j = 0; j < 3; j++) { g.a[j] = static_cast<float>(o.a[j]); g.b[j] = static_cast<float>(o.b[j]); g.v[j] = static_cast<float>(o.v[j]); }
-        for (int j = 0; j < 9; j++) g.u[j] = static_cast<float>(o.u[j]);
+        if (why != kColliderOk) return fail(h, TETSIM_EINVAL, at + kRefusal[why - 1]);
+        f[k] = collider_f32(d[k]);
     }
     h->n_colliders = count;
     for (uint32_t k = 0; k < kMaxColliders; k++) { h->col[k] = f[k]; h->d_col[k] = d[k]; }
@@ -544,8 +513,8 @@ int raycast_device(tetsim_handle h, const void* rays, uint64_t ray_stride, const
     if (!h) return TETSIM_EINVAL;
     if (count && (!rays || !hits)) return fail(h, TETSIM_EINVAL, "null argument");
     constexpr uint64_t ray_row = sizeof(TetSimRay), hit_row = sizeof(TetSimRayHit);
-    if (!record_stride_ok(ray_stride, ray_row, 8u)) return fail(h, TETSIM_EINVAL, "ray_stride must be 0 or a multiple of 8 of at least 64");
-    if (!record_stride_ok(hit_stride, hit_row, 8u)) return fail(h, TETSIM_EINVAL, "hit_stride must be 0 or a multiple of 8 of at least 48");
+    if (int rc = check_record_stride(h, "ray_stride", ray_stride, ray_row, 8u)) return rc;
+    if (int rc = check_record_stride(h, "hit_stride", hit_stride, hit_row, 8u)) return rc;
     if (int rc = check_query_state(h, true)) return rc;
     if (ray_body && h->tri_spans_bodies)
         return fail(h, TETSIM_ESTATE, "a triangle of the visual mesh has rows of different bodies: it belongs to no body's own surface (cast without ray_body)");
@@ -597,8 +566,8 @@ static_assert(sizeof(TetSimPointQuery) == sizeof(PointQueryIn) && sizeof(TetSimC
 int closest_check(tetsim_handle h, const void* queries, uint64_t query_stride, const void* query_body, uint32_t count, void* out, uint64_t out_stride, ClosestIo* io) {
     if (count && (!queries || !out)) return fail(h, TETSIM_EINVAL, "null argument");
     constexpr uint64_t query_row = sizeof(TetSimPointQuery), out_row = sizeof(TetSimClosest);
-    if (!record_stride_ok(query_stride, query_row, 8u)) return fail(h, TETSIM_EINVAL, "query_stride must be 0 or a multiple of 8 of at least 32");
-    if (!record_stride_ok(out_stride, out_row, 8u)) return fail(h, TETSIM_EINVAL, "out_stride must be 0 or a multiple of 8 of at least 64");
+    if (int rc = check_record_stride(h, "query_stride", query_stride, query_row, 8u)) return rc;
+    if (int rc = check_record_stride(h, "out_stride", out_stride, out_row, 8u)) return rc;
     if (int rc = check_query_state(h, true)) return rc;
     if (query_body && h->tri_spans_bodies)
         return fail(h, TETSIM_ESTATE, "a triangle of the visual mesh has rows of different bodies: it belongs to no body's own surface (query without query_body)");
@@ -729,7 +698,7 @@ int tetsim_prep_bvh(const float* positions, uint32_t nvis, const int32_t* tri_id
 int tetsim_visual_bounding_spheres_device(tetsim_handle h, void* dst, uint64_t row_stride, void* caller_stream) {
     if (!h) return TETSIM_EINVAL;
     constexpr uint64_t row = 4ull * sizeof(double);
-    if (!record_stride_ok(row_stride, row, 8u)) return fail(h, TETSIM_EINVAL, "row_stride must be 0 or a multiple of 8 of at least 32");
+    if (int rc = check_record_stride(h, "row_stride", row_stride, row, 8u)) return rc;
     if (!dst) return fail(h, TETSIM_EINVAL, "dst is null");
     if (int rc = check_query_state(h, false)) return rc;
     if (int rc = device_call_guard(h)) return rc;

@@ -468,6 +468,28 @@ class SoftBodyHIP:
             return dev, torch.cuda.current_stream(dev).cuda_stream
         return dev, int(getattr(stream, "cuda_stream", stream))
 
+    def _out_rows(self, torch, dev, key, out, shape, dtype, name="out", align=None, packed=False):
+        """Where a device-side call writes: the tensor cached under `key` (allocated once; anew when its first dimension changed), or the
+        caller's `out` behind the checks -- dtype, device, shape (rows,) or (rows, width); rows contiguous and not overlapping, the row
+        stride free unless `packed`; align: rows and row stride multiples of that many bytes."""
+        n = shape[0]
+        if out is None:
+            out = self._export_cache.get(key)
+            if out is None or out.shape[0] != n:
+                out = self._export_cache[key] = torch.empty(shape, dtype=dtype, device=dev)
+            return out
+        ok = isinstance(out, torch.Tensor) and out.dtype == dtype and out.device == dev and tuple(out.shape) == tuple(shape)
+        if ok and len(shape) == 2:
+            ok = not (n and out.stride(1) != 1) and not (n > 1 and out.stride(0) < shape[1])
+        if ok:
+            ok = not (n > 1 and out.stride(0) < 1) and not (packed and not out.is_contiguous())
+        if ok and align:
+            ok = not (n > 1 and out.stride(0) * out.element_size() % align) and not (n and out.data_ptr() % align)
+        if not ok:
+            raise ValueError("%s must be a %s tensor on %s of shape %s with contiguous, non-overlapping%s rows"
+                             % (name, dtype, dev, tuple(shape), ", %d-byte aligned" % align if align else ""))
+        return out
+
     def exportTensors(self, fields=("pos",), out=None, stream=None):
         """{name: torch.Tensor} of the named fields (_EXPORT_FIELDS: pos, vel, prevPos, quats, visPos, visNormals, visVertexNormals) on
         the handle's device, float32 [rows, 3] ([rows, 4] for quats), bit for bit what the host read of the same name returns -- without
@@ -478,19 +500,13 @@ class SoftBodyHIP:
         import torch
         dev, s = self._torch_stream(torch, stream)
         names = [fields] if isinstance(fields, str) else list(fields)
-        cache = self._export_cache
         arr = (capi.TetSimDeviceField * max(1, len(names)))()
         res = {}
         for f, name in zip(arr, names):
             field, rows, width = _EXPORT_FIELDS[name]
             n = int(getattr(self.info, rows))
-            t = out.get(name) if out is not None else None
-            if t is None:
-                t = cache.get(name)
-                if t is None or t.shape[0] != n:   # (num_vis_verts changes when a visual mesh is attached)
-                    t = cache[name] = torch.empty((n, width), dtype=torch.float32, device=dev)
-            else:
-                _check_rows(torch, t, dev, n, width, "out[%r]" % name)
+            # (the cached tensor is made anew when num_vis_verts changed: a visual mesh was attached)
+            t = self._out_rows(torch, dev, name, out.get(name) if out is not None else None, (n, width), torch.float32, "out[%r]" % name)
             f.field, f.reserved, f.dst = field, 0, t.data_ptr()
             f.row_stride = 4 * t.stride(0) if n > 1 else 0
             res[name] = t
@@ -536,14 +552,19 @@ class SoftBodyHIP:
         self._snapshots.append(snap)
         return snap
 
-    def _snapshot_call(self, fn, snap, bodies, stream):
+    def _masked_call(self, bodies, stream, call):
+        """A device-side call that takes a body mask: `stream` and `bodies` resolved (_torch_stream, _body_mask), then call(torch, dev, mask
+        address or None, stream) -- which checks its own arguments and returns the library's code -- and the mask kept alive."""
         import torch
         dev, s = self._torch_stream(torch, stream)
+        ptr, keep = self._body_mask(torch, dev, bodies)
+        capi.check(call(torch, dev, ptr, s), self._h)
+        self._mask_keep = keep   # (a converted host sequence lives until the next call: the kernel may not have read it yet)
+
+    def _snapshot_call(self, fn, snap, bodies, stream):
         if not isinstance(snap, Snapshot) or snap._s is None:
             raise ValueError("snap must be a live Snapshot")
-        ptr, keep = self._body_mask(torch, dev, bodies)
-        capi.check(fn(self._h, snap._s, ptr, s), self._h)
-        self._mask_keep = keep   # (a converted host sequence lives until the next call: the kernel may not have read it yet)
+        self._masked_call(bodies, stream, lambda torch, dev, mask, s: fn(self._h, snap._s, mask, s))
 
     def capture(self, snap, bodies=None, stream=None):
         """Overwrite the chosen bodies' part of `snap` with their current state.  bodies: None = all, a torch.bool / torch.uint8 tensor
@@ -564,14 +585,13 @@ class SoftBodyHIP:
         the substeps enqueued so far, with no host copy and no synchronisation.  bodies: a mask as in restore -- a body it leaves out is
         not written.  keep_velocity: the body's velocities are turned and kept under the row's linear and angular velocity.  A row
         with a non-finite value or a zero quaternion leaves its body untouched."""
-        import torch
-        dev, s = self._torch_stream(torch, stream)
         n = self.info.num_bodies
-        _check_rows(torch, rows, dev, n, capi.PLACE_WIDTH, "rows")
-        ptr, keep = self._body_mask(torch, dev, bodies)
-        capi.check(self._L.tetsim_place_bodies_device(self._h, rows.data_ptr(), 4 * rows.stride(0) if n > 1 else 0, ptr,
-                                                      capi.PLACE_KEEP_VELOCITY if keep_velocity else 0, s), self._h)
-        self._mask_keep = keep   # (a converted host sequence lives until the next call: the kernel may not have read it yet)
+
+        def call(torch, dev, mask, s):
+            _check_rows(torch, rows, dev, n, capi.PLACE_WIDTH, "rows")
+            return self._L.tetsim_place_bodies_device(self._h, rows.data_ptr(), 4 * rows.stride(0) if n > 1 else 0, mask,
+                                                      capi.PLACE_KEEP_VELOCITY if keep_velocity else 0, s)
+        self._masked_call(bodies, stream, call)
 
     def placeBodies(self, rows, bodies=None, keep_velocity=False):
         """placeBodiesDevice from host arrays: rows float32 [num_bodies, 16] (place_rows), bodies None or a sequence of num_bodies truth
@@ -597,13 +617,7 @@ class SoftBodyHIP:
         import torch
         dev, s = self._torch_stream(torch, stream)
         n, w = self.info.num_bodies, capi.OBS_WIDTH
-        if out is None:
-            out = self._export_cache.get("observations")
-            if out is None:
-                out = self._export_cache["observations"] = torch.empty((n, w), dtype=torch.float64, device=dev)
-        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or out.device != dev or tuple(out.shape) != (n, w)
-              or out.stride(1) != 1 or (n > 1 and out.stride(0) < w)):
-            raise ValueError("out must be a float64 tensor on %s of shape (%d, %d) with contiguous, non-overlapping rows" % (dev, n, w))
+        out = self._out_rows(torch, dev, "observations", out, (n, w), torch.float64)
         capi.check(self._L.tetsim_observe_bodies_device(self._h, out.data_ptr(), 8 * out.stride(0) if n > 1 else 0, s), self._h)
         return out
 
@@ -623,13 +637,7 @@ class SoftBodyHIP:
         import torch
         dev, s = self._torch_stream(torch, stream)
         n, w = self.info.num_bodies, capi.POSE_WIDTH
-        if out is None:
-            out = self._export_cache.get("poses")
-            if out is None:
-                out = self._export_cache["poses"] = torch.empty((n, w), dtype=torch.float64, device=dev)
-        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or out.device != dev or tuple(out.shape) != (n, w)
-              or out.stride(1) != 1 or (n > 1 and out.stride(0) < w)):
-            raise ValueError("out must be a float64 tensor on %s of shape (%d, %d) with contiguous, non-overlapping rows" % (dev, n, w))
+        out = self._out_rows(torch, dev, "poses", out, (n, w), torch.float64)
         capi.check(self._L.tetsim_body_poses_device(self._h, out.data_ptr(), 8 * out.stride(0) if n > 1 else 0, s), self._h)
         return out
 
@@ -649,7 +657,7 @@ class SoftBodyHIP:
         import torch
         dev, s = self._torch_stream(torch, stream)
         n = self.info.num_bodies
-        out = self._strain_out(torch, dev, "touch", out, n, capi.TOUCH_WIDTH, torch.float64)
+        out = self._out_rows(torch, dev, "touch", out, (n, capi.TOUCH_WIDTH), torch.float64)
         capi.check(self._L.tetsim_touch_bodies_device(self._h, float(margin), out.data_ptr(), 8 * out.stride(0) if n > 1 else 0, s), self._h)
         return out
 
@@ -666,27 +674,11 @@ class SoftBodyHIP:
         import torch
         dev, s = self._torch_stream(torch, stream)
         n, w = self.info.owned_particles, capi.TOUCH_PARTICLE_WIDTH
-        if out is None:
-            out = self._export_cache.get("touch_particles")
-            if out is None:
-                out = self._export_cache["touch_particles"] = torch.empty((n, w), dtype=torch.float32, device=dev)
-        else:
-            _check_rows(torch, out, dev, n, w, "out")
+        out = self._out_rows(torch, dev, "touch_particles", out, (n, w), torch.float32)
         capi.check(self._L.tetsim_touch_particles_device(self._h, float(margin), out.data_ptr(), 4 * out.stride(0) if n > 1 else 0, s), self._h)
         return out
 
     # -- per-tet strain (include/tetsim.h: tetsim_tet_strain_device / _body_strain_device / _visual_strain_device) -----------------
-    def _strain_out(self, torch, dev, key, out, n, w, dtype):
-        """The cached tensor of a strain call, or the caller's `out` behind the checks of observeBodies."""
-        if out is None:
-            out = self._export_cache.get(key)
-            if out is None or out.shape[0] != n:
-                out = self._export_cache[key] = torch.empty((n, w), dtype=dtype, device=dev)
-        elif (not isinstance(out, torch.Tensor) or out.dtype != dtype or out.device != dev or tuple(out.shape) != (n, w)
-              or (n and out.stride(1) != 1) or (n > 1 and out.stride(0) < w)):
-            raise ValueError("out must be a %s tensor on %s of shape (%d, %d) with contiguous, non-overlapping rows" % (dtype, dev, n, w))
-        return out
-
     def tetStrainDevice(self, out=None, stream=None):
         """torch.float32 [num_elems, 16] on the handle's device, row t = tet t of the caller's numbering: the deformation gradient F
         (9, column-major), J = det F, DEV (the reference's r_s), the principal stretches (3, descending) and the norm of the Green
@@ -695,7 +687,7 @@ class SoftBodyHIP:
         import torch
         dev, s = self._torch_stream(torch, stream)
         n, w = self.info.num_elems, capi.STRAIN_WIDTH
-        out = self._strain_out(torch, dev, "tetStrain", out, n, w, torch.float32)
+        out = self._out_rows(torch, dev, "tetStrain", out, (n, w), torch.float32)
         capi.check(self._L.tetsim_tet_strain_device(self._h, out.data_ptr(), 4 * out.stride(0) if n > 1 else 0, s), self._h)
         return out
 
@@ -712,7 +704,7 @@ class SoftBodyHIP:
         import torch
         dev, s = self._torch_stream(torch, stream)
         n, w = self.info.num_bodies, capi.STRAIN_BODY_WIDTH
-        out = self._strain_out(torch, dev, "bodyStrain", out, n, w, torch.float64)
+        out = self._out_rows(torch, dev, "bodyStrain", out, (n, w), torch.float64)
         capi.check(self._L.tetsim_body_strain_device(self._h, out.data_ptr(), 8 * out.stride(0) if n > 1 else 0, s), self._h)
         return out
 
@@ -727,13 +719,7 @@ class SoftBodyHIP:
                 raise ValueError("channel must be an index 0..14 or one of %s" % sorted(_STRAIN_CHANNELS))
             channel = _STRAIN_CHANNELS[channel]
         n = self.info.num_vis_verts
-        if out is None:
-            out = self._export_cache.get("visualStrain")
-            if out is None or out.shape[0] != n:
-                out = self._export_cache["visualStrain"] = torch.empty((n,), dtype=torch.float32, device=dev)
-        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != dev or tuple(out.shape) != (n,)
-              or (n > 1 and out.stride(0) < 1)):
-            raise ValueError("out must be a float32 tensor on %s of shape (%d,) with non-overlapping elements" % (dev, n))
+        out = self._out_rows(torch, dev, "visualStrain", out, (n,), torch.float32)
         capi.check(self._L.tetsim_visual_strain_device(self._h, int(channel), out.data_ptr(), 4 * out.stride(0) if n > 1 else 0, s), self._h)
         return out
 
@@ -873,13 +859,7 @@ class SoftBodyHIP:
         if bodies is not None and (not isinstance(bodies, torch.Tensor) or bodies.dtype != torch.int32 or bodies.device != dev
                                    or tuple(bodies.shape) != (n,) or not bodies.is_contiguous()):
             raise ValueError("bodies must be a contiguous int32 tensor on %s of shape (%d,)" % (dev, n))
-        if out is None:
-            out = self._export_cache.get("rayHits")
-            if out is None or out.shape[0] != n:
-                out = self._export_cache["rayHits"] = torch.empty((n, 48), dtype=torch.uint8, device=dev)
-        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != dev or tuple(out.shape) != (n, 48)
-              or (n and out.stride(1) != 1) or (n > 1 and (out.stride(0) < 48 or out.stride(0) % 8)) or (n and out.data_ptr() % 8)):
-            raise ValueError("out must be a uint8 tensor on %s of shape (%d, 48) with contiguous, non-overlapping, 8-byte aligned rows" % (dev, n))
+        out = self._out_rows(torch, dev, "rayHits", out, (n, 48), torch.uint8, align=8)
         capi.check(call(self._h, rays.data_ptr() if n else None, 8 * rays.stride(0) if n > 1 else 0, bodies.data_ptr() if bodies is not None and n else None, n,
                         out.data_ptr() if n else None, out.stride(0) if n > 1 else 0, s), self._h)
         i32, f64 = out.view(torch.int32), out.view(torch.float64)   # (rows of 12 / 6 of them; a strided `out` keeps its row stride)
@@ -904,13 +884,7 @@ class SoftBodyHIP:
         if bodies is not None and (not isinstance(bodies, torch.Tensor) or bodies.dtype != torch.int32 or bodies.device != dev
                                    or tuple(bodies.shape) != (n,) or not bodies.is_contiguous()):
             raise ValueError("bodies must be a contiguous int32 tensor on %s of shape (%d,)" % (dev, n))
-        if out is None:
-            out = self._export_cache.get("closestPoints")
-            if out is None or out.shape[0] != n:
-                out = self._export_cache["closestPoints"] = torch.empty((n, 64), dtype=torch.uint8, device=dev)
-        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != dev or tuple(out.shape) != (n, 64)
-              or (n and out.stride(1) != 1) or (n > 1 and (out.stride(0) < 64 or out.stride(0) % 8)) or (n and out.data_ptr() % 8)):
-            raise ValueError("out must be a uint8 tensor on %s of shape (%d, 64) with contiguous, non-overlapping, 8-byte aligned rows" % (dev, n))
+        out = self._out_rows(torch, dev, "closestPoints", out, (n, 64), torch.uint8, align=8)
         capi.check(self._L.tetsim_closest_visual_device(self._h, queries.data_ptr() if n else None, 8 * queries.stride(0) if n > 1 else 0,
                                                         bodies.data_ptr() if bodies is not None and n else None, n,
                                                         out.data_ptr() if n else None, out.stride(0) if n > 1 else 0, s), self._h)
@@ -936,13 +910,7 @@ class SoftBodyHIP:
         import torch
         dev, s = self._torch_stream(torch, stream)
         n = self.info.num_bodies
-        if out is None:
-            out = self._export_cache.get("visualSpheres")
-            if out is None:
-                out = self._export_cache["visualSpheres"] = torch.empty((n, 4), dtype=torch.float64, device=dev)
-        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or out.device != dev or tuple(out.shape) != (n, 4)
-              or out.stride(1) != 1 or (n > 1 and out.stride(0) < 4)):
-            raise ValueError("out must be a float64 tensor on %s of shape (%d, 4) with contiguous, non-overlapping rows" % (dev, n))
+        out = self._out_rows(torch, dev, "visualSpheres", out, (n, 4), torch.float64)
         capi.check(self._L.tetsim_visual_bounding_spheres_device(self._h, out.data_ptr(), 8 * out.stride(0) if n > 1 else 0, s), self._h)
         return out
 
@@ -997,16 +965,15 @@ class SoftBodyHIP:
         targets torch.float32 [num_bodies, 3] (rows contiguous; the row stride is passed through), both on the handle's device and
         produced on `stream` (as in exportTensors; reusable on it right after the call).  bodies: a mask as in restore -- a body it leaves
         out keeps its row.  A row the table cannot hold (an index outside its body, a non-finite target) means "not held" for that body."""
-        import torch
-        dev, s = self._torch_stream(torch, stream)
         n = self.info.num_bodies
-        if (not isinstance(particles, torch.Tensor) or particles.dtype != torch.int32 or particles.device != dev or tuple(particles.shape) != (n,)
-                or not particles.is_contiguous()):
-            raise ValueError("particles must be a contiguous int32 tensor on %s of shape (%d,)" % (dev, n))
-        _check_rows(torch, targets, dev, n, 3, "targets")
-        ptr, keep = self._body_mask(torch, dev, bodies)
-        capi.check(self._L.tetsim_set_body_grabs_device(self._h, particles.data_ptr(), targets.data_ptr(), 4 * targets.stride(0) if n > 1 else 0, ptr, s), self._h)
-        self._mask_keep = keep   # (a converted host sequence lives until the next call: the kernel may not have read it yet)
+
+        def call(torch, dev, mask, s):
+            if (not isinstance(particles, torch.Tensor) or particles.dtype != torch.int32 or particles.device != dev or tuple(particles.shape) != (n,)
+                    or not particles.is_contiguous()):
+                raise ValueError("particles must be a contiguous int32 tensor on %s of shape (%d,)" % (dev, n))
+            _check_rows(torch, targets, dev, n, 3, "targets")
+            return self._L.tetsim_set_body_grabs_device(self._h, particles.data_ptr(), targets.data_ptr(), 4 * targets.stride(0) if n > 1 else 0, mask, s)
+        self._masked_call(bodies, stream, call)
 
     # -- body colliders (include/tetsim.h: tetsim_set_body_colliders / _device) ---------------------------------------------
     def setBodyColliders(self, lists_or_rows):
@@ -1030,20 +997,19 @@ class SoftBodyHIP:
         nothing outside a row's 24 floats is read), on the handle's device and produced on `stream` (as in exportTensors; reusable on
         it right after the call).  bodies: a mask as in setBodyGrabsDevice -- a body it leaves out keeps its whole list.  A row the
         table cannot hold (what setColliders would refuse) is an empty slot for that body and disturbs no other row."""
-        import torch
-        dev, s = self._torch_stream(torch, stream)
         n, w = self.info.num_bodies, capi.BODY_COLLIDER_FLOATS
-        ok = (isinstance(rows, torch.Tensor) and rows.dtype == torch.float32 and rows.device == dev and rows.dim() == 3 and rows.shape[0] == n
-              and 1 <= rows.shape[1] and rows.shape[2] >= w and rows.stride(2) == 1)
-        if ok:
-            per_body = int(rows.shape[1])
-            step = rows.stride(1) if per_body > 1 else (rows.stride(0) if n > 1 else w)
-            ok = step >= w and (n == 1 or per_body == 1 or rows.stride(0) == per_body * step)
-        if not ok:
-            raise ValueError("rows must be a float32 tensor on %s of shape (%d, per_body, >= %d) with a contiguous last dimension and evenly spaced rows" % (dev, n, w))
-        ptr, keep = self._body_mask(torch, dev, bodies)
-        capi.check(self._L.tetsim_set_body_colliders_device(self._h, rows.data_ptr(), 4 * step if n * per_body > 1 else 0, per_body, ptr, s), self._h)
-        self._mask_keep = keep   # (a converted host sequence lives until the next call: the kernel may not have read it yet)
+
+        def call(torch, dev, mask, s):
+            ok = (isinstance(rows, torch.Tensor) and rows.dtype == torch.float32 and rows.device == dev and rows.dim() == 3 and rows.shape[0] == n
+                  and 1 <= rows.shape[1] and rows.shape[2] >= w and rows.stride(2) == 1)
+            if ok:
+                per_body = int(rows.shape[1])
+                step = rows.stride(1) if per_body > 1 else (rows.stride(0) if n > 1 else w)
+                ok = step >= w and (n == 1 or per_body == 1 or rows.stride(0) == per_body * step)
+            if not ok:
+                raise ValueError("rows must be a float32 tensor on %s of shape (%d, per_body, >= %d) with a contiguous last dimension and evenly spaced rows" % (dev, n, w))
+            return self._L.tetsim_set_body_colliders_device(self._h, rows.data_ptr(), 4 * step if n * per_body > 1 else 0, per_body, mask, s)
+        self._masked_call(bodies, stream, call)
 
     # -- body parameters (include/tetsim.h: tetsim_set_body_params / _device) ------------------------------------------------
     def setBodyParams(self, rows_or_dicts):
@@ -1071,16 +1037,15 @@ class SoftBodyHIP:
         and a contiguous last dimension (a [:, :10] view of a wider tensor is fine: nothing outside a row's ten doubles is read), on the
         handle's device and produced on `stream` (as in exportTensors; reusable on it right after the call).  bodies: a mask as in
         setBodyGrabsDevice -- a body it leaves out keeps its row.  A row with a non-finite value leaves its body's previous row in place."""
-        import torch
-        dev, s = self._torch_stream(torch, stream)
         n, w = self.info.num_bodies, capi.BODY_PARAMS_WIDTH
-        ok = (isinstance(rows, torch.Tensor) and rows.dtype == torch.float64 and rows.device == dev and rows.dim() == 2 and rows.shape[0] == n
-              and rows.shape[1] >= w and rows.stride(1) == 1 and (n == 1 or rows.stride(0) >= w))
-        if not ok:
-            raise ValueError("rows must be a float64 tensor on %s of shape (%d, >= %d) with a contiguous last dimension" % (dev, n, w))
-        ptr, keep = self._body_mask(torch, dev, bodies)
-        capi.check(self._L.tetsim_set_body_params_device(self._h, rows.data_ptr(), 8 * rows.stride(0) if n > 1 else 0, ptr, s), self._h)
-        self._mask_keep = keep   # (a converted host sequence lives until the next call: the kernel may not have read it yet)
+
+        def call(torch, dev, mask, s):
+            ok = (isinstance(rows, torch.Tensor) and rows.dtype == torch.float64 and rows.device == dev and rows.dim() == 2 and rows.shape[0] == n
+                  and rows.shape[1] >= w and rows.stride(1) == 1 and (n == 1 or rows.stride(0) >= w))
+            if not ok:
+                raise ValueError("rows must be a float64 tensor on %s of shape (%d, >= %d) with a contiguous last dimension" % (dev, n, w))
+            return self._L.tetsim_set_body_params_device(self._h, rows.data_ptr(), 8 * rows.stride(0) if n > 1 else 0, mask, s)
+        self._masked_call(bodies, stream, call)
 
     def nearestParticlesDevice(self, points, out_ids=None, out_dist2=None, stream=None):
         """(ids, dist2): per body the index INSIDE the body of its particle nearest to points[b], torch.int32 [num_bodies], and the squared
@@ -1094,13 +1059,7 @@ class SoftBodyHIP:
         _check_rows(torch, points, dev, n, 3, "points")
         outs = []
         for key, out, dtype in (("nearestIds", out_ids, torch.int32), ("nearestDist2", out_dist2, torch.float64)):
-            if out is None:
-                out = self._export_cache.get(key)
-                if out is None:
-                    out = self._export_cache[key] = torch.empty((n,), dtype=dtype, device=dev)
-            elif not isinstance(out, torch.Tensor) or out.dtype != dtype or out.device != dev or tuple(out.shape) != (n,) or not out.is_contiguous():
-                raise ValueError("%s must be a contiguous %s tensor on %s of shape (%d,)" % (key, dtype, dev, n))
-            outs.append(out)
+            outs.append(self._out_rows(torch, dev, key, out, (n,), dtype, key, packed=True))
         capi.check(self._L.tetsim_nearest_particles_device(self._h, points.data_ptr(), 4 * points.stride(0) if n > 1 else 0,
                                                            outs[0].data_ptr(), outs[1].data_ptr(), s), self._h)
         return outs[0], outs[1]

@@ -3,7 +3,9 @@
 Registers (no GPU needed): registers, scalar spills, private segment and waves per SIMD of the kernels that take the table, read from the
 .note metadata of the code objects in a build's object directory -- one directory alone, or a parent's build against this one:
 
-    python tools/body_params_cost.py --registers tetsim_amd/csrc/obj [--parent PARENT/tetsim_amd/csrc/obj]
+    python tools/body_params_cost.py --registers tetsim_amd/csrc/obj [--parent PARENT/tetsim_amd/csrc/obj] [--units body_colliders,body_params]
+
+(--units: every kernel of the named units instead -- the set kernels themselves, profiles/body_rows_refactor.txt.)
 
 Time (MI355X): 64 Dragons in one batch, one call of 20 substeps (timeSubsteps: between HIP events), polar FAST and Neo-Hookean FAST, with
 the table ON (every row equal to the call's parameters) against OFF, median of 20 calls after 5 warm-up calls; then the set kernel,
@@ -41,11 +43,11 @@ def llvm(tool):
     return tool
 
 
-def kernel_notes(objdir):
+def kernel_notes(objdir, units=None):
     """{unit: kernel: (vgprs, sgprs, vgpr spills, sgpr spills, private segment)} of the gfx950 code objects of a build"""
     out = {}
     with tempfile.TemporaryDirectory() as tmp:
-        for unit in UNITS:
+        for unit in units or UNITS:
             obj = os.path.join(objdir, unit + ".o")
             if not os.path.exists(obj):
                 continue
@@ -57,7 +59,7 @@ def kernel_notes(objdir):
                 def field(k):
                     return re.search(r"\." + k + r":\s+(\S+)", blk).group(1)
                 name = field("name")
-                if not any(k in name for k in KERNELS):
+                if not units and not any(k in name for k in KERNELS):
                     continue
                 nice = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip()
                 nice = re.sub(r"\(.*", "", nice.replace("(anonymous namespace)::", "").replace("void ", "").replace("tetsim::", ""))
@@ -69,8 +71,8 @@ def waves(vgprs):
     return min(8, 512 // (max(vgprs, 1) + 7 & ~7))   # gfx950: 512 registers per lane and SIMD, granted in blocks of 8
 
 
-def register_table(objdir, parent):
-    mine, theirs = kernel_notes(objdir), kernel_notes(parent) if parent else {}
+def register_table(objdir, parent, units=None):
+    mine, theirs = kernel_notes(objdir, units), kernel_notes(parent, units) if parent else {}
     lines = ["kernel: vgprs / sgprs / vgpr spills / sgpr spills / private segment bytes / waves per SIMD by vgprs" + (", parent -> this change" if parent else "")]
     for k in sorted(mine):
         def show(r):
@@ -119,9 +121,10 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--registers", default=None, metavar="OBJDIR")
     ap.add_argument("--parent", default=None, metavar="OBJDIR")
+    ap.add_argument("--units", default=None, help="with --registers: comma-separated units, every kernel of each")
     a = ap.parse_args()
     if a.registers:
-        lines = register_table(a.registers, a.parent)
+        lines = register_table(a.registers, a.parent, a.units.split(",") if a.units else None)
     else:
         import torch
         torch.cuda.init()   # (before the library opens the device: torch finds no GPU behind it otherwise)
