@@ -143,7 +143,92 @@ inline int blk_mode(const PJBlk& d) { return pjb_mode(d); }
 // and the predictions it stages were written by particle waves of the same launch: memory-side loads, looked at until they carry the
 // previous substep's sequence number poll->want (0: the launch's first substep, whose predictions a completed launch left)
 struct PJPoll { uint32_t block, want; uint32_t* error; uint32_t timeout_ms; };
-template <int kMode, bool kFused, bool kAlt = false, bool kHaloWait = false, bool kPoll = false>
+
+// ---- the steps the kernels of this unit share --------------------------------------------------------------------------------------------
+// What must agree BIT FOR BIT between the kernels (tetsim_step == tetsim_step_n, frame == fused == pair == call; tests/
+// test_gpu_blocked_paths_golden.py holds the bits themselves) exists once, here: which slot, tet, particle and run of the list a lane of a
+// tile has (tile_lane), what a tet's row says (decode_tet_row), how a record unpacks and goes back (unpack_record, store_record), the order
+// a particle's partial sums are added in (add_eight and the ninth behind it), what a particle lane stores (store_vertex_out) -- with
+// pjb_vertex_update above.  TWO steps are still written out twice and kept equal by hand, in pjb_tet_body and in pjb_frame_body: the scatter
+// of V * (goal + cc) into the planes and the list-order reduction of a slot's run (with the slot fill and the frame's own clock code):
+// behind shared functions the frame kernels' schedule moved and a Dragon frame cost 1.5-3 % more (profiles/pj_blocked_refactor.txt).
+// Every wait of this unit is bounded (timeout_ms, 30 s by default; 0 = unbounded): a wedged peer or a wrong schedule must not wedge the
+// GPU -- never in a correct run.  The clock arithmetic and the error word are here; each loop keeps its own sleep, memory order and look.
+struct BoundedWait {
+    long long t0, limit;   // 100 MHz ticks
+    __device__ __forceinline__ explicit BoundedWait(uint32_t timeout_ms) : t0(wall_clock64()), limit(100000ll * timeout_ms) {}
+    // (waiting: this lane still misses something -- the clock is read only then)
+    __device__ __forceinline__ bool expired(bool waiting = true) const { return limit && waiting && wall_clock64() - t0 > limit; }
+    __device__ __forceinline__ static void raise(uint32_t* error) { __hip_atomic_store(error, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
+};
+// What lane `tid` of tile `b` is: the tile's tets [t0, t0 + ntb) and slots [v0, v0 + nu), the lane's slot and tet (element 0 of the tile
+// for a lane without one: see "1. stage the tile's particles" below), its particle, and its slot's run of the tile's list.
+// The ids and the run starts are REQUESTED here, in this order, in front of everything the caller asks for.
+struct TileLane {   // owner: the tile holding the first of the particle's partial sums -- the one writer of the particle's state (fused, frame)
+    uint32_t t0, ntb, v0, nu, slot, e, vid, range, first, last;
+    bool has_slot, has_tet, owner;
+};
+__device__ __forceinline__ TileLane tile_lane(const PJBlk& d, const uint32_t b, const uint32_t tid) {
+    TileLane L;
+    L.t0 = d.blk_tet_off[b]; L.ntb = d.blk_tet_off[b + 1] - L.t0;
+    L.v0 = d.blk_vert_off[b]; L.nu = d.blk_vert_off[b + 1] - L.v0;
+    L.has_slot = tid < L.nu; L.has_tet = tid < L.ntb;
+    L.slot = L.v0 + (L.has_slot ? tid : 0u); L.e = L.t0 + (L.has_tet ? tid : 0u);
+    L.vid = static_cast<uint32_t>(d.blk_verts[L.slot]);   // (unsigned: no sign extension right behind the load)
+    // the slot's run of the tile's list: [first, the next slot's first) -- one more entry per tile closes its last run
+    L.range = L.has_slot ? d.lc_first[L.slot + b] : 0u;
+    const uint32_t range_end = L.has_slot ? d.lc_first[L.slot + b + 1u] : 0u;
+    L.first = L.range & 0x7ffu; L.last = range_end & 0x7ffu;   // (bit 15: owner flag)
+    L.owner = L.has_slot && ((L.range >> 15) & 1u);
+    return L;
+}
+// the tet's constants, one 12-byte row: the list positions of its four corners (10 bits each), which corners the incidence table
+// dropped (they have a place in the list and leave +0 there: the sums keep their bits), the rest volume
+struct TetCorners { uint32_t lp[4], dropped; float V; };
+__device__ __forceinline__ TetCorners decode_tet_row(const PJTetRow row) {
+    return {{row.pos_lo & 1023u, (row.pos_lo >> 10) & 1023u, (row.pos_lo >> 20) & 1023u, (row.pos_lo >> 30) | ((row.pos_hi & 255u) << 2)}, row.pos_hi >> 8, __uint_as_float(row.vol)};
+}
+// a tet's record: 48 bytes (36: lean state, rc.x alone) <-> the four corners of its shape
+template <int kMode>
+__device__ __forceinline__ void unpack_record(const float4 ra, const float4 rb, const float4 rc, f3 rest[4]) {
+    rest[0] = F3(ra.x, ra.y, ra.z); rest[1] = F3(ra.w, rb.x, rb.y);
+    rest[2] = F3(rb.z, rb.w, rc.x); rest[3] = F3(rc.y, rc.z, rc.w);
+    if constexpr (kMode == kModeLeanState) rest[3] = lean_fourth_corner(rest);
+}
+template <int kMode>
+__device__ __forceinline__ void store_record(const PJBlk& d, const uint32_t e, const f3 shape[4], const float4 q, const bool store_shape = true) {
+    if constexpr (kMode != kModeLeanState) store_wt(d.quat, e, q);
+    if (kMode != kModeConstantRest && store_shape) {  // constant-rest-shape bodies never write the shape back
+        store_wt(d.rest_a, e, make_float4(shape[0].x, shape[0].y, shape[0].z, shape[1].x));
+        store_wt(d.rest_b, e, make_float4(shape[1].y, shape[1].z, shape[2].x, shape[2].y));
+        if constexpr (kMode == kModeLeanState) store_wt1(d.rest_c1, e, shape[2].z);
+        else store_wt(d.rest_c, e, make_float4(shape[2].z, shape[3].x, shape[3].y, shape[3].z));
+    }
+}
+// a particle's partial sums, eight at a time in ascending tile order (absent = +0): the particle kernel's order of additions, and
+// so the fused, frame and call kernels'.  What follows the eight differs and stays with its kernel: the next eight columns (particle
+// kernel, call), or the ninth and then entry by entry -- plain loads (fused) or looks that wait for a stamp (frame).
+template <class A, class G>
+__device__ __forceinline__ void add_eight(A& acc, const G* g) {
+#pragma unroll
+    for (uint32_t j = 0; j < 8u; j++) { acc.x += g[j].x; acc.y += g[j].y; acc.z += g[j].z; }
+}
+// eight columns of a column-major (ELL) index table from column j0 on; 0xffffffff = no entry
+__device__ __forceinline__ void ell_columns(const uint32_t* col, const uint32_t j0, const uint32_t cols, const uint32_t stride, uint32_t (&idx)[8]) {
+#pragma unroll
+    for (uint32_t j = 0; j < 8u; j++) idx[j] = (j0 + j < cols) ? col[static_cast<size_t>(j0 + j) * stride] : 0xffffffffu;
+}
+// what a particle lane leaves: position, velocity (where somebody reads it) and the next substep's prediction; stamp: the fourth float of
+// position and prediction -- 0, or the substep's sequence number where tiles of the same launch look for it (pjb_call_kernel)
+__device__ __forceinline__ void store_vertex_out(const PJBlk& d, const uint32_t v, const VertexOut o, const uint32_t stamp, const bool with_vel) {
+    store_wt(d.fin_out, v, make_float4(o.p.x, o.p.y, o.p.z, __uint_as_float(stamp)));
+    if (with_vel) store_wt(d.vel, v, make_float4(o.vel.x, o.vel.y, o.vel.z, 0.0f));
+    store_wt(d.pos_pred, v, make_float4(o.pred.x, o.pred.y, o.pred.z, __uint_as_float(stamp)));
+}
+
+// how a tile's predictions are staged: one `if constexpr` branch each below (kFused, kHaloWait, kAlt, kPoll, else the headline's)
+enum class Stage { Plain, Fused, Alt, HaloWait, Poll };
+template <int kMode, Stage kStage>
 __device__ __forceinline__ void pjb_tet_body(const PJBlk& d, uint32_t tile_first, uint32_t tile_count, uint32_t tiles_per_xcd TETSIM_DBG_PARAM,
                                              [[maybe_unused]] const PJHaloWait* hw = nullptr, const uint32_t stamp = 0u, [[maybe_unused]] const PJPoll* poll = nullptr) {
     __shared__ float4 s_pos[kTile];        // staged particle positions
@@ -153,6 +238,7 @@ __device__ __forceinline__ void pjb_tet_body(const PJBlk& d, uint32_t tile_first
     __shared__ uint8_t s_slot[4 * kTile];  // the slot whose run a list position belongs to: where a tet finds its corners' particles
 
     constexpr bool kLean = kMode == kModeConstantRest;
+    constexpr bool kFused = kStage == Stage::Fused, kAlt = kStage == Stage::Alt, kHaloWait = kStage == Stage::HaloWait, kPoll = kStage == Stage::Poll;
     uint32_t block_index = blockIdx.x;
     if constexpr (kPoll) block_index = poll->block;
     const uint32_t rel = xcd_tile(block_index, tiles_per_xcd);
@@ -161,8 +247,6 @@ __device__ __forceinline__ void pjb_tet_body(const PJBlk& d, uint32_t tile_first
     const uint32_t tid = threadIdx.x;
     TETSIM_LAB_TILE_BEGIN();
     TETSIM_POLL_TILE(0);
-    const uint32_t t0 = d.blk_tet_off[b], ntb = d.blk_tet_off[b + 1] - t0;
-    const uint32_t v0 = d.blk_vert_off[b], nu = d.blk_vert_off[b + 1] - v0;
 
     // 1. stage the tile's particles.  Order of ISSUE matters: the particle gather is a dependent pair (slot -> particle id ->
     // position) and the tet record is independent of it, so the ids are requested first, then the whole tet record, and only
@@ -173,17 +257,13 @@ __device__ __forceinline__ void pjb_tet_body(const PJBlk& d, uint32_t tile_first
     // request per wave, results unused): with the loads inside `if`s the wait-count pass sees paths with different numbers of
     // loads in flight and, at the join, waits for the position gather's operand with the most conservative count -- which
     // lets (almost) the whole tet record land first, i.e. serialises the round trips again.
-    const bool has_slot = tid < nu, has_tet = tid < ntb;
-    const uint32_t slot = v0 + (has_slot ? tid : 0u), e = t0 + (has_tet ? tid : 0u);
-    const uint32_t vid = static_cast<uint32_t>(d.blk_verts[slot]);   // (unsigned: no sign extension right behind the load)
-    // the slot's run of the tile's list: [first, the next slot's first) -- one more entry per tile closes its last run
-    const uint32_t range = has_slot ? d.lc_first[slot + b] : 0u, range_end = has_slot ? d.lc_first[slot + b + 1u] : 0u;
-    const uint32_t first = range & 0x7ffu, last = range_end & 0x7ffu;   // (bit 15: owner flag)
+    const TileLane L = tile_lane(d, b, tid);
+    const uint32_t e = L.e, vid = L.vid;
     // Every list position gets the slot of its run, written by the slot's lane as soon as its two starts are there (they come with
     // the particle ids, a trip before the positions): the tet lanes read their corners' slots from it behind the staging barrier.
     auto fill_slots = [&]() {
-        if (has_slot)
-            for (uint32_t i = first; i < last; i++) s_slot[i] = static_cast<uint8_t>(tid);
+        if (L.has_slot)
+            for (uint32_t i = L.first; i < L.last; i++) s_slot[i] = static_cast<uint8_t>(tid);
     };
     // kFused: the particle update of the PREVIOUS substep happens here, for this tile's own particles (a particle in k tiles is
     // updated k times, identically; the tile holding the first of its partial sums -- `owner` -- writes the result back): the
@@ -191,14 +271,12 @@ __device__ __forceinline__ void pjb_tet_body(const PJBlk& d, uint32_t tile_first
     // particle's previous position and weight together with the tet record (round trip 2).  One kernel per substep instead of
     // two: the particle kernel's launch, its 30 MB and a second dependency bubble per substep are gone, for one more gather
     // level here.  Partial sums and positions are double buffered (other tiles still read the old ones).
-    uint32_t src[8];
-    uint32_t src8 = 0xffffffffu;
+    uint32_t src[8], src8 = 0xffffffffu;
     [[maybe_unused]] uint32_t maxsrc = 0;
     if constexpr (kFused) {
         maxsrc = d.blk_maxsrc[b];
-        const uint32_t* col = d.slot_src + slot;
-#pragma unroll
-        for (uint32_t j = 0; j < 8u; j++) src[j] = (j < maxsrc) ? col[static_cast<size_t>(j) * d.ns_pad] : 0xffffffffu;   // (uniform)
+        const uint32_t* col = d.slot_src + L.slot;
+        ell_columns(col, 0u, maxsrc, d.ns_pad, src);   // (uniform)
         if (maxsrc > 8u) src8 = col[8ull * d.ns_pad];
     }
     // (kPoll: the record was written by this tile's workgroup of the PREVIOUS substep of the same launch -- no kernel boundary has emptied
@@ -217,12 +295,7 @@ __device__ __forceinline__ void pjb_tet_body(const PJBlk& d, uint32_t tile_first
     bool record_late = false;
     if constexpr (kPoll) record_late = poll->want != 0u;   // (uniform)
     if (!record_late) load_record();
-    // the tet's constants, one 12-byte row: the list positions of its four corners (10 bits each), which corners the incidence table
-    // dropped (they have a place in the list and leave +0 there: the sums keep their bits), the rest volume
-    const PJTetRow row = d.tet_row[e];
-    const float V = __uint_as_float(row.vol);
-    const uint32_t lp[4] = {row.pos_lo & 1023u, (row.pos_lo >> 10) & 1023u, (row.pos_lo >> 20) & 1023u, (row.pos_lo >> 30) | ((row.pos_hi & 255u) << 2)};
-    const uint32_t dropped = row.pos_hi >> 8;
+    const TetCorners corners = decode_tet_row(d.tet_row[e]);
     float4 pos_stage;
     if constexpr (kFused) {
         // (a ghost would keep its received prediction; fused bodies have none)
@@ -237,11 +310,10 @@ __device__ __forceinline__ void pjb_tet_body(const PJBlk& d, uint32_t tile_first
         const float wsum = d.wsum[vid];
         fill_slots();
         f3 acc = F3(0.0f, 0.0f, 0.0f);
-#pragma unroll
-        for (uint32_t j = 0; j < 8u; j++) { acc.x += g[j].x; acc.y += g[j].y; acc.z += g[j].z; }
+        add_eight(acc, g);
         if (src8 != 0xffffffffu) { acc.x += t8.x; acc.y += t8.y; acc.z += t8.z; }
         if (maxsrc > 9u) {   // (uniform, rare: a tile with a particle at the corner of more than nine tiles -- irregular meshes; one trip per entry)
-            const uint32_t* col = d.slot_src + slot;
+            const uint32_t* col = d.slot_src + L.slot;
             for (uint32_t j = 9u; j < maxsrc; j++) {
                 const uint32_t sj = col[static_cast<size_t>(j) * d.ns_pad];
                 const float4 tj = d.partial_prev[sj == 0xffffffffu ? 0u : sj];
@@ -250,7 +322,7 @@ __device__ __forceinline__ void pjb_tet_body(const PJBlk& d, uint32_t tile_first
         }
         const VertexOut o = pjb_vertex_update<true>(acc, wsum, xyz(prev4), *d.params, vid);
         pos_stage = make_float4(o.pred.x, o.pred.y, o.pred.z, 0.0f);
-        if (has_slot && ((range >> 15) & 1u)) {   // one writer per particle
+        if (L.owner) {   // one writer per particle
             store_wt(d.fin_out, vid, make_float4(o.p.x, o.p.y, o.p.z, 0.0f));
             if (d.vel) store_wt(d.vel, vid, make_float4(o.vel.x, o.vel.y, o.vel.z, 0.0f));
         }
@@ -259,12 +331,12 @@ __device__ __forceinline__ void pjb_tet_body(const PJBlk& d, uint32_t tile_first
             const PJPeerSync& w = *hw->w;
             const uint32_t* word = tid == 0u ? hw->vflag : (tid <= w.n_wait ? w.wait[tid - 1u] : nullptr);
             bool pending = word != nullptr;
-            const long long t0 = wall_clock64(), limit = 100000ll * hw->timeout_ms;   // 100 MHz ticks
+            const BoundedWait wait(hw->timeout_ms);
             while (true) {   // (relaxed looks: an acquire load is a load plus a cache invalidation)
                 if (pending) pending = __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) == 0u;
                 if (__builtin_amdgcn_ballot_w64(pending) == 0ull) break;
                 __builtin_amdgcn_s_sleep(16);
-                if (limit && wall_clock64() - t0 > limit) { if (tid == 0) __hip_atomic_store(hw->error, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); break; }
+                if (wait.expired()) { if (tid == 0) BoundedWait::raise(hw->error); break; }
             }
             if (w.delay_us && w.n_wait) { const long long d0 = wall_clock64(); while (wall_clock64() - d0 < 100ll * w.delay_us) __builtin_amdgcn_s_sleep(8); }
         }
@@ -284,15 +356,15 @@ __device__ __forceinline__ void pjb_tet_body(const PJBlk& d, uint32_t tile_first
         pos_stage = load_coherent(d.pos_pred, vid);
         fill_slots();   // (under the first look's trip)
         if (poll->want != 0u) {
-            bool pend = has_slot && __float_as_uint(pos_stage.w) != poll->want;
+            bool pend = L.has_slot && __float_as_uint(pos_stage.w) != poll->want;
             if (__builtin_amdgcn_ballot_w64(pend) != 0ull) {
-                const long long t0 = wall_clock64(), limit = 100000ll * poll->timeout_ms;   // 100 MHz ticks; 0 = unbounded
+                const BoundedWait wait(poll->timeout_ms);
                 do {
                     __builtin_amdgcn_s_sleep(TETSIM_POLL_SLEEP);
                     TETSIM_POLL_LOOK();
                     asm volatile("" ::: "memory");   // (every look is a fresh load)
                     if (pend) { pos_stage = load_coherent(d.pos_pred, vid); pend = __float_as_uint(pos_stage.w) != poll->want; }
-                    if (limit && pend && wall_clock64() - t0 > limit) { __hip_atomic_store(poll->error, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); pend = false; }
+                    if (wait.expired(pend)) { BoundedWait::raise(poll->error); pend = false; }
                 } while (__builtin_amdgcn_ballot_w64(pend) != 0ull);
             }
             TETSIM_POLL_TILE(2);
@@ -305,7 +377,7 @@ __device__ __forceinline__ void pjb_tet_body(const PJBlk& d, uint32_t tile_first
         pos_stage = d.pos_pred[vid];
         fill_slots();
     }
-    if (has_slot) s_pos[tid] = pos_stage;
+    if (L.has_slot) s_pos[tid] = pos_stage;
     TETSIM_STAMP(1);  // loads issued (and landed, for this wave)
     // Every load above has been consumed by now on the path that has tets; say so for ALL paths.  Without this, the
     // wait-count model keeps "load into v[..] pending" alive through the path that skips the solve, and protects the reuse
@@ -316,15 +388,11 @@ __device__ __forceinline__ void pjb_tet_body(const PJBlk& d, uint32_t tile_first
     TETSIM_STAMP(2);  // tile staged
 
     // 2. solve
-    if (has_tet) {
+    if (L.has_tet) {
         f3 cur[4], rest[4], goal[4];
-        {
-            const uint32_t l0 = s_slot[lp[0]], l1 = s_slot[lp[1]], l2 = s_slot[lp[2]], l3 = s_slot[lp[3]];
-            cur[0] = xyz(s_pos[l0]); cur[1] = xyz(s_pos[l1]); cur[2] = xyz(s_pos[l2]); cur[3] = xyz(s_pos[l3]);
-        }
-        rest[0] = F3(ra.x, ra.y, ra.z); rest[1] = F3(ra.w, rb.x, rb.y);
-        rest[2] = F3(rb.z, rb.w, rc.x); rest[3] = F3(rc.y, rc.z, rc.w);
-        if constexpr (kMode == kModeLeanState) rest[3] = lean_fourth_corner(rest);
+        const uint32_t l0 = s_slot[corners.lp[0]], l1 = s_slot[corners.lp[1]], l2 = s_slot[corners.lp[2]], l3 = s_slot[corners.lp[3]];
+        cur[0] = xyz(s_pos[l0]); cur[1] = xyz(s_pos[l1]); cur[2] = xyz(s_pos[l2]); cur[3] = xyz(s_pos[l3]);
+        unpack_record<kMode>(ra, rb, rc, rest);
         float4 q_new;
         // The carried shape lives in HBM relative to its own centroid (see pj_solve_tet): `goal` comes back centred, the
         // world-space goal is goal + cc.  Same bytes as the reference's world-space shape, 21 instructions fewer per tet
@@ -333,21 +401,15 @@ __device__ __forceinline__ void pjb_tet_body(const PJBlk& d, uint32_t tile_first
         TETSIM_LAB_SOLVE_TET(cur, rest, q_old, q_new, goal, cc);   // pj_solve_tet(..., 9 iterations, peeled, kLean, centred, &cc, d.rot_exit_w2)
         TETSIM_STAMP(3);  // solved
         // LDS staging first, global results after it: nothing below may have to wait for the write-through stores
-        const f3 vcc = cc * V;
+        const f3 vcc = cc * corners.V;
 #pragma unroll
         for (int k = 0; k < 4; k++) {  // V * (goal + cc), at the corner's place in the list
-            const bool live = ((dropped >> k) & 1u) == 0u;
-            s_gx[lp[k]] = live ? fmaf(goal[k].x, V, vcc.x) : 0.0f;
-            s_gy[lp[k]] = live ? fmaf(goal[k].y, V, vcc.y) : 0.0f;
-            s_gz[lp[k]] = live ? fmaf(goal[k].z, V, vcc.z) : 0.0f;
+            const bool live = ((corners.dropped >> k) & 1u) == 0u;
+            s_gx[corners.lp[k]] = live ? fmaf(goal[k].x, corners.V, vcc.x) : 0.0f;
+            s_gy[corners.lp[k]] = live ? fmaf(goal[k].y, corners.V, vcc.y) : 0.0f;
+            s_gz[corners.lp[k]] = live ? fmaf(goal[k].z, corners.V, vcc.z) : 0.0f;
         }
-        if constexpr (kMode != kModeLeanState) store_wt(d.quat, e, q_new);
-        if (!kLean && TETSIM_DBG_STORE_REST) {  // constant-rest-shape bodies never write the shape back
-            store_wt(d.rest_a, e, make_float4(goal[0].x, goal[0].y, goal[0].z, goal[1].x));
-            store_wt(d.rest_b, e, make_float4(goal[1].y, goal[1].z, goal[2].x, goal[2].y));
-            if constexpr (kMode == kModeLeanState) store_wt1(d.rest_c1, e, goal[2].z);
-            else store_wt(d.rest_c, e, make_float4(goal[2].z, goal[3].x, goal[3].y, goal[3].z));
-        }
+        store_record<kMode>(d, e, goal, q_new, TETSIM_DBG_STORE_REST);   // (the carried shape of the next substep is this one's goal)
     }
     TETSIM_STAMP(4);  // stores issued
     if constexpr (kPoll) __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): this wave's record stores have LANDED (write-through: at the memory side) before any partial sum of the tile is stored
@@ -355,7 +417,7 @@ __device__ __forceinline__ void pjb_tet_body(const PJBlk& d, uint32_t tile_first
     TETSIM_STAMP(5);
 
     // 3. one lane per tile particle: fixed-order sum of its corner goals -> one partial per (tile, particle)
-    if (tid < nu) {
+    if (L.has_slot) {
         // The slot's run of the list, front to back: the values sit where they are added, no index in front of them.  4 entries per
         // trip: their 12 reads are independent LDS ops in flight together (one entry at a time is a chain of dependent LDS round
         // trips); whole groups of 4 run unmasked, the 0-3 left over one by one.  Accumulation order is list order, i.e.
@@ -364,33 +426,30 @@ __device__ __forceinline__ void pjb_tet_body(const PJBlk& d, uint32_t tile_first
         // constants -- so it is not reduced here at all: the host adds it up once, in this very order (tetsim_create.hip ->
         // PJBlk::wsum), and the particle pass reads it.  Three planes per entry instead of four.
         float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        uint32_t i = first;
-        for (; i + 4u <= last; i += 4u) {
+        uint32_t i = L.first;
+        for (; i + 4u <= L.last; i += 4u) {
             float gx[4], gy[4], gz[4];
 #pragma unroll
             for (uint32_t j = 0; j < 4u; j++) { gx[j] = s_gx[i + j]; gy[j] = s_gy[i + j]; gz[j] = s_gz[i + j]; }
 #pragma unroll
             for (uint32_t j = 0; j < 4u; j++) { acc.x += gx[j]; acc.y += gy[j]; acc.z += gz[j]; }
         }
-        for (; i < last; i++) { acc.x += s_gx[i]; acc.y += s_gy[i]; acc.z += s_gz[i]; }
+        for (; i < L.last; i++) { acc.x += s_gx[i]; acc.y += s_gy[i]; acc.z += s_gz[i]; }
         acc.w = __uint_as_float(stamp);
-        store_wt(d.partial, v0 + tid, acc);
+        store_wt(d.partial, L.v0 + tid, acc);
     }
     TETSIM_STAMP(6);
     TETSIM_POLL_TILE(4);
 }
 
-__global__ __launch_bounds__(kTile, 2) void pjb_tet_kernel(PJBlk d, uint32_t tile_first, uint32_t tile_count,
-                                                        uint32_t tiles_per_xcd TETSIM_DBG_PARAM) {
-    pjb_tet_body<kModeCarried, false>(d, tile_first, tile_count, tiles_per_xcd TETSIM_DBG_ARG);
+__global__ __launch_bounds__(kTile, 2) void pjb_tet_kernel(PJBlk d, uint32_t tile_first, uint32_t tile_count, uint32_t tiles_per_xcd TETSIM_DBG_PARAM) {
+    pjb_tet_body<kModeCarried, Stage::Plain>(d, tile_first, tile_count, tiles_per_xcd TETSIM_DBG_ARG);
 }
-__global__ __launch_bounds__(kTile, 2) void pjb_tet_kernel_constant_rest(PJBlk d, uint32_t tile_first, uint32_t tile_count,
-                                                                      uint32_t tiles_per_xcd TETSIM_DBG_PARAM) {
-    pjb_tet_body<kModeConstantRest, false>(d, tile_first, tile_count, tiles_per_xcd TETSIM_DBG_ARG);
+__global__ __launch_bounds__(kTile, 2) void pjb_tet_kernel_constant_rest(PJBlk d, uint32_t tile_first, uint32_t tile_count, uint32_t tiles_per_xcd TETSIM_DBG_PARAM) {
+    pjb_tet_body<kModeConstantRest, Stage::Plain>(d, tile_first, tile_count, tiles_per_xcd TETSIM_DBG_ARG);
 }
-__global__ __launch_bounds__(kTile, 2) void pjb_tet_kernel_lean(PJBlk d, uint32_t tile_first, uint32_t tile_count,
-                                                             uint32_t tiles_per_xcd TETSIM_DBG_PARAM) {
-    pjb_tet_body<kModeLeanState, false>(d, tile_first, tile_count, tiles_per_xcd TETSIM_DBG_ARG);
+__global__ __launch_bounds__(kTile, 2) void pjb_tet_kernel_lean(PJBlk d, uint32_t tile_first, uint32_t tile_count, uint32_t tiles_per_xcd TETSIM_DBG_PARAM) {
+    pjb_tet_body<kModeLeanState, Stage::Plain>(d, tile_first, tile_count, tiles_per_xcd TETSIM_DBG_ARG);
 }
 // The variants partitioned and mid-sized bodies need are ONE kernel template over what happens around the tile's solve:
 //   TetRaise  raises a hand-over word as it STARTS (partitioned bodies): a kernel starts only when everything in front
@@ -421,26 +480,32 @@ template <int kMode, class Extra>
 __global__ __launch_bounds__(kTile, 2) void pjb_tet_kernel_x(PJBlk d, uint32_t tile_first, uint32_t tile_count, uint32_t tiles_per_xcd, Extra x TETSIM_DBG_PARAM) {
     if constexpr (std::is_same_v<Extra, TetRaise>) {
         clear_then_raise(x.clear, x.sig);
-        pjb_tet_body<kMode, false>(d, tile_first, tile_count, tiles_per_xcd TETSIM_DBG_ARG);
+        pjb_tet_body<kMode, Stage::Plain>(d, tile_first, tile_count, tiles_per_xcd TETSIM_DBG_ARG);
     } else if constexpr (std::is_same_v<Extra, TetAlt>) {
-        pjb_tet_body<kMode, false, true>(d, tile_first, tile_count, tiles_per_xcd TETSIM_DBG_ARG);
+        pjb_tet_body<kMode, Stage::Alt>(d, tile_first, tile_count, tiles_per_xcd TETSIM_DBG_ARG);
     } else if constexpr (std::is_same_v<Extra, TetHwait>) {
         if (blockIdx.x == 0 && threadIdx.x < x.w.n_raise) __hip_atomic_store(x.w.raise[threadIdx.x], 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
         const PJHaloWait hw = {&x.w, x.vflag, x.error, x.timeout_ms, x.ghosts};
-        pjb_tet_body<kMode, false, false, true>(d, tile_first, tile_count, tiles_per_xcd TETSIM_DBG_ARG, &hw);
+        pjb_tet_body<kMode, Stage::HaloWait>(d, tile_first, tile_count, tiles_per_xcd TETSIM_DBG_ARG, &hw);
     } else {
-        pjb_tet_body<kMode, true>(d, tile_first, tile_count, tiles_per_xcd TETSIM_DBG_ARG);
+        pjb_tet_body<kMode, Stage::Fused>(d, tile_first, tile_count, tiles_per_xcd TETSIM_DBG_ARG);
     }
 }
-// one launcher for all of them: the kernel by (constant rest shape?, variant), its own begin / end events on request
+// the host's two choices, once: a kernel by the body's record (blk_mode), and a launch with its own begin / end events on request
+template <class K>
+K* by_mode(int mode, K* carried, K* constant_rest, K* lean) { return mode == kModeConstantRest ? constant_rest : mode == kModeLeanState ? lean : carried; }
+template <class K, class... Args>
+void launch(K* kernel, dim3 grid, dim3 block, hipStream_t s, hipEvent_t e0, hipEvent_t e1, const Args&... args) {
+    if (e0) hipExtLaunchKernelGGL(kernel, grid, block, 0, s, e0, e1, 0, args...);
+    else hipLaunchKernelGGL(kernel, grid, block, 0, s, args...);
+}
+// one launcher for all of them: the kernel by (record, variant)
 template <class Extra>
 void launch_tet_x(hipStream_t s, const PJBlk& d, uint32_t tile_first, uint32_t tile_count, const Extra& x, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr) {
     if (tile_count == 0) return;
     const uint32_t per_xcd = (tile_count + 7u) / 8u;
-    const int mode = blk_mode(d);
-    auto* kernel = mode == kModeConstantRest ? pjb_tet_kernel_x<kModeConstantRest, Extra> : mode == kModeLeanState ? pjb_tet_kernel_x<kModeLeanState, Extra> : pjb_tet_kernel_x<kModeCarried, Extra>;
-    if (e0) hipExtLaunchKernelGGL(kernel, dim3(per_xcd * 8u), dim3(kTile), 0, s, e0, e1, 0, d, tile_first, tile_count, per_xcd, x TETSIM_DBG_LAUNCH);
-    else hipLaunchKernelGGL(kernel, dim3(per_xcd * 8u), dim3(kTile), 0, s, d, tile_first, tile_count, per_xcd, x TETSIM_DBG_LAUNCH);
+    auto* kernel = by_mode(blk_mode(d), pjb_tet_kernel_x<kModeCarried, Extra>, pjb_tet_kernel_x<kModeConstantRest, Extra>, pjb_tet_kernel_x<kModeLeanState, Extra>);
+    launch(kernel, dim3(per_xcd * 8u), dim3(kTile), s, e0, e1, d, tile_first, tile_count, per_xcd, x TETSIM_DBG_LAUNCH);
 }
 
 // ---- one persistent launch per tetsim_step_n call (small bodies) -------------------------------------------
@@ -481,44 +546,34 @@ __device__ __forceinline__ void pjb_frame_body(const PJBlk& d, const DevParams& 
     const uint32_t b = static_cast<uint32_t>(bt);
     const uint32_t tid = threadIdx.x;
     TETSIM_LAB_FRAME_BEGIN();
-    const uint32_t t0 = d.blk_tet_off[b], ntb = d.blk_tet_off[b + 1] - t0;
-    const uint32_t v0 = d.blk_vert_off[b], nu = d.blk_vert_off[b + 1] - v0;
-    const bool has_slot = tid < nu, has_tet = tid < ntb;
-    const uint32_t slot = v0 + (has_slot ? tid : 0u), e = t0 + (has_tet ? tid : 0u);
     // everything that stays for the whole call, requested together (ids first: the particle loads depend on them)
-    const uint32_t vid = static_cast<uint32_t>(d.blk_verts[slot]);
-    const uint32_t range = has_slot ? d.lc_first[slot + b] : 0u, range_end = has_slot ? d.lc_first[slot + b + 1u] : 0u;
+    const TileLane L = tile_lane(d, b, tid);
+    const uint32_t e = L.e, vid = L.vid;
     const uint32_t maxsrc = d.blk_maxsrc[b];
     uint32_t src[9];
     {
-        const uint32_t* col = d.slot_src + slot;
+        const uint32_t* col = d.slot_src + L.slot;
 #pragma unroll
-        for (uint32_t j = 0; j < 9u; j++) src[j] = (has_slot && j < maxsrc) ? col[static_cast<size_t>(j) * d.ns_pad] : 0xffffffffu;
+        for (uint32_t j = 0; j < 9u; j++) src[j] = (L.has_slot && j < maxsrc) ? col[static_cast<size_t>(j) * d.ns_pad] : 0xffffffffu;
     }
-    const PJTetRow row = d.tet_row[e];   // (list positions, dropped corners, rest volume: pjb_tet_body)
+    const TetCorners corners = decode_tet_row(d.tet_row[e]);
     const float4 ra = d.rest_a[e], rb = d.rest_b[e];
     float4 rc = make_float4(0.0f, 0.0f, 0.0f, 0.0f), q = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
     if constexpr (kMode == kModeLeanState) rc.x = d.rest_c1[e];   // (lean state: three corners, no quaternion -- pjb_tet_body)
     else { rc = d.rest_c[e]; q = d.quat[e]; }
-    const float V = __uint_as_float(row.vol);
-    const uint32_t lp[4] = {row.pos_lo & 1023u, (row.pos_lo >> 10) & 1023u, (row.pos_lo >> 20) & 1023u, (row.pos_lo >> 30) | ((row.pos_hi & 255u) << 2)};
-    const uint32_t dropped = row.pos_hi >> 8;
-    f3 rest[4];
-    rest[0] = F3(ra.x, ra.y, ra.z); rest[1] = F3(ra.w, rb.x, rb.y);
-    rest[2] = F3(rb.z, rb.w, rc.x); rest[3] = F3(rc.y, rc.z, rc.w);
+    f3 rest[4];   // (lean state: the fourth corner is formed again in every substep, from the three that are carried)
+    unpack_record<kMode>(ra, rb, rc, rest);
     f3 prev = xyz(d.pos_final[vid]);
     const float wsum = d.wsum[vid];
     f3 stage = xyz(d.pos_pred[vid]);     // substep 0 starts from the prediction the previous call left
     const uint32_t epoch = d.epoch ? d.epoch : P.epoch;   // (a direct launch -- tetsim_step -- brings its own block of sequence numbers)
-    const uint32_t first = range & 0x7ffu, last = range_end & 0x7ffu;
-    const bool owner = has_slot && ((range >> 15) & 1u);
-    // the slots of the tet's corners stay in registers for the call: read once from the table the slot lanes fill (pjb_tet_body)
-    if (has_slot)
-        for (uint32_t i = first; i < last; i++) s_slot[i] = static_cast<uint8_t>(tid);
+    // the slots of the tet's corners stay in registers for the call: read once from the table the slot lanes fill (pjb_tet_body: fill_slots)
+    if (L.has_slot)
+        for (uint32_t i = L.first; i < L.last; i++) s_slot[i] = static_cast<uint8_t>(tid);
     __syncthreads();
-    const uint32_t li[4] = {s_slot[lp[0]], s_slot[lp[1]], s_slot[lp[2]], s_slot[lp[3]]};
+    const uint32_t li[4] = {s_slot[corners.lp[0]], s_slot[corners.lp[1]], s_slot[corners.lp[2]], s_slot[corners.lp[3]]};
     float4* const pbuf[2] = {pbuf0, pbuf1};
-    const long long limit = 100000ll * timeout_ms;   // 100 MHz ticks; 0 = unbounded
+    const long long limit = 100000ll * timeout_ms;   // 100 MHz ticks; 0 = unbounded (BoundedWait's arithmetic, kept here: see the list of shared steps)
 
     // the particle update of substep s from the partial sums of every tile that touches the particle (this one included):
     // ascending tile order, absent = +0 -- the particle kernel's order of additions
@@ -541,19 +596,15 @@ __device__ __forceinline__ void pjb_frame_body(const PJBlk& d, const DevParams& 
 #pragma unroll
             for (uint32_t j = 0; j < 9u; j++)
                 if (((pend >> j) & 1u) && __float_as_uint(t[j].w) == expect) { g[j] = xyz(t[j]); pend &= ~(1u << j); }
-            if (limit && pend != 0u && wall_clock64() - w0 > limit) {   // never in a correct run; a wedged GPU helps nobody
-                __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                pend = 0u;
-            }
+            if (limit && pend != 0u && wall_clock64() - w0 > limit) { BoundedWait::raise(err); pend = 0u; }   // never in a correct run; a wedged GPU helps nobody
         }
         f3 acc = F3(0.0f, 0.0f, 0.0f);
-#pragma unroll
-        for (uint32_t j = 0; j < 8u; j++) { acc.x += g[j].x; acc.y += g[j].y; acc.z += g[j].z; }
+        add_eight(acc, g);
         if (src[8] != 0xffffffffu) { acc.x += g[8].x; acc.y += g[8].y; acc.z += g[8].z; }
         if (maxsrc > 9u) {   // (uniform, rare: lists of more than nine partial sums -- irregular meshes; entry by entry, the ids re-read from the table)
-            const uint32_t* col = d.slot_src + slot;
+            const uint32_t* col = d.slot_src + L.slot;
             for (uint32_t j = 9u; j < maxsrc; j++) {
-                const uint32_t sj = has_slot ? col[static_cast<size_t>(j) * d.ns_pad] : 0xffffffffu;
+                const uint32_t sj = L.has_slot ? col[static_cast<size_t>(j) * d.ns_pad] : 0xffffffffu;
                 bool miss = sj != 0xffffffffu;
                 f3 gj = F3(0.0f, 0.0f, 0.0f);
                 while (__builtin_amdgcn_ballot_w64(miss) != 0ull) {
@@ -561,10 +612,7 @@ __device__ __forceinline__ void pjb_frame_body(const PJBlk& d, const DevParams& 
                         const float4 t = kLocal ? load_l2(buf, sj) : load_coherent(buf, sj);
                         if (__float_as_uint(t.w) == expect) { gj = xyz(t); miss = false; }
                     }
-                    if (limit && miss && wall_clock64() - w0 > limit) {
-                        __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                        miss = false;
-                    }
+                    if (limit && miss && wall_clock64() - w0 > limit) { BoundedWait::raise(err); miss = false; }
                 }
                 acc.x += gj.x; acc.y += gj.y; acc.z += gj.z;
             }
@@ -580,10 +628,10 @@ __device__ __forceinline__ void pjb_frame_body(const PJBlk& d, const DevParams& 
             stage = o.pred;
         }
         FRAME_STAMP(1);
-        if (has_slot) s_pos[tid] = make_float4(stage.x, stage.y, stage.z, 0.0f);
+        if (L.has_slot) s_pos[tid] = make_float4(stage.x, stage.y, stage.z, 0.0f);
         __syncthreads();
         FRAME_STAMP(2);
-        if (has_tet) {
+        if (L.has_tet) {
             f3 cur[4], r[4], goal[4];
             cur[0] = xyz(s_pos[li[0]]); cur[1] = xyz(s_pos[li[1]]); cur[2] = xyz(s_pos[li[2]]); cur[3] = xyz(s_pos[li[3]]);
 #pragma unroll
@@ -597,32 +645,32 @@ __device__ __forceinline__ void pjb_frame_body(const PJBlk& d, const DevParams& 
 #pragma unroll
                 for (int k = 0; k < 4; k++) rest[k] = goal[k];   // the carried shape stays in registers
             }
-            const f3 vcc = cc * V;
+            const f3 vcc = cc * corners.V;
 #pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const bool live = ((dropped >> k) & 1u) == 0u;
-                s_gx[lp[k]] = live ? fmaf(goal[k].x, V, vcc.x) : 0.0f;
-                s_gy[lp[k]] = live ? fmaf(goal[k].y, V, vcc.y) : 0.0f;
-                s_gz[lp[k]] = live ? fmaf(goal[k].z, V, vcc.z) : 0.0f;
+            for (int k = 0; k < 4; k++) {   // (pjb_tet_body's scatter, operation for operation)
+                const bool live = ((corners.dropped >> k) & 1u) == 0u;
+                s_gx[corners.lp[k]] = live ? fmaf(goal[k].x, corners.V, vcc.x) : 0.0f;
+                s_gy[corners.lp[k]] = live ? fmaf(goal[k].y, corners.V, vcc.y) : 0.0f;
+                s_gz[corners.lp[k]] = live ? fmaf(goal[k].z, corners.V, vcc.z) : 0.0f;
             }
         }
         FRAME_STAMP(3);
         __syncthreads();
         FRAME_STAMP(4);
-        if (has_slot) {   // the tet kernel's reduction, entry for entry
+        if (L.has_slot) {   // the tet kernel's reduction, entry for entry
             float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            uint32_t i = first;
-            for (; i + 4u <= last; i += 4u) {
+            uint32_t i = L.first;
+            for (; i + 4u <= L.last; i += 4u) {
                 float gx[4], gy[4], gz[4];
 #pragma unroll
                 for (uint32_t j = 0; j < 4u; j++) { gx[j] = s_gx[i + j]; gy[j] = s_gy[i + j]; gz[j] = s_gz[i + j]; }
 #pragma unroll
                 for (uint32_t j = 0; j < 4u; j++) { acc.x += gx[j]; acc.y += gy[j]; acc.z += gz[j]; }
             }
-            for (; i < last; i++) { acc.x += s_gx[i]; acc.y += s_gy[i]; acc.z += s_gz[i]; }
+            for (; i < L.last; i++) { acc.x += s_gx[i]; acc.y += s_gy[i]; acc.z += s_gz[i]; }
             acc.w = __uint_as_float(epoch + s);   // data and "substep s is here" in one 16-byte store
-            if constexpr (kLocal) store_plain(pbuf[s & 1u], v0 + tid, acc);
-            else store_wt(pbuf[s & 1u], v0 + tid, acc);
+            if constexpr (kLocal) store_plain(pbuf[s & 1u], L.v0 + tid, acc);
+            else store_wt(pbuf[s & 1u], L.v0 + tid, acc);
         }
         FRAME_STAMP(5);
         // (no barrier here: the next trip writes s_pos, last read before the second barrier above, and the planes are rewritten
@@ -631,20 +679,12 @@ __device__ __forceinline__ void pjb_frame_body(const PJBlk& d, const DevParams& 
     // the particle update that ends the call, and the state back to memory: one writer per particle, every lane its own tet
     const VertexOut o = gather_update(n - 1u);
     TETSIM_LAB_FRAME_END();
-    if (owner) {
+    if (L.owner) {   // (pos_final itself: the frame kernel double-buffers nothing but the partial sums)
         store_wt(d.pos_final, vid, make_float4(o.p.x, o.p.y, o.p.z, 0.0f));
         store_wt(d.vel, vid, make_float4(o.vel.x, o.vel.y, o.vel.z, 0.0f));
         store_wt(d.pos_pred, vid, make_float4(o.pred.x, o.pred.y, o.pred.z, 0.0f));
     }
-    if (has_tet) {
-        if constexpr (kMode != kModeLeanState) store_wt(d.quat, e, q);
-        if (!kLean) {
-            store_wt(d.rest_a, e, make_float4(rest[0].x, rest[0].y, rest[0].z, rest[1].x));
-            store_wt(d.rest_b, e, make_float4(rest[1].y, rest[1].z, rest[2].x, rest[2].y));
-            if constexpr (kMode == kModeLeanState) store_wt1(d.rest_c1, e, rest[2].z);
-            else store_wt(d.rest_c, e, make_float4(rest[2].z, rest[3].x, rest[3].y, rest[3].z));
-        }
-    }
+    if (L.has_tet) store_record<kMode>(d, e, rest, q);
 }
 #define TETSIM_FRAME_KERNEL(name, mode, local)                                                                                         \
     __global__ __launch_bounds__(kTile, 2) void name(PJBlk d, uint32_t n, const int32_t* block_tile, float4* pbuf0, float4* pbuf1, uint32_t* err, \
@@ -659,6 +699,10 @@ TETSIM_FRAME_KERNEL(pjb_frame_kernel_local, kModeCarried, true)
 TETSIM_FRAME_KERNEL(pjb_frame_kernel_constant_rest_local, kModeConstantRest, true)
 TETSIM_FRAME_KERNEL(pjb_frame_kernel_lean_local, kModeLeanState, true)
 #undef TETSIM_FRAME_KERNEL
+inline auto* frame_kernel(int mode, bool local) {
+    return local ? by_mode(mode, pjb_frame_kernel_local, pjb_frame_kernel_constant_rest_local, pjb_frame_kernel_lean_local)
+                 : by_mode(mode, pjb_frame_kernel, pjb_frame_kernel_constant_rest, pjb_frame_kernel_lean);
+}
 // which XCD runs block i of a grid: the dispatcher hands consecutive workgroups to consecutive XCDs (round-robin), which the
 // host verifies with this kernel before it relies on it (hardware register XCC_ID)
 __global__ void pjb_probe_xcd_kernel(uint32_t* out) {
@@ -684,17 +728,14 @@ __global__ void pjb_probe_xcd_kernel(uint32_t* out) {
 // Tried and dropped: the hand-over inside the compute kernels (last-workgroup detection / every workgroup polling on entry).
 // Any per-workgroup device-scope atomic -- read-modify-write or load, one word or 64 words a cache line apart -- costs
 // ~20 ns and serialises: the 2,744-workgroup particle pass went from 7 us to 60-400 us.
-__device__ __forceinline__ void await_done(const PJSync& y) {
+__device__ __forceinline__ void await_done(uint32_t* flag, uint32_t* error, uint32_t timeout_ms) {
     if (threadIdx.x == 0) {
-        const long long t0 = wall_clock64(), limit = 100000ll * y.timeout_ms;   // 100 MHz ticks
-        while (__hip_atomic_load(y.flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) == 0u) {
+        const BoundedWait wait(timeout_ms);
+        while (__hip_atomic_load(flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) == 0u) {
             __builtin_amdgcn_s_sleep(4);
-            if (limit && wall_clock64() - t0 > limit) {
-                __hip_atomic_store(y.error, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                return;
-            }
+            if (wait.expired()) { BoundedWait::raise(error); return; }
         }
-        __hip_atomic_store(y.flag, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // consumed
+        __hip_atomic_store(flag, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // consumed
     }
 }
 
@@ -717,22 +758,18 @@ __device__ __forceinline__ void pjb_vertex_body(const PJBlk& d, uint32_t first, 
     for (uint32_t j0 = 0; j0 < d.vp_cols; j0 += 8u) {
         uint32_t idx[8];
         float4 g[8];
-#pragma unroll
-        for (uint32_t j = 0; j < 8u; j++) idx[j] = (j0 + j < d.vp_cols) ? col[static_cast<size_t>(j0 + j) * d.nv_pad] : 0xffffffffu;
+        ell_columns(col, j0, d.vp_cols, d.nv_pad, idx);
 #pragma unroll
         for (uint32_t j = 0; j < 8u; j++) {
             if constexpr (kCoherent) { const float4 t = load_coherent(d.partial, idx[j] != 0xffffffffu ? idx[j] : 0u); g[j] = idx[j] != 0xffffffffu ? t : make_float4(0.0f, 0.0f, 0.0f, 0.0f); }
             else g[j] = idx[j] != 0xffffffffu ? d.partial[idx[j]] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         }
-#pragma unroll
-        for (uint32_t j = 0; j < 8u; j++) { acc.x += g[j].x; acc.y += g[j].y; acc.z += g[j].z; }
+        add_eight(acc, g);
         if (__all(idx[7] == 0xffffffffu)) break;  // lists are front-packed: nobody in this wave has a ninth partial
     }
     // (the weight: sum of the rest volumes of the particle's live corners -- a constant, added up on the host in the tiles' entry order)
     const VertexOut o = pjb_vertex_update<false>(xyz(acc), d.wsum[v], xyz(d.fin_in[v]), *d.params, v);
-    store_wt(d.fin_out, v, make_float4(o.p.x, o.p.y, o.p.z, 0.0f));
-    if (d.vel) store_wt(d.vel, v, make_float4(o.vel.x, o.vel.y, o.vel.z, 0.0f));   // (null between two substeps of one call: nothing reads it there)
-    store_wt(d.pos_pred, v, make_float4(o.pred.x, o.pred.y, o.pred.z, 0.0f));
+    store_vertex_out(d, v, o, 0u, d.vel != nullptr);   // (no velocity array between two substeps of one call: nothing reads it there)
     if constexpr (kPeer) {
         // peer-to-peer halo: the prediction also goes straight into the ghost range of every neighbour that reads this particle
         // (write-through, system scope: peer memory over xGMI, or this device's own memory for partitions sharing a GPU).  The
@@ -781,28 +818,16 @@ __global__ __launch_bounds__(64) void pjb_vertex_kernel(PJBlk d, uint32_t first,
 // g / period, or the substep before for a wrapped entry.  The plain table is every tile, then every particle block; with a lag a particle
 // block sits a chosen distance behind the last tile on its particles' lists instead of behind the whole substep, so its first look
 // succeeds.  Progress rests on "whatever a block waits for has a smaller grid index", which the table's builder checks on the host.
-template <int kMode>
-__global__ __launch_bounds__(kTile, 2) void pjb_call_kernel(PJBlk d, uint32_t n_sub, uint32_t tile_count, uint32_t tiles_per_xcd, const uint32_t* __restrict__ sched, uint32_t period,
-                                                           uint32_t* err, uint32_t timeout_ms, DevParams pv, DevParams* pdev TETSIM_DBG_PARAM) {
-    const uint32_t turn = blockIdx.x / period, entry = sched[blockIdx.x - turn * period];   // (the period is a multiple of 8: an entry's position and blockIdx.x land on the same XCD)
-    if (blockIdx.x == 0u && threadIdx.x == 0u) store_params(pdev, pv);
-    const uint32_t back = (entry & kSchedWrapped) ? 1u : 0u, kind = entry >> 30, r = entry & kSchedIndexMask;
-    if (kind == kSchedEmpty || turn < back || turn - back >= n_sub) return;   // (nothing here, or a substep outside the call: the head of the first period, the tail)
-    const uint32_t sub = turn - back;
-    const uint32_t stamp = (d.epoch ? d.epoch : pv.epoch) + sub + 1u;
-    TETSIM_LAB_CALL_MARK(sub, n_sub);
-    if (kind == kSchedTile) {
-        const PJPoll poll = {r, sub ? stamp - 1u : 0u, err, timeout_ms};
-        pjb_tet_body<kMode, false, false, false, true>(d, 0u, tile_count, tiles_per_xcd TETSIM_DBG_ARG, nullptr, stamp, &poll);
-        return;
-    }
+// The kernel itself (below) is the schedule's decode and the dispatch; a tile entry is pjb_tet_body<.., Stage::Poll>, and this is a particle
+// entry -- block r of substep `sub`: pjb_vertex_body's gather and update behind looks at stamps
+__device__ __forceinline__ void pjb_call_particles(const PJBlk& d, const uint32_t r, const uint32_t sub, const uint32_t n_sub, const uint32_t stamp, uint32_t* const err,
+                                                   const uint32_t timeout_ms, const DevParams& pv TETSIM_DBG_PARAM) {
     const uint32_t v = r * kTile + threadIdx.x;
     if (v >= d.nv_owned) return;
     TETSIM_POLL_BEGIN();
     TETSIM_POLL_PB(0);
     float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     const uint32_t* col = d.vp_ell + v;
-    const long long limit = 100000ll * timeout_ms;   // 100 MHz ticks; 0 = unbounded
     const float wsum = d.wsum[v];
     // (the store of this particle's lane one substep before -- another wave of the same launch: past the caches, and looked at again below
     // until it carries that substep's number: it was stored ~a tile's lifetime ago, the first look finds it)
@@ -810,8 +835,7 @@ __global__ __launch_bounds__(kTile, 2) void pjb_call_kernel(PJBlk d, uint32_t n_
     for (uint32_t j0 = 0; j0 < d.vp_cols; j0 += 8u) {   // (pjb_vertex_body's gather, every sum looked at until it is this substep's)
         uint32_t idx[8];
         float4 g[8];
-#pragma unroll
-        for (uint32_t j = 0; j < 8u; j++) idx[j] = (j0 + j < d.vp_cols) ? col[static_cast<size_t>(j0 + j) * d.nv_pad] : 0xffffffffu;
+        ell_columns(col, j0, d.vp_cols, d.nv_pad, idx);
         uint32_t pend = 0;
         TETSIM_POLL_PB_FIRST(j0);
 #pragma unroll
@@ -821,7 +845,7 @@ __global__ __launch_bounds__(kTile, 2) void pjb_call_kernel(PJBlk d, uint32_t n_
             pend |= (idx[j] != 0xffffffffu && __float_as_uint(t.w) != stamp ? 1u : 0u) << j;
         }
         if (__builtin_amdgcn_ballot_w64(pend != 0u) != 0ull) {
-            const long long t0 = wall_clock64();
+            const BoundedWait wait(timeout_ms);
             do {
                 __builtin_amdgcn_s_sleep(TETSIM_POLL_SLEEP);
                 TETSIM_POLL_LOOK();
@@ -832,36 +856,44 @@ __global__ __launch_bounds__(kTile, 2) void pjb_call_kernel(PJBlk d, uint32_t n_
                         const float4 t = load_coherent(d.partial, idx[j]);
                         if (__float_as_uint(t.w) == stamp) { g[j] = t; pend &= ~(1u << j); }
                     }
-                if (limit && pend != 0u && wall_clock64() - t0 > limit) {   // never in a correct run; a wedged GPU helps nobody
-                    __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    pend = 0u;
-                }
+                if (wait.expired(pend != 0u)) { BoundedWait::raise(err); pend = 0u; }
             } while (__builtin_amdgcn_ballot_w64(pend != 0u) != 0ull);
         }
-#pragma unroll
-        for (uint32_t j = 0; j < 8u; j++) { acc.x += g[j].x; acc.y += g[j].y; acc.z += g[j].z; }
+        add_eight(acc, g);
         if (__all(idx[7] == 0xffffffffu)) break;
     }
     TETSIM_POLL_PB(2);
     if (sub) {
-        const long long t0 = wall_clock64();
+        const BoundedWait wait(timeout_ms);
         while (__float_as_uint(prev.w) != stamp - 1u) {
             __builtin_amdgcn_s_sleep(4);
             TETSIM_POLL_LOOK();
             asm volatile("" ::: "memory");
             prev = load_coherent(d.fin_in, v);
-            if (limit && wall_clock64() - t0 > limit) { __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); break; }
+            if (wait.expired()) { BoundedWait::raise(err); break; }
         }
     }
     TETSIM_POLL_PB(3);
     // (the one uniform branch of the body parameters taken HERE, around the whole update: with the table off this block runs the text it always
     // ran, its eight values in scalar registers -- per lane behind a join inside the update the benchmark's call was 1 % slower)
     const VertexOut o = pv.body_params ? pjb_vertex_update<false, true>(xyz(acc), wsum, xyz(prev), pv, v) : pjb_vertex_update<false, false>(xyz(acc), wsum, xyz(prev), pv, v);
-    store_wt(d.fin_out, v, make_float4(o.p.x, o.p.y, o.p.z, __uint_as_float(stamp)));
-    if (d.vel && sub + 1u == n_sub) store_wt(d.vel, v, make_float4(o.vel.x, o.vel.y, o.vel.z, 0.0f));   // (the velocity array: behind a call's last substep only)
-    store_wt(d.pos_pred, v, make_float4(o.pred.x, o.pred.y, o.pred.z, __uint_as_float(stamp)));
+    store_vertex_out(d, v, o, stamp, d.vel && sub + 1u == n_sub);   // (the velocity array: behind a call's last substep only)
     TETSIM_POLL_PB(4);
     TETSIM_POLL_PB_SAVE();
+}
+template <int kMode>
+__global__ __launch_bounds__(kTile, 2) void pjb_call_kernel(PJBlk d, uint32_t n_sub, uint32_t tile_count, uint32_t tiles_per_xcd, const uint32_t* __restrict__ sched, uint32_t period,
+                                                           uint32_t* err, uint32_t timeout_ms, DevParams pv, DevParams* pdev TETSIM_DBG_PARAM) {
+    const uint32_t turn = blockIdx.x / period, entry = sched[blockIdx.x - turn * period];   // (the period is a multiple of 8: an entry's position and blockIdx.x land on the same XCD)
+    if (blockIdx.x == 0u && threadIdx.x == 0u) store_params(pdev, pv);
+    const uint32_t back = (entry & kSchedWrapped) ? 1u : 0u, kind = entry >> 30, r = entry & kSchedIndexMask;
+    if (kind == kSchedEmpty || turn < back || turn - back >= n_sub) return;   // (nothing here, or a substep outside the call: the head of the first period, the tail)
+    const uint32_t sub = turn - back;
+    const uint32_t stamp = (d.epoch ? d.epoch : pv.epoch) + sub + 1u;
+    TETSIM_LAB_CALL_MARK(sub, n_sub);
+    if (kind != kSchedTile) return pjb_call_particles(d, r, sub, n_sub, stamp, err, timeout_ms, pv TETSIM_DBG_ARG);
+    const PJPoll poll = {r, sub ? stamp - 1u : 0u, err, timeout_ms};
+    pjb_tet_body<kMode, Stage::Poll>(d, 0u, tile_count, tiles_per_xcd TETSIM_DBG_ARG, nullptr, stamp, &poll);
 }
 __global__ __launch_bounds__(64) void pjb_vertex_kernel_raise(PJBlk d, uint32_t first, uint32_t count, uint32_t* sig, uint32_t* clear) {
     clear_then_raise(clear, sig);
@@ -872,12 +904,12 @@ __global__ __launch_bounds__(64) void pjb_vertex_kernel_raise(PJBlk d, uint32_t 
 // one-wave wait kernel this replaces cost the main queue a third launch boundary per substep.
 __global__ __launch_bounds__(64) void pjb_vertex_kernel_await(PJBlk d, uint32_t first, uint32_t count, uint32_t* flag, uint32_t* error, uint32_t timeout_ms) {
     if (threadIdx.x == 0) {
-        const long long t0 = wall_clock64(), limit = 100000ll * timeout_ms;   // 100 MHz ticks
+        const BoundedWait wait(timeout_ms);
         // (RELAXED: an acquire load is a load plus a cache invalidation, and thousands of waves invalidating their XCD's L2 on every
         // look took the substep from 37 to 53-150 us)
         while (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) {
             __builtin_amdgcn_s_sleep(16);
-            if (limit && wall_clock64() - t0 > limit) { __hip_atomic_store(error, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); break; }
+            if (wait.expired()) { BoundedWait::raise(error); break; }
         }
     }
     __builtin_amdgcn_wave_barrier();
@@ -899,16 +931,14 @@ __global__ __launch_bounds__(64) void pjb_vertex_kernel_peer(PJBlk d, uint32_t f
 // raise of substep s+2 lands on the word of substep s only after its consumer has cleared it -- the dependency cycle orders
 // them -- whereas ONE word per neighbour could see two raises before a wait (s+1's while this wave still waits for V).
 __global__ void pjb_wait_peers_kernel(uint32_t* flag, uint32_t* error, uint32_t timeout_ms, PJPeerSync w) {
-    PJSync y;
-    y.flag = flag; y.error = error; y.timeout_ms = timeout_ms;
     const uint32_t t = threadIdx.x;
     if (t < w.n_raise) __hip_atomic_store(w.raise[t], 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    if (y.flag) await_done(y);
+    if (flag) await_done(flag, error, timeout_ms);
     if (t < w.n_wait) {
-        const long long t0 = wall_clock64(), limit = 100000ll * y.timeout_ms;
+        const BoundedWait wait(timeout_ms);
         while (__hip_atomic_load(w.wait[t], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM) == 0u) {
             __builtin_amdgcn_s_sleep(4);
-            if (limit && wall_clock64() - t0 > limit) { __hip_atomic_store(y.error, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); break; }
+            if (wait.expired()) { BoundedWait::raise(error); break; }
         }
         __hip_atomic_store(w.wait[t], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         if (w.delay_us) { const long long d0 = wall_clock64(); while (wall_clock64() - d0 < 100ll * w.delay_us) __builtin_amdgcn_s_sleep(8); }
@@ -916,11 +946,7 @@ __global__ void pjb_wait_peers_kernel(uint32_t* flag, uint32_t* error, uint32_t 
 }
 // (scalar arguments, not the PJSync struct: the unit is built with kernel-argument preload, which hands leading SCALARS to the wave in
 // SGPRs -- these one-wave kernels sit on the substep's critical chains and have nothing to hide a scalar load behind)
-__global__ void pjb_wait_kernel(uint32_t* flag, uint32_t* error, uint32_t timeout_ms) {
-    PJSync y;
-    y.flag = flag; y.error = error; y.timeout_ms = timeout_ms;
-    await_done(y);
-}
+__global__ void pjb_wait_kernel(uint32_t* flag, uint32_t* error, uint32_t timeout_ms) { await_done(flag, error, timeout_ms); }
 __global__ void pjb_signal_kernel(uint32_t* flag, uint32_t* clear) {
     if (threadIdx.x == 0) {
         if (clear) __hip_atomic_store(clear, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -985,27 +1011,19 @@ void pjb_launch_tet(hipStream_t s, const PJBlk& d, uint32_t tile_first, uint32_t
     if (tile_count == 0) return;   // (callers with a word to raise or clear check this themselves)
     if (raise_word || clear_word) return launch_tet_x(s, d, tile_first, tile_count, TetRaise{raise_word, clear_word}, e0, e1);
     const uint32_t per_xcd = (tile_count + 7u) / 8u;
-    const int mode = blk_mode(d);
-    auto* kernel = mode == kModeConstantRest ? pjb_tet_kernel_constant_rest : mode == kModeLeanState ? pjb_tet_kernel_lean : pjb_tet_kernel;
-    if (e0) hipExtLaunchKernelGGL(kernel, dim3(per_xcd * 8u), dim3(kTile), 0, s, e0, e1, 0, d, tile_first, tile_count, per_xcd TETSIM_DBG_LAUNCH);
-    else hipLaunchKernelGGL(kernel, dim3(per_xcd * 8u), dim3(kTile), 0, s, d, tile_first, tile_count, per_xcd TETSIM_DBG_LAUNCH);
+    launch(by_mode(blk_mode(d), pjb_tet_kernel, pjb_tet_kernel_constant_rest, pjb_tet_kernel_lean), dim3(per_xcd * 8u), dim3(kTile), s, e0, e1, d, tile_first, tile_count, per_xcd TETSIM_DBG_LAUNCH);
 }
 void pjb_launch_call(hipStream_t s, const PJBlk& d, const PJCallSched& sched, uint32_t n, uint32_t* err, uint32_t timeout_ms, const DevParams& params, DevParams* params_dev) {
     if (d.nb == 0 || n == 0 || sched.period == 0) return;
     const uint32_t per_xcd = (d.nb + 7u) / 8u;
-    const int mode = blk_mode(d);
-    auto* kernel = mode == kModeConstantRest ? pjb_call_kernel<kModeConstantRest> : mode == kModeLeanState ? pjb_call_kernel<kModeLeanState> : pjb_call_kernel<kModeCarried>;
-    hipLaunchKernelGGL(kernel, dim3(sched.period * n + sched.tail), dim3(kTile), 0, s, d, n, d.nb, per_xcd, sched.entry, sched.period, err, timeout_ms, params, params_dev TETSIM_DBG_LAUNCH);
+    launch(by_mode(blk_mode(d), pjb_call_kernel<kModeCarried>, pjb_call_kernel<kModeConstantRest>, pjb_call_kernel<kModeLeanState>), dim3(sched.period * n + sched.tail), dim3(kTile), s, nullptr, nullptr,
+           d, n, d.nb, per_xcd, sched.entry, sched.period, err, timeout_ms, params, params_dev TETSIM_DBG_LAUNCH);
 }
 void pjb_launch_tet_fused(hipStream_t s, const PJBlk& d, hipEvent_t e0, hipEvent_t e1) { launch_tet_x(s, d, 0u, d.nb, TetFused{0u}, e0, e1); }
 void pjb_launch_frame(hipStream_t s, const PJBlk& d, uint32_t n, const int32_t* block_tile, uint32_t blocks, bool local, float4* pbuf0, float4* pbuf1,
                       uint32_t* err, uint32_t timeout_ms, const DevParams& params, DevParams* params_dev, hipEvent_t e0, hipEvent_t e1) {
     if (d.nb == 0 || n == 0 || blocks == 0) return;
-    const int mode = blk_mode(d);
-    auto* kernel = local ? (mode == kModeConstantRest ? pjb_frame_kernel_constant_rest_local : mode == kModeLeanState ? pjb_frame_kernel_lean_local : pjb_frame_kernel_local)
-                         : (mode == kModeConstantRest ? pjb_frame_kernel_constant_rest : mode == kModeLeanState ? pjb_frame_kernel_lean : pjb_frame_kernel);
-    if (e0) hipExtLaunchKernelGGL(kernel, dim3(blocks), dim3(kTile), 0, s, e0, e1, 0, d, n, block_tile, pbuf0, pbuf1, err, timeout_ms, params, params_dev);
-    else hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kTile), 0, s, d, n, block_tile, pbuf0, pbuf1, err, timeout_ms, params, params_dev);
+    launch(frame_kernel(blk_mode(d), local), dim3(blocks), dim3(kTile), s, e0, e1, d, n, block_tile, pbuf0, pbuf1, err, timeout_ms, params, params_dev);
 }
 uint32_t pjb_frame_capacity(int mode, uint32_t* compute_units) {
     int per_cu = 0, dev = 0;
@@ -1014,10 +1032,8 @@ uint32_t pjb_frame_capacity(int mode, uint32_t* compute_units) {
     // the smaller answer of the two placements' kernels: which one a body launches is decided after this query (a body too large for the
     // one-XCD placement takes the other), and their register counts need not stay equal
     int per_cu_any = 0;
-    auto* k_local = mode == kModeConstantRest ? pjb_frame_kernel_constant_rest_local : mode == kModeLeanState ? pjb_frame_kernel_lean_local : pjb_frame_kernel_local;
-    auto* k_any = mode == kModeConstantRest ? pjb_frame_kernel_constant_rest : mode == kModeLeanState ? pjb_frame_kernel_lean : pjb_frame_kernel;
-    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_local, static_cast<int>(kTile), 0);
-    const hipError_t e2 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_any, k_any, static_cast<int>(kTile), 0);
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, frame_kernel(mode, true), static_cast<int>(kTile), 0);
+    const hipError_t e2 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_any, frame_kernel(mode, false), static_cast<int>(kTile), 0);
     if (e != hipSuccess || e2 != hipSuccess || per_cu <= 0 || per_cu_any <= 0) return 0;
     per_cu = std::min(per_cu, per_cu_any);
     if (compute_units) *compute_units = static_cast<uint32_t>(prop.multiProcessorCount);
@@ -1033,7 +1049,7 @@ void pjb_wait_capacity(int mode, uint32_t* vertex_waves, uint32_t* hwait_blocks)
     hipDeviceProp_t prop;
     if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_v, pjb_vertex_kernel_await, 64, 0) != hipSuccess) per_cu_v = 0;
-    auto* k_hwait = mode == kModeConstantRest ? pjb_tet_kernel_x<kModeConstantRest, TetHwait> : mode == kModeLeanState ? pjb_tet_kernel_x<kModeLeanState, TetHwait> : pjb_tet_kernel_x<kModeCarried, TetHwait>;
+    auto* k_hwait = by_mode(mode, pjb_tet_kernel_x<kModeCarried, TetHwait>, pjb_tet_kernel_x<kModeConstantRest, TetHwait>, pjb_tet_kernel_x<kModeLeanState, TetHwait>);
     const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_t, k_hwait, static_cast<int>(kTile), 0);
     if (e != hipSuccess) per_cu_t = 0;
     const uint32_t cus = static_cast<uint32_t>(std::max(prop.multiProcessorCount, 0));
@@ -1068,18 +1084,12 @@ void pjb_launch_wait(hipStream_t s, const PJSync& y) { hipLaunchKernelGGL(pjb_wa
 void pjb_launch_signal(hipStream_t s, const PJSync& y, uint32_t* clear_word) { hipLaunchKernelGGL(pjb_signal_kernel, dim3(1), dim3(64), 0, s, y.flag, clear_word); }
 void pjb_launch_vertex_await(hipStream_t s, const PJBlk& d, uint32_t first, uint32_t count, const PJSync& y, hipEvent_t e0, hipEvent_t e1) {
     if (count == 0) return;
-    if (e0) hipExtLaunchKernelGGL(pjb_vertex_kernel_await, dim3((count + 63u) / 64u), dim3(64), 0, s, e0, e1, 0, d, first, count, y.flag, y.error, y.timeout_ms);
-    else hipLaunchKernelGGL(pjb_vertex_kernel_await, dim3((count + 63u) / 64u), dim3(64), 0, s, d, first, count, y.flag, y.error, y.timeout_ms);
+    launch(pjb_vertex_kernel_await, dim3((count + 63u) / 64u), dim3(64), s, e0, e1, d, first, count, y.flag, y.error, y.timeout_ms);
 }
 void pjb_launch_vertex(hipStream_t s, const PJBlk& d, uint32_t first, uint32_t count, hipEvent_t e0, hipEvent_t e1, uint32_t* raise_word, uint32_t* clear_word) {
     if (count == 0) return;
-    if (raise_word || clear_word) {
-        if (e0) hipExtLaunchKernelGGL(pjb_vertex_kernel_raise, dim3((count + 63u) / 64u), dim3(64), 0, s, e0, e1, 0, d, first, count, raise_word, clear_word);
-        else hipLaunchKernelGGL(pjb_vertex_kernel_raise, dim3((count + 63u) / 64u), dim3(64), 0, s, d, first, count, raise_word, clear_word);
-        return;
-    }
-    if (e0) hipExtLaunchKernelGGL(pjb_vertex_kernel, dim3((count + 63u) / 64u), dim3(64), 0, s, e0, e1, 0, d, first, count);
-    else hipLaunchKernelGGL(pjb_vertex_kernel, dim3((count + 63u) / 64u), dim3(64), 0, s, d, first, count);
+    if (raise_word || clear_word) launch(pjb_vertex_kernel_raise, dim3((count + 63u) / 64u), dim3(64), s, e0, e1, d, first, count, raise_word, clear_word);
+    else launch(pjb_vertex_kernel, dim3((count + 63u) / 64u), dim3(64), s, e0, e1, d, first, count);
 }
 void pjb_launch_recover_quats(hipStream_t s, const PJBlk& d, const float4* rest0_a, const float4* rest0_b, const float4* rest0_c) {
     if (d.nt == 0 || !d.lean_state) return;
