@@ -172,6 +172,25 @@ __device__ __forceinline__ void body_compliances_of(const DevParams& P, uint32_t
         devC = r->dev_compliance; volC = r->vol_compliance;
     }
 }
+// What every tet solve starts from, in this unit's arithmetic: the time step and the two compliances of the handle -- of the body of tet e
+// where one is named (body_compliances; a cluster's tets and particles are one body's, so its first tet names it).
+struct TetScalars { T dt, devC, volC; };
+__device__ __forceinline__ TetScalars tet_scalars(const DevParams& P) {
+#if TETSIM_FAST
+    return {P.dt, static_cast<T>(P.d_dev_compliance), static_cast<T>(P.d_vol_compliance)};
+#else
+    return {P.d_dt, P.d_dev_compliance, P.d_vol_compliance};
+#endif
+}
+__device__ __forceinline__ TetScalars tet_scalars(const DevParams& P, uint32_t e) {
+    TetScalars s = tet_scalars(P);
+    body_compliances(P, e, s.devC, s.volC);
+    return s;
+}
+// ... and what solve_quad takes in their place: a_dev = devCompliance / dt / dt, a_vol likewise (left to right, as `devC / dt / dt * irv`
+// evaluates in solve_elem), c_off = volCompliance / devCompliance
+struct QuadScalars { T a_dev, a_vol, c_off; };
+__device__ __forceinline__ QuadScalars quad_scalars(const TetScalars& s) { return {s.devC / s.dt / s.dt, s.volC / s.dt / s.dt, s.volC / s.devC}; }
 
 // One dependency level: lanes [first, first+count) of the solve order.
 template <bool kWriteThrough>
@@ -179,15 +198,7 @@ __global__ __launch_bounds__(256) void TETSIM_SFX(nh_level_kernel_)(NHDev d, uin
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count) return;
     const uint32_t e = first + i;
-    const DevParams& P = *d.params;
-#if TETSIM_FAST
-    const T dt = P.dt;
-    T devC = static_cast<T>(P.d_dev_compliance), volC = static_cast<T>(P.d_vol_compliance);
-#else
-    const T dt = P.d_dt;
-    T devC = P.d_dev_compliance, volC = P.d_vol_compliance;
-#endif
-    body_compliances(P, e, devC, volC);
+    const TetScalars S = tet_scalars(*d.params, e);
     const int4 id = d.tet_idx[e];
     const float4 ia = d.irp_a[e], ib = d.irp_b[e], ic = d.irp_c[e];
     const float ir[9] = {ia.x, ia.y, ia.z, ia.w, ib.x, ib.y, ib.z, ib.w, ic.x};
@@ -197,7 +208,7 @@ __global__ __launch_bounds__(256) void TETSIM_SFX(nh_level_kernel_)(NHDev d, uin
     float im[4];
 #pragma unroll
     for (int k = 0; k < 4; k++) { p[k].x = p4[k].x; p[k].y = p4[k].y; p[k].z = p4[k].z; im[k] = p4[k].w; }
-    const T ve = solve_elem(p, im, ir, static_cast<T>(ic.y), dt, devC, volC);
+    const T ve = solve_elem(p, im, ir, static_cast<T>(ic.y), S.dt, S.devC, S.volC);
     if (d.vol_err) d.vol_err[d.order[e]] = static_cast<double>(ve);   // (null in a sweep that is not its call's last: the call leaves its LAST sweep's behind)
     if constexpr (kWriteThrough) {  // big levels: the next level's launch reads these from other CUs and XCDs (see the cluster kernel)
         store_wt(d.pos, static_cast<uint32_t>(id.x), make_float4(p[0].x, p[0].y, p[0].z, im[0]));
@@ -423,14 +434,7 @@ __global__ __launch_bounds__(64) void TETSIM_SFX(nh_cluster_kernel_)(NHDev d, NH
     const uint32_t lane = threadIdx.x, i = blockIdx.x * 64u + lane;
     if (i >= L.clusters) return;
     const DevParams& P = *d.params;
-#if TETSIM_FAST
-    const T dt = P.dt;
-    T devC = static_cast<T>(P.d_dev_compliance), volC = static_cast<T>(P.d_vol_compliance);
-#else
-    const T dt = P.d_dt;
-    T devC = P.d_dev_compliance, volC = P.d_vol_compliance;
-#endif
-    body_compliances(P, L.first[0] + i, devC, volC);   // (a cluster's tets and particles are one body's: its first tet names it)
+    const TetScalars S = tet_scalars(P, L.first[0] + i);
     int32_t vid[kNHClusterVerts];
 #pragma unroll
     for (uint32_t k = 0; k < kNHClusterVerts; k++) vid[k] = L.slot_vid[static_cast<size_t>(k) * L.clusters + i];
@@ -476,7 +480,7 @@ __global__ __launch_bounds__(64) void TETSIM_SFX(nh_cluster_kernel_)(NHDev d, NH
         g3 p[4] = {{q0.x, q0.y, q0.z}, {q1.x, q1.y, q1.z}, {q2.x, q2.y, q2.z}, {q3.x, q3.y, q3.z}};
         const float im[4] = {q0.w, q1.w, q2.w, q3.w};
         const float ir[9] = {ia.x, ia.y, ia.z, ia.w, ib.x, ib.y, ib.z, ib.w, ic.x};
-        const T ve = solve_elem(p, im, ir, static_cast<T>(ic.y), dt, devC, volC);
+        const T ve = solve_elem(p, im, ir, static_cast<T>(ic.y), S.dt, S.devC, S.volC);
         if (d.vol_err) d.vol_err[ord] = static_cast<double>(ve);
         s_pos[s0] = make_float4(p[0].x, p[0].y, p[0].z, im[0]);  // corner order as in the level kernel
         s_pos[s1] = make_float4(p[1].x, p[1].y, p[1].z, im[1]);
@@ -661,13 +665,13 @@ __device__ __forceinline__ NHTetRecord nh_load_record(const NHDev& d, uint32_t e
     return r;
 }
 // one tet on the quad's four lanes out of a float4 particle array `sp` (LDS or memory): lane c works on float c of every record
-__device__ __forceinline__ T nh_solve_record_quad(float* const sp, const NHTetRecord& r, uint32_t c, T a_dev, T a_vol, T c_off) {
+__device__ __forceinline__ T nh_solve_record_quad(float* const sp, const NHTetRecord& r, uint32_t c, const QuadScalars& Q) {
     const uint32_t a0 = 4u * static_cast<uint32_t>(r.id.x) + c, a1 = 4u * static_cast<uint32_t>(r.id.y) + c,
                    a2 = 4u * static_cast<uint32_t>(r.id.z) + c, a3 = 4u * static_cast<uint32_t>(r.id.w) + c;
     float p[4] = {sp[a0], sp[a1], sp[a2], sp[a3]};   // lanes 0..2: a coordinate; lane 3: the inverse masses
     const float im[4] = {quad<kQuadLane3>(p[0]), quad<kQuadLane3>(p[1]), quad<kQuadLane3>(p[2]), quad<kQuadLane3>(p[3])};
     const float ir[9] = {r.a.x, r.a.y, r.a.z, r.a.w, r.b.x, r.b.y, r.b.z, r.b.w, r.c.x};
-    const T ve = solve_quad(p, im, ir, static_cast<T>(r.c.y), a_dev, a_vol, c_off);
+    const T ve = solve_quad(p, im, ir, static_cast<T>(r.c.y), Q.a_dev, Q.a_vol, Q.c_off);
     if (c < 3u) { sp[a0] = p[0]; sp[a1] = p[1]; sp[a2] = p[2]; sp[a3] = p[3]; }   // (lane 3 leaves the inverse masses alone)
     return ve;
 }
@@ -686,15 +690,9 @@ __global__ __launch_bounds__(512) void TETSIM_SFX(nh_frame_kernel_)(NHDev d, con
     float* const sp = reinterpret_cast<float*>(s_frame);
     const uint32_t tid = threadIdx.x, nthr = blockDim.x, c = tid & 3u, qd = tid >> 2, nq = nthr >> 2;
     const DevParams& P = pv;
-#if TETSIM_FAST
-    const T dt = P.dt;
-    T devC = static_cast<T>(P.d_dev_compliance), volC = static_cast<T>(P.d_vol_compliance);
-#else
-    const T dt = P.d_dt;
-    T devC = P.d_dev_compliance, volC = P.d_vol_compliance;
-#endif
-    body_compliances_of(P, body, devC, volC);   // (one workgroup per body: the row arrives through scalar loads)
-    const T a_dev = devC / dt / dt, a_vol = volC / dt / dt, c_off = volC / devC;   // (left to right, as `devC / dt / dt * irv` evaluates)
+    TetScalars S = tet_scalars(P);
+    body_compliances_of(P, body, S.devC, S.volC);   // (one workgroup per body: the row arrives through scalar loads)
+    const QuadScalars Q = quad_scalars(S);
     const VParams q = load_vparams_of(P, body);
     for (uint32_t v = tid; v < nvb; v += nthr) {   // the call starts with a prediction (Softbody.js:198-202), as enqueue_substep(first) does
         float4 pos = d.pos[vbase + v], vel = d.vel[vbase + v], prev;
@@ -746,13 +744,13 @@ __global__ __launch_bounds__(512) void TETSIM_SFX(nh_frame_kernel_)(NHDev d, con
                     // the corners as indices into this body's LDS arrays
                     cur.id.x -= static_cast<int32_t>(vbase); cur.id.y -= static_cast<int32_t>(vbase); cur.id.z -= static_cast<int32_t>(vbase); cur.id.w -= static_cast<int32_t>(vbase);
                     T ve;
-                    if (quads) ve = nh_solve_record_quad(sp, cur, c, a_dev, a_vol, c_off);
+                    if (quads) ve = nh_solve_record_quad(sp, cur, c, Q);
                     else {
                         const float4 q0 = s_pos[cur.id.x], q1 = s_pos[cur.id.y], q2 = s_pos[cur.id.z], q3 = s_pos[cur.id.w];
                         g3 p[4] = {{q0.x, q0.y, q0.z}, {q1.x, q1.y, q1.z}, {q2.x, q2.y, q2.z}, {q3.x, q3.y, q3.z}};
                         const float im[4] = {q0.w, q1.w, q2.w, q3.w};
                         const float ir[9] = {cur.a.x, cur.a.y, cur.a.z, cur.a.w, cur.b.x, cur.b.y, cur.b.z, cur.b.w, cur.c.x};
-                        ve = solve_elem(p, im, ir, static_cast<T>(cur.c.y), dt, devC, volC);
+                        ve = solve_elem(p, im, ir, static_cast<T>(cur.c.y), S.dt, S.devC, S.volC);
                         s_pos[cur.id.x] = make_float4(p[0].x, p[0].y, p[0].z, im[0]);
                         s_pos[cur.id.y] = make_float4(p[1].x, p[1].y, p[1].z, im[1]);
                         s_pos[cur.id.z] = make_float4(p[2].x, p[2].y, p[2].z, im[2]);
@@ -788,19 +786,82 @@ __global__ __launch_bounds__(512) void TETSIM_SFX(nh_frame_kernel_)(NHDev d, con
 __global__ __launch_bounds__(256) void TETSIM_SFX(nh_level4_kernel_)(NHDev d, uint32_t first, uint32_t count) {
     const uint32_t i = (blockIdx.x * 256u + threadIdx.x) >> 2, c = threadIdx.x & 3u;
     if (i >= count) return;   // (whole quads)
-    const DevParams& P = *d.params;
-#if TETSIM_FAST
-    const T dt = P.dt;
-    T devC = static_cast<T>(P.d_dev_compliance), volC = static_cast<T>(P.d_vol_compliance);
-#else
-    const T dt = P.d_dt;
-    T devC = P.d_dev_compliance, volC = P.d_vol_compliance;
-#endif
-    body_compliances(P, first + i, devC, volC);
-    const T a_dev = devC / dt / dt, a_vol = volC / dt / dt, c_off = volC / devC;
     const uint32_t e = first + i;
-    const T ve = nh_solve_record_quad(reinterpret_cast<float*>(d.pos), nh_load_record(d, e), c, a_dev, a_vol, c_off);
+    const QuadScalars Q = quad_scalars(tet_scalars(*d.params, e));
+    const T ve = nh_solve_record_quad(reinterpret_cast<float*>(d.pos), nh_load_record(d, e), c, Q);
     if (c == 0u && d.vol_err) d.vol_err[d.order[e]] = static_cast<double>(ve);
+}
+
+// ---- the steps of one cluster on four lanes ------------------------------------------------------------------------------------------
+// Three kernels execute a cluster this way and promise each other's bits: nh_cluster4_kernel (one launch per colour), nh_sweep1_kernel
+// (per substep) and nh_call_kernel (per call).  nh_cluster4_kernel and nh_sweep1_kernel take the steps they share from ONE routine
+// each: which cluster and coordinate a lane is (quad_lane), the solve's scalars (tet_scalars, quad_scalars above), the tets' streamed
+// records (ClusterRecords, cluster_tet), the chain of solves out of LDS (solve_cluster_steps) and the particle pass of a first toucher
+// (fold_particle above); the sweep also the colour of a block (find_colour) and a look at a handed-on particle (take_stamped).
+// nh_call_kernel is NOT built from them: it keeps every one of these steps WRITTEN OUT, kept equal to the routines by hand.  Built from
+// them it has the same registers, LDS and waves and is 124 bytes shorter, and a substep of the 1 M-tet lattice costs 0.1-0.4 % more in
+// four sessions of five; no single routine accounts for it, only the kernel with every step written out measures as before
+// (profiles/nh_cluster_refactor.txt, sections 5 to 7).  A change to a routine below is therefore made a second time in nh_call_kernel;
+// tests/test_gpu_nh_cluster_paths_golden.py and the twin tests hold the two to each other's bits.  Also kept in each kernel: the ORDER in
+// which its loads are issued with the barriers that hold it, the polling loop and the stamped hand-over tail of the two one-launch kernels.
+// Lane `lane` of a wave works on coordinate c (3: the inverse masses) of the wave's cluster cl, which is cluster i of its colour; `block`
+// counts from the colour's first block.  s_pos: the wave's own LDS slice [vertex slot][cluster of the wave] -- four independent waves per
+// workgroup, no barrier anywhere.  (A lane with i >= clusters leaves at once, in whole quads: the DPP moves stay inside a quad.)
+struct QuadLane { float4* s_pos; uint32_t lane, c, cl, i; };
+__device__ __forceinline__ QuadLane quad_lane(float4 (*s_all)[kNHClusterVerts * 16], uint32_t block) {
+    const uint32_t lane = threadIdx.x & 63u;
+    return {s_all[threadIdx.x >> 6], lane, lane & 3u, lane >> 2, (block * 4u + (threadIdx.x >> 6)) * 16u + (lane >> 2)};
+}
+// The tet of step j of cluster i: a step the cluster does not have names its first tet.  The two routines say the same; which one a
+// kernel takes decides what the compiler makes of it, and the kernels keep what they had before these routines existed.  Where L is a
+// kernel argument (nh_cluster4_kernel) first[] sits in scalar registers: both sums are formed and one is chosen.  Where L lies in memory
+// (the one-launch kernels' colour table) the choice is made between the two READS of first[]: one load at a lane-dependent address,
+// which this step's records then wait for.  (Written as the one expression below, the kernel-argument case came out either way,
+// depending on the code around it.)  The forms are NOT interchangeable in speed: with the select form nh_call_kernel measures 0.858
+// against 0.833 ms per 20 substeps on the 1 M-tet lattice, five pairs (profiles/nh_cluster_refactor.txt, which also shows how to tell
+// the forms apart in the assembly: a global_load_dword and s_waitcnt vmcnt(0) in front of every step's five record loads, or none).
+__device__ __forceinline__ uint32_t cluster_tet(const NHClusterLaunch& L, uint32_t i, uint32_t j) {
+    return (j < L.nsteps && i < L.count[j]) ? L.first[j] + i : L.first[0] + i;
+}
+__device__ __forceinline__ uint32_t cluster_tet_of_arguments(const NHClusterLaunch& L, uint32_t i, uint32_t j) {
+    const uint32_t e_j = L.first[j] + i, e_0 = L.first[0] + i;
+    return (j < L.nsteps && i < L.count[j]) ? e_j : e_0;
+}
+// The streamed records of the cluster's tets.  Order of issue in every kernel (vmcnt retires in order): ids and the FIRST tet's record,
+// then -- as soon as the ids are here -- the particles, then every other tet's record, unconditionally (a step this cluster does not
+// have re-reads its first tet).  The first solve starts when the particles land while the later records stream in.  The kernels hold
+// that order with a sched_barrier behind request(0), behind the particles and behind request(1..7): left alone, the scheduler issues
+// ids -> particles -> records, three dependent trips.
+struct ClusterRecords {
+    uint32_t cs[kNHClusterTets];
+    float4 ia[kNHClusterTets], ib[kNHClusterTets], ic[kNHClusterTets];
+    int32_t ord[kNHClusterTets];
+    __device__ __forceinline__ void request(const NHDev& d, uint32_t j, uint32_t e) {   // e: cluster_tet
+        cs[j] = d.corner_slots[e];
+        ia[j] = d.irp_a[e]; ib[j] = d.irp_b[e]; ic[j] = d.irp_c[e];
+        ord[j] = d.order[e];
+    }
+};
+// The cluster's tets one after the other out of the wave's LDS slice (Gauss-Seidel inside the cluster, in the sequential order): one wave
+// per slice and the LDS operations of a wave execute in order, so no barrier.  store_vol_err: this sweep's volError is what the call
+// leaves behind (the call kernel: its last substep's only).
+__device__ __forceinline__ void solve_cluster_steps(const QuadLane& q, const NHClusterLaunch& L, const ClusterRecords& r, const QuadScalars& Q,
+                                                    const NHDev& d, bool store_vol_err) {
+    float* const sp = reinterpret_cast<float*>(q.s_pos) + q.lane;   // this lane's float of slot 0; slot s is 64 floats on per s
+#pragma unroll
+    for (uint32_t j = 0; j < kNHClusterTets; j++) {
+        if (j >= L.nsteps) break;            // (uniform)
+        if (q.i < L.count[j]) {              // (counts do not increase with j; whole quads agree)
+            // float index of (slot, cl, c) = slot * 64 + lane: one field extraction and one add per corner
+            const uint32_t a0 = (r.cs[j] << 6) & 0x3fc0u, a1 = (r.cs[j] >> 2) & 0x3fc0u, a2 = (r.cs[j] >> 10) & 0x3fc0u, a3 = (r.cs[j] >> 18) & 0x3fc0u;
+            float p[4] = {sp[a0], sp[a1], sp[a2], sp[a3]};   // lanes 0..2: a coordinate; lane 3: the inverse masses
+            const float im[4] = {quad<kQuadLane3>(p[0]), quad<kQuadLane3>(p[1]), quad<kQuadLane3>(p[2]), quad<kQuadLane3>(p[3])};
+            const float ir[9] = {r.ia[j].x, r.ia[j].y, r.ia[j].z, r.ia[j].w, r.ib[j].x, r.ib[j].y, r.ib[j].z, r.ib[j].w, r.ic[j].x};
+            const T ve = solve_quad(p, im, ir, static_cast<T>(r.ic[j].y), Q.a_dev, Q.a_vol, Q.c_off);
+            if (q.c == 0u && d.vol_err && store_vol_err) d.vol_err[r.ord[j]] = static_cast<double>(ve);
+            if (q.c < 3u) { sp[a0] = p[0]; sp[a1] = p[1]; sp[a2] = p[2]; sp[a3] = p[3]; }   // (lane 3 leaves the inverse masses alone)
+        }
+    }
 }
 
 // The first five arguments repeat what the first memory trips need (ids, particles, mask, count) as plain scalars in front of the
@@ -810,39 +871,20 @@ template <bool kWriteThrough, bool kFold>
 __global__ __launch_bounds__(256) void TETSIM_SFX(nh_cluster4_kernel_)(const int32_t* __restrict__ a_slot_vid, const float4* __restrict__ a_pos,
                                                                const uint8_t* __restrict__ a_first_mask, const float4* __restrict__ a_prev,
                                                                uint32_t a_clusters, NHDev d, NHClusterLaunch L) {
-    // four independent waves per workgroup (no barrier anywhere)
-    __shared__ float4 s_all[4][kNHClusterVerts * 16];   // [wave][vertex slot][cluster of the wave]
-    float4* const s_pos = s_all[threadIdx.x >> 6];
-    const uint32_t lane = threadIdx.x & 63u, c = lane & 3u, cl = lane >> 2, i = (blockIdx.x * 4u + (threadIdx.x >> 6)) * 16u + cl;
-    if (i >= a_clusters) return;   // (whole quads leave: the DPP moves stay inside a quad)
+    __shared__ float4 s_all[4][kNHClusterVerts * 16];
+    const QuadLane q = quad_lane(s_all, blockIdx.x);
+    float4* const s_pos = q.s_pos;
+    const uint32_t c = q.c, cl = q.cl, i = q.i;
+    if (i >= a_clusters) return;
     const DevParams& P = *d.params;
-#if TETSIM_FAST
-    const T dt = P.dt;
-    T devC = static_cast<T>(P.d_dev_compliance), volC = static_cast<T>(P.d_vol_compliance);
-#else
-    const T dt = P.d_dt;
-    T devC = P.d_dev_compliance, volC = P.d_vol_compliance;
-#endif
-    body_compliances(P, L.first[0] + i, devC, volC);   // (the cluster's body, as in nh_cluster_kernel)
-    const T a_dev = devC / dt / dt, a_vol = volC / dt / dt, c_off = volC / devC;
+    const QuadScalars Q = quad_scalars(tet_scalars(P, L.first[0] + i));
     // the cluster's <= 8 particles: lane c fetches slots c and c + 4 (unconditionally, see nh_cluster_kernel) and writes them back
     const int32_t va = a_slot_vid[static_cast<size_t>(c) * a_clusters + i], vb = a_slot_vid[static_cast<size_t>(c + 4u) * a_clusters + i];
     [[maybe_unused]] uint32_t fmask = 0;
     if constexpr (kFold) fmask = a_first_mask[i];
-    // Order of issue (vmcnt retires in order): ids and the FIRST tet's record, then -- as soon as the ids are here -- the particles,
-    // then every other tet's record, unconditionally (a step this cluster does not have re-reads its first tet).  The first solve
-    // starts when the particles land while the later records stream in.
-    uint32_t cs[kNHClusterTets];
-    float4 ia[kNHClusterTets], ib[kNHClusterTets], ic[kNHClusterTets];
-    int32_t ord[kNHClusterTets];
-    auto request = [&](uint32_t j) {
-        const uint32_t e = (j < L.nsteps && i < L.count[j]) ? L.first[j] + i : L.first[0] + i;
-        cs[j] = d.corner_slots[e];
-        ia[j] = d.irp_a[e]; ib[j] = d.irp_b[e]; ic[j] = d.irp_c[e];
-        ord[j] = d.order[e];
-    };
-    request(0);
-    __builtin_amdgcn_sched_barrier(0);   // (left alone, the scheduler issues ids -> particles -> records: three dependent trips)
+    ClusterRecords rec;
+    rec.request(d, 0, cluster_tet_of_arguments(L, i, 0));
+    __builtin_amdgcn_sched_barrier(0);
     float4 ga = a_pos[va < 0 ? 0 : va], gb = a_pos[vb < 0 ? 0 : vb];
     [[maybe_unused]] float4 pa = make_float4(0.0f, 0.0f, 0.0f, 0.0f), pb = pa;
     if constexpr (kFold) {
@@ -853,42 +895,29 @@ __global__ __launch_bounds__(256) void TETSIM_SFX(nh_cluster4_kernel_)(const int
     }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (uint32_t j = 1; j < kNHClusterTets; j++) request(j);
+    for (uint32_t j = 1; j < kNHClusterTets; j++) rec.request(d, j, cluster_tet_of_arguments(L, i, j));
     __builtin_amdgcn_sched_barrier(0);
     if constexpr (kFold) {
         // the lane that loads a particle the cluster touches first finishes the previous substep and predicts this one for it (whole
         // particles, two per lane: the per-coordinate split starts behind this)
         if (fmask & (0x11u << c)) {
-            const VParams q = load_vparams_of(P, cluster_body(P, L.first[0] + i));
-            if ((fmask >> c) & 1u) fold_particle(d, q, static_cast<uint32_t>(va), ga, pa);
-            if ((fmask >> (c + 4u)) & 1u) fold_particle(d, q, static_cast<uint32_t>(vb), gb, pb);
+            const VParams vp = load_vparams_of(P, cluster_body(P, L.first[0] + i));
+            if ((fmask >> c) & 1u) fold_particle(d, vp, static_cast<uint32_t>(va), ga, pa);
+            if ((fmask >> (c + 4u)) & 1u) fold_particle(d, vp, static_cast<uint32_t>(vb), gb, pb);
         }
     }
     s_pos[c * 16u + cl] = ga;
     s_pos[(c + 4u) * 16u + cl] = gb;
-    float* const sp = reinterpret_cast<float*>(s_pos);   // one wave per LDS slice, LDS operations of a wave execute in order: no barrier
-#pragma unroll
-    for (uint32_t j = 0; j < kNHClusterTets; j++) {
-        if (j >= L.nsteps) break;            // (uniform)
-        if (i < L.count[j]) {                // (counts do not increase with j; whole quads agree)
-            const uint32_t a0 = ((cs[j] << 6) & 0x3fc0u) + lane, a1 = ((cs[j] >> 2) & 0x3fc0u) + lane,   // float index of (slot, cl, c) = slot * 64 + lane
-                           a2 = ((cs[j] >> 10) & 0x3fc0u) + lane, a3 = ((cs[j] >> 18) & 0x3fc0u) + lane;
-            float p[4] = {sp[a0], sp[a1], sp[a2], sp[a3]};   // lanes 0..2: a coordinate; lane 3: the inverse masses
-            const float im[4] = {quad<kQuadLane3>(p[0]), quad<kQuadLane3>(p[1]), quad<kQuadLane3>(p[2]), quad<kQuadLane3>(p[3])};
-            const float ir[9] = {ia[j].x, ia[j].y, ia[j].z, ia[j].w, ib[j].x, ib[j].y, ib[j].z, ib[j].w, ic[j].x};
-            const T ve = solve_quad(p, im, ir, static_cast<T>(ic[j].y), a_dev, a_vol, c_off);
-            if (c == 0u && d.vol_err) d.vol_err[ord[j]] = static_cast<double>(ve);
-            if (c < 3u) { sp[a0] = p[0]; sp[a1] = p[1]; sp[a2] = p[2]; sp[a3] = p[3]; }   // (lane 3 leaves the inverse masses alone)
-        }
-    }
+    solve_cluster_steps(q, L, rec, Q, d, true);
     if (va >= 0) { if constexpr (kWriteThrough) store_wt(d.pos, static_cast<uint32_t>(va), s_pos[c * 16u + cl]); else d.pos[va] = s_pos[c * 16u + cl]; }
     if (vb >= 0) { if constexpr (kWriteThrough) store_wt(d.pos, static_cast<uint32_t>(vb), s_pos[(c + 4u) * 16u + cl]); else d.pos[vb] = s_pos[(c + 4u) * 16u + cl]; }
 }
 
 #if TETSIM_FAST
 // ---- the clustered sweep as ONE launch: all colours in one grid, particles handed on with their stamp (dev_common.h: NHSweep) -------
-// nh_cluster4_kernel's cluster on four lanes, operation for operation -- the same solve_quad on the same inputs in the same order, so the
-// sweep equals the one-launch-per-colour sweep bit for bit -- with three differences around it:
+// nh_cluster4_kernel's cluster on four lanes, operation for operation -- the solves are solve_cluster_steps there and here, on the same
+// inputs, and the particle pass of a first toucher is fold_particle, so the sweep equals the one-launch-per-colour sweep bit for bit --
+// with three differences around it:
 //   * a wave finds its colour from its block index (scalar search over <= 255 colours) and reads that colour's descriptor;
 //   * a slot whose particle an EARLIER colour of this sweep touched is polled from the exchange array until it carries the stamp of that
 //     colour (memory-side loads: the writer may sit on another XCD, and no kernel boundary lies between the two); first touches come
@@ -896,23 +925,30 @@ __global__ __launch_bounds__(256) void TETSIM_SFX(nh_cluster4_kernel_)(const int
 //   * a slot's result goes to the exchange array with this colour's stamp -- or, when no later cluster touches the particle, to
 //     NHDev::pos with its inverse mass, where the particle kernels, the next substep's first touchers and the read-backs expect it.
 // Eight launch boundaries and ramps per substep become one.  Waits are bounded (timeout_ms; *error says so at the next tetsim_sync).
+// The colour of block `block` of a sweep: a uniform search over the colours' first blocks.
+__device__ __forceinline__ uint32_t find_colour(const NHSweepColour* __restrict__ cols, uint32_t ncol, uint32_t block) {
+    uint32_t k = 0;
+    while (k + 1u < ncol && block >= cols[k + 1u].first_block) k++;   // (uniform)
+    return k;
+}
+// A look at a handed-on particle: it is taken once it carries the stamp of the colour that wrote it.
+__device__ __forceinline__ void take_stamped(const float4& x, uint32_t want, float4& g, bool& pend) {
+    if (pend && __float_as_uint(x.w) == want) { g = x; pend = false; }
+}
 template <bool kFold>
 __global__ __launch_bounds__(256) void nh_sweep1_kernel(const NHSweepColour* __restrict__ cols, uint32_t ncol, float4* xch, uint32_t sub_index, uint32_t epoch_arg,
                                                         uint32_t* err, uint32_t timeout_ms, NHDev d) {
     __shared__ float4 s_all[4][kNHClusterVerts * 16];
-    float4* const s_pos = s_all[threadIdx.x >> 6];
-    uint32_t k = 0;
-    while (k + 1u < ncol && blockIdx.x >= cols[k + 1u].first_block) k++;   // (uniform)
+    const uint32_t k = find_colour(cols, ncol, blockIdx.x);
     const NHSweepColour& C = cols[k];
     const NHClusterLaunch& L = C.L;
-    const uint32_t lane = threadIdx.x & 63u, c = lane & 3u, cl = lane >> 2, i = ((blockIdx.x - C.first_block) * 4u + (threadIdx.x >> 6)) * 16u + cl;
+    const QuadLane q = quad_lane(s_all, blockIdx.x - C.first_block);
+    float4* const s_pos = q.s_pos;
+    const uint32_t c = q.c, cl = q.cl, i = q.i;
     const uint32_t clusters = L.clusters;
-    if (i >= clusters) return;   // (whole quads leave)
+    if (i >= clusters) return;
     const DevParams& P = *d.params;
-    const T dt = P.dt;
-    T devC = static_cast<T>(P.d_dev_compliance), volC = static_cast<T>(P.d_vol_compliance);
-    body_compliances(P, L.first[0] + i, devC, volC);
-    const T a_dev = devC / dt / dt, a_vol = volC / dt / dt, c_off = volC / devC;
+    const QuadScalars Q = quad_scalars(tet_scalars(P, L.first[0] + i));
     const uint32_t stamp = (epoch_arg ? epoch_arg : P.epoch) + sub_index * ncol + k + 1u;
     const int32_t va = L.slot_vid[static_cast<size_t>(c) * clusters + i], vb = L.slot_vid[static_cast<size_t>(c + 4u) * clusters + i];
     const float ima = C.slot_im[static_cast<size_t>(c) * clusters + i], imb = C.slot_im[static_cast<size_t>(c + 4u) * clusters + i];
@@ -920,16 +956,8 @@ __global__ __launch_bounds__(256) void nh_sweep1_kernel(const NHSweepColour* __r
     const uint32_t lmask = C.last_mask[i];
     [[maybe_unused]] uint32_t fmask = 0;
     if constexpr (kFold) fmask = L.first_mask[i];
-    uint32_t cs[kNHClusterTets];
-    float4 ia[kNHClusterTets], ib[kNHClusterTets], ic[kNHClusterTets];
-    int32_t ord[kNHClusterTets];
-    auto request = [&](uint32_t j) {
-        const uint32_t e = (j < L.nsteps && i < L.count[j]) ? L.first[j] + i : L.first[0] + i;
-        cs[j] = d.corner_slots[e];
-        ia[j] = d.irp_a[e]; ib[j] = d.irp_b[e]; ic[j] = d.irp_c[e];
-        ord[j] = d.order[e];
-    };
-    request(0);
+    ClusterRecords rec;
+    rec.request(d, 0, cluster_tet(L, i, 0));
     __builtin_amdgcn_sched_barrier(0);
     // slot c -> byte c of dl.x, slot c + 4 -> byte c of dl.y: 0 = first touch of the sweep
     const uint32_t da = (dl.x >> (8u * c)) & 0xffu, db = (dl.y >> (8u * c)) & 0xffu;
@@ -946,10 +974,10 @@ __global__ __launch_bounds__(256) void nh_sweep1_kernel(const NHSweepColour* __r
     }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (uint32_t j = 1; j < kNHClusterTets; j++) request(j);
+    for (uint32_t j = 1; j < kNHClusterTets; j++) rec.request(d, j, cluster_tet(L, i, j));
     __builtin_amdgcn_sched_barrier(0);
-    if (pend_a && __float_as_uint(xa.w) == want_a) { ga = xa; pend_a = false; }
-    if (pend_b && __float_as_uint(xb.w) == want_b) { gb = xb; pend_b = false; }
+    take_stamped(xa, want_a, ga, pend_a);
+    take_stamped(xb, want_b, gb, pend_b);
     if (__builtin_amdgcn_ballot_w64(pend_a || pend_b) != 0ull) {
         const long long t0 = wall_clock64(), limit = 100000ll * timeout_ms;   // 100 MHz ticks; 0 = unbounded
         do {
@@ -957,8 +985,8 @@ __global__ __launch_bounds__(256) void nh_sweep1_kernel(const NHSweepColour* __r
             // (other workgroups write the exchange array while this one looks: every look is a fresh load -- declared __restrict__, with no
             // store to it inside the loop, the first build's looks were folded into the one in front of the loop and waited for ever)
             asm volatile("" ::: "memory");
-            if (pend_a) { xa = load_coherent(xch, ua); if (__float_as_uint(xa.w) == want_a) { ga = xa; pend_a = false; } }
-            if (pend_b) { xb = load_coherent(xch, ub); if (__float_as_uint(xb.w) == want_b) { gb = xb; pend_b = false; } }
+            if (pend_a) take_stamped(load_coherent(xch, ua), want_a, ga, pend_a);
+            if (pend_b) take_stamped(load_coherent(xch, ub), want_b, gb, pend_b);
             if (limit && (pend_a || pend_b) && wall_clock64() - t0 > limit) {   // never in a correct run; a wedged GPU helps nobody
                 __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                 pend_a = pend_b = false;
@@ -967,29 +995,18 @@ __global__ __launch_bounds__(256) void nh_sweep1_kernel(const NHSweepColour* __r
     }
     if constexpr (kFold) {
         if (fmask & (0x11u << c)) {
-            const VParams q = load_vparams_of(P, cluster_body(P, L.first[0] + i));
-            if ((fmask >> c) & 1u) fold_particle<false>(d, q, ua, ga, pa);
-            if ((fmask >> (c + 4u)) & 1u) fold_particle<false>(d, q, ub, gb, pb);
+            const VParams vp = load_vparams_of(P, cluster_body(P, L.first[0] + i));
+            if ((fmask >> c) & 1u) fold_particle<false>(d, vp, ua, ga, pa);
+            if ((fmask >> (c + 4u)) & 1u) fold_particle<false>(d, vp, ub, gb, pb);
         }
     }
     ga.w = ima; gb.w = imb;   // the inverse masses (lane 3 of a quad reads them from the fourth float below)
     s_pos[c * 16u + cl] = ga;
     s_pos[(c + 4u) * 16u + cl] = gb;
-    float* const sp = reinterpret_cast<float*>(s_pos);
-#pragma unroll
-    for (uint32_t j = 0; j < kNHClusterTets; j++) {
-        if (j >= L.nsteps) break;            // (uniform)
-        if (i < L.count[j]) {
-            const uint32_t a0 = ((cs[j] << 6) & 0x3fc0u) + lane, a1 = ((cs[j] >> 2) & 0x3fc0u) + lane,   // float index of (slot, cl, c) = slot * 64 + lane
-                           a2 = ((cs[j] >> 10) & 0x3fc0u) + lane, a3 = ((cs[j] >> 18) & 0x3fc0u) + lane;
-            float p[4] = {sp[a0], sp[a1], sp[a2], sp[a3]};
-            const float im[4] = {quad<kQuadLane3>(p[0]), quad<kQuadLane3>(p[1]), quad<kQuadLane3>(p[2]), quad<kQuadLane3>(p[3])};
-            const float ir[9] = {ia[j].x, ia[j].y, ia[j].z, ia[j].w, ib[j].x, ib[j].y, ib[j].z, ib[j].w, ic[j].x};
-            const T ve = solve_quad(p, im, ir, static_cast<T>(ic[j].y), a_dev, a_vol, c_off);
-            if (c == 0u && d.vol_err) d.vol_err[ord[j]] = static_cast<double>(ve);
-            if (c < 3u) { sp[a0] = p[0]; sp[a1] = p[1]; sp[a2] = p[2]; sp[a3] = p[3]; }
-        }
-    }
+    solve_cluster_steps(q, L, rec, Q, d, true);
+    // A slot's result leaves the cluster: to NHDev::pos with its inverse mass where no later cluster of the sweep touches the particle, else
+    // to the exchange array with this colour's stamp in the fourth float.  (Not a function: behind one the compiler merges the two stores
+    // into one at a lane-dependent base, a loop over the bases present in the wave, and this kernel loses a wave.)
     if (va >= 0) {
         float4 r = s_pos[c * 16u + cl];
         if ((lmask >> c) & 1u) store_wt(d.pos, ua, r);
@@ -1008,20 +1025,21 @@ __global__ __launch_bounds__(256) void nh_sweep1_kernel(const NHSweepColour* __r
 // the first toucher does the particle pass between the two substeps as it takes the particle over (fold_particle's operations; the previous
 // position it needs was stored by itself one substep earlier, stamped, and is read past the caches), and only the call's last substep
 // stores to NHDev::pos and volError.  One launch boundary per CALL instead of per substep; colour 0 of a substep starts wherever the
-// clusters around it have finished the substep before.  Same arithmetic in the same order: bit-equal to the per-substep launches.
+// clusters around it have finished the substep before.  Same arithmetic in the same order: bit-equal to the per-substep launches.  (Every
+// step is written out here, not taken from the shared routines above: see the note in front of quad_lane.)
 __global__ __launch_bounds__(256) void nh_call_kernel(const NHSweepColour* __restrict__ cols, uint32_t ncol, float4* xch, uint32_t n_sub, uint32_t blocks_per_sub, uint32_t blocks,
                                                       uint32_t* err, uint32_t timeout_ms, NHDev d) {
     __shared__ float4 s_all[4][kNHClusterVerts * 16];
-    float4* const s_pos = s_all[threadIdx.x >> 6];
     const uint32_t sub = blockIdx.x / blocks_per_sub, r = blockIdx.x - sub * blocks_per_sub;
     if (r >= blocks) return;   // (padding: a substep's blocks are a multiple of 8)
     uint32_t k = 0;
     while (k + 1u < ncol && r >= cols[k + 1u].first_block) k++;   // (uniform)
     const NHSweepColour& C = cols[k];
     const NHClusterLaunch& L = C.L;
+    float4* const s_pos = s_all[threadIdx.x >> 6];
     const uint32_t lane = threadIdx.x & 63u, c = lane & 3u, cl = lane >> 2, i = ((r - C.first_block) * 4u + (threadIdx.x >> 6)) * 16u + cl;
     const uint32_t clusters = L.clusters;
-    if (i >= clusters) return;   // (whole quads leave)
+    if (i >= clusters) return;
     const DevParams& P = *d.params;
     const T dt = P.dt;
     T devC = static_cast<T>(P.d_dev_compliance), volC = static_cast<T>(P.d_vol_compliance);
@@ -1074,7 +1092,7 @@ __global__ __launch_bounds__(256) void nh_call_kernel(const NHSweepColour* __res
             if (pend_b) { xb = load_coherent(xch, ub); if (__float_as_uint(xb.w) == want_b) { gb = xb; pend_b = false; } }
             if (ppend_a) { pa = load_coherent(d.prev, ua); ppend_a = __float_as_uint(pa.w) != sub_base - ncol; }
             if (ppend_b) { pb = load_coherent(d.prev, ub); ppend_b = __float_as_uint(pb.w) != sub_base - ncol; }
-            if (limit && (pend_a || pend_b || ppend_a || ppend_b) && wall_clock64() - t0 > limit) {   // never in a correct run
+            if (limit && (pend_a || pend_b || ppend_a || ppend_b) && wall_clock64() - t0 > limit) {
                 __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                 pend_a = pend_b = ppend_a = ppend_b = false;
             }
@@ -1086,11 +1104,11 @@ __global__ __launch_bounds__(256) void nh_call_kernel(const NHSweepColour* __res
     // solves of colour 0 started ~1 us late (tools/nh_link_trace.py)
     float4 keep_a = pa, keep_b = pb;
     if (fold_a || fold_b) {
-        const VParams q = load_vparams_of(P, cluster_body(P, L.first[0] + i));
+        const VParams vp = load_vparams_of(P, cluster_body(P, L.first[0] + i));
         auto fold = [&](uint32_t v, float4& pos, const float4& prev_in, float4& prev) {
             float4 vel;
-            post_vertex<false>(q, v, pos, prev_in, vel);
-            predict_vertex(q, vel, pos, prev);
+            post_vertex<false>(vp, v, pos, prev_in, vel);
+            predict_vertex(vp, vel, pos, prev);
             prev.w = __uint_as_float(sub_base);
         };
         if (fold_a) fold(ua, ga, pa, keep_a);
@@ -1104,7 +1122,6 @@ __global__ __launch_bounds__(256) void nh_call_kernel(const NHSweepColour* __res
     for (uint32_t j = 0; j < kNHClusterTets; j++) {
         if (j >= L.nsteps) break;            // (uniform)
         if (i < L.count[j]) {
-            // float index of (slot, cl, c) = slot * 64 + lane: one field extraction and one add per corner
             const uint32_t a0 = ((cs[j] << 6) & 0x3fc0u) + lane, a1 = ((cs[j] >> 2) & 0x3fc0u) + lane,
                            a2 = ((cs[j] >> 10) & 0x3fc0u) + lane, a3 = ((cs[j] >> 18) & 0x3fc0u) + lane;
             float p[4] = {sp[a0], sp[a1], sp[a2], sp[a3]};
@@ -1115,6 +1132,7 @@ __global__ __launch_bounds__(256) void nh_call_kernel(const NHSweepColour* __res
             if (c < 3u) { sp[a0] = p[0]; sp[a1] = p[1]; sp[a2] = p[2]; sp[a3] = p[3]; }
         }
     }
+    // the hand-over of nh_sweep1_kernel, to NHDev::pos in the call's last substep only
     if (va >= 0) {
         float4 r = s_pos[c * 16u + cl];
         if (((lmask >> c) & 1u) && last_sub) store_wt(d.pos, ua, r);
@@ -1130,6 +1148,10 @@ __global__ __launch_bounds__(256) void nh_call_kernel(const NHSweepColour* __res
 }
 #endif
 
+// the instantiation of a kernel by a launch-time flag: either(wt, either(fold, k<true, true>, k<true, false>), ...)
+template <class K>
+K* either(bool flag, K* yes, K* no) { return flag ? yes : no; }
+
 }  // namespace
 
 #if TETSIM_FAST
@@ -1140,8 +1162,7 @@ void nh_launch_call_fast(hipStream_t s, const NHDev& d, const NHSweep& w, uint32
 }
 void nh_launch_sweep1_fast(hipStream_t s, const NHDev& d, const NHSweep& w, bool fold, uint32_t sub_index, uint32_t epoch) {
     if (w.blocks == 0) return;
-    if (fold) hipLaunchKernelGGL(nh_sweep1_kernel<true>, dim3(w.blocks), dim3(256), 0, s, w.colours, w.ncolours, w.exchange, sub_index, epoch, w.error, w.timeout_ms, d);
-    else hipLaunchKernelGGL(nh_sweep1_kernel<false>, dim3(w.blocks), dim3(256), 0, s, w.colours, w.ncolours, w.exchange, sub_index, epoch, w.error, w.timeout_ms, d);
+    hipLaunchKernelGGL(either(fold, nh_sweep1_kernel<true>, nh_sweep1_kernel<false>), dim3(w.blocks), dim3(256), 0, s, w.colours, w.ncolours, w.exchange, sub_index, epoch, w.error, w.timeout_ms, d);
 }
 #endif
 
@@ -1160,8 +1181,7 @@ void TETSIM_SFX(nh_launch_level_)(hipStream_t s, const NHDev& d, uint32_t first,
     const uint32_t block = count >= 262144u ? 256u : 64u;
     // write-through stores pay on big levels (1 M-tet lattice, 32 k tets per colour: 191 -> 163 us per substep) and cost 3-5% on
     // the Dragon's 120-tet levels, whose next level finds the lines in the same L2
-    if (count >= 4096u) hipLaunchKernelGGL(TETSIM_SFX(nh_level_kernel_)<true>, dim3((count + block - 1u) / block), dim3(block), 0, s, d, first, count);
-    else hipLaunchKernelGGL(TETSIM_SFX(nh_level_kernel_)<false>, dim3((count + block - 1u) / block), dim3(block), 0, s, d, first, count);
+    hipLaunchKernelGGL(either(count >= 4096u, TETSIM_SFX(nh_level_kernel_)<true>, TETSIM_SFX(nh_level_kernel_)<false>), dim3((count + block - 1u) / block), dim3(block), 0, s, d, first, count);
 }
 void TETSIM_SFX(nh_launch_level4_)(hipStream_t s, const NHDev& d, uint32_t first, uint32_t count) {
     if (count == 0) return;
@@ -1187,17 +1207,14 @@ void TETSIM_SFX(nh_launch_cluster_)(hipStream_t s, const NHDev& d, const NHClust
         const dim3 grid((L.clusters + 63u) / 64u), block(256);
         const float4* cpos = d.pos;
         const float4* cprev = d.prev;
-        if (wt && fold) hipLaunchKernelGGL((TETSIM_SFX(nh_cluster4_kernel_)<true, true>), grid, block, 0, s, L.slot_vid, cpos, L.first_mask, cprev, L.clusters, d, L);
-        else if (wt) hipLaunchKernelGGL((TETSIM_SFX(nh_cluster4_kernel_)<true, false>), grid, block, 0, s, L.slot_vid, cpos, L.first_mask, cprev, L.clusters, d, L);
-        else if (fold) hipLaunchKernelGGL((TETSIM_SFX(nh_cluster4_kernel_)<false, true>), grid, block, 0, s, L.slot_vid, cpos, L.first_mask, cprev, L.clusters, d, L);
-        else hipLaunchKernelGGL((TETSIM_SFX(nh_cluster4_kernel_)<false, false>), grid, block, 0, s, L.slot_vid, cpos, L.first_mask, cprev, L.clusters, d, L);
+        auto* kernel = either(wt, either(fold, TETSIM_SFX(nh_cluster4_kernel_)<true, true>, TETSIM_SFX(nh_cluster4_kernel_)<true, false>),
+                              either(fold, TETSIM_SFX(nh_cluster4_kernel_)<false, true>, TETSIM_SFX(nh_cluster4_kernel_)<false, false>));
+        hipLaunchKernelGGL(kernel, grid, block, 0, s, L.slot_vid, cpos, L.first_mask, cprev, L.clusters, d, L);
         return;
     }
-    const dim3 grid((L.clusters + 63u) / 64u), block(64);
-    if (wt && fold) hipLaunchKernelGGL((TETSIM_SFX(nh_cluster_kernel_)<true, true>), grid, block, 0, s, d, L);
-    else if (wt) hipLaunchKernelGGL((TETSIM_SFX(nh_cluster_kernel_)<true, false>), grid, block, 0, s, d, L);
-    else if (fold) hipLaunchKernelGGL((TETSIM_SFX(nh_cluster_kernel_)<false, true>), grid, block, 0, s, d, L);
-    else hipLaunchKernelGGL((TETSIM_SFX(nh_cluster_kernel_)<false, false>), grid, block, 0, s, d, L);
+    auto* kernel = either(wt, either(fold, TETSIM_SFX(nh_cluster_kernel_)<true, true>, TETSIM_SFX(nh_cluster_kernel_)<true, false>),
+                          either(fold, TETSIM_SFX(nh_cluster_kernel_)<false, true>, TETSIM_SFX(nh_cluster_kernel_)<false, false>));
+    hipLaunchKernelGGL(kernel, dim3((L.clusters + 63u) / 64u), dim3(64), 0, s, d, L);
 }
 uint32_t TETSIM_SFX(nh_frame_lds_limit_)() {
     // (a kernel may use all of a CU's LDS once it says so -- per device: asked for at every create, on the body's device)
