@@ -130,3 +130,110 @@ def test_colliders_apply_in_list_order_and_respect_the_mask():
     step = collide_f32(collide_f32(p, p, [a], 0.01), p, [s], 0.01)   # one pass each, in list order: the sphere acts last
     assert np.array_equal(got[0], step[0]) and np.array_equal(got[1], p[1])
     assert got[0][1] < 0.0 and np.linalg.norm(got[0].astype(np.float64) - [0.0, 0.1, 0.0]) >= 0.2 - 1e-6
+
+
+# ---- the high-precision reference (collide_exact) and the edge scene the GPU tests plant on a body (tests/test_gpu_collider_pass.py) ----
+
+def _oracle_state(case):
+    """the CPU oracle's stand-in for the device state of a case of test_gpu_collider_pass.py: (p0, prev, tets, live, colliders, planted, pp)"""
+    from oracle import OracleNH, OraclePJ
+    from test_gpu_collider_pass import CASES, WARM, _grab, mesh
+    from test_gpu_colliders import DT, GRAB_ID
+    name, kw, _, pp = CASES[case]
+    v, t = mesh(name)
+    live = np.zeros(len(v), bool)
+    live[np.unique(t)] = True
+    vv = v[:live.sum()] if not live.all() else v          # (the oracle divides 0 / 0 on a particle no tet references: it is the last one)
+    orc = OracleNH(vv, t, pp) if kw["solver"] == "neohookean" else OraclePJ(vv, t, pp)
+    orc.setGrab(*_grab(v))
+    for _ in range(WARM):
+        orc.simulate(DT, pp)
+    prev = np.array(orc.pos, np.float32)
+    orc.simulate(DT, pp)
+    p0 = np.array(orc.pos, np.float32)
+    if not live.all():
+        p0, prev = (np.concatenate([x, np.full((1, 3), np.nan, np.float32)]) for x in (p0, prev))
+    from collider_ref import edge_scene
+    cols, planted = edge_scene(p0, prev, t, DT, skip=[GRAB_ID] + np.nonzero(~live)[0].tolist())
+    return p0, prev, t, live, cols, planted, pp
+
+
+EDGE_CASES = ["quad-dragon", "fused-lat28", "call-loose", "nh-frame-dragon", "nh-clustered-delaunay400", "floor-quad-floor5"]
+
+
+@pytest.mark.parametrize("case", EDGE_CASES)
+def test_edge_scene_is_sized_by_the_reference_alone(case):
+    """On the oracle's positions (they agree with the device's to ~1e-4 m): >= 8 hit particles per entry, fragile particles <= 2 % of the
+    hit ones, every planted particle in the state its edge demands, the planted offsets exact -- in both list orders of the spheres."""
+    from collider_ref import EPS, collide_exact, f32_view, swapped
+    from test_gpu_collider_pass import capsule_regions, check_reference
+    from test_gpu_colliders import DT, GRAB_ID
+    p0, prev, t, live, cols, planted, pp = _oracle_state(case)
+    mask = live.copy()
+    mask[GRAB_ID] = False
+    assert len(cols) == capi.MAX_COLLIDERS
+    for c in cols:                                             # every value is an f32: rows and doubles are the same numbers
+        for k in ("a", "b", "radius", "friction", "velocity"):
+            x = np.asarray(c.get(k, 0.0), np.float64)
+            assert np.array_equal(x, x.astype(F32).astype(np.float64)), (c["kind"], k)
+    for order, cs in enumerate((cols, swapped(cols))):
+        pl = planted if order == 0 else {k: (i, {0: 1, 1: 0}.get(e, e), w) for k, (i, e, w) in planted.items()}
+        ex = collide_exact(p0, prev, cs, DT, mask)
+        plm, fragile = check_reference(ex, pl, live, cs)
+        assert min(capsule_regions(p0, cs[3], ex["hits"][:, 3])) > 0
+        print(case, order, "hits per entry", ex["hits"].sum(0), "fragile", int((fragile & ex["hits"].any(1)).sum()), "max r/L %.3g" % ex["cond"].max())
+    # the planted offsets are exact as real numbers: the same in f32, in f64 and under fused multiply-adds
+    V = f32_view(cols)
+    for what, (i, entry, push) in planted.items():
+        x, c = p0[i].astype(np.float64), V[entry]
+        if c["kind"] == 2:
+            l, g = x - c["a"], c["b"] - np.abs(x - c["a"])
+            assert np.array_equal(l.astype(F32).astype(np.float64), l)            # (axis-aligned: l is the subtraction)
+            j = int(np.argmax(np.abs(push)))
+            assert g[j] == g.min() == float(push[j]) and (l[j] > 0 or (l[j] == 0 and not np.signbit(l[j]))), (what, l, g)
+            ties = {"box tie two-way": 2, "box tie three-way": 3, "box zero": 1}[what]
+            assert (g == g.min()).sum() == ties and j == int(np.argmin(g)), (what, g)
+        elif c["kind"] == 3:
+            assert np.array_equal(p0[i], c["a"].astype(F32))
+        else:
+            assert np.array_equal(p0[i], c["a"].astype(F32)) or np.array_equal(p0[i], c["b"].astype(F32))
+            ab = c["b"] - c["a"]                                                  # a + (b - a) * 1 is b itself only if b - a is exact
+            assert np.array_equal(ab.astype(F32).astype(np.float64), ab), what
+    if case.startswith("floor"):
+        assert (p0[:, 1] == 0.0).sum() >= 4
+
+
+@pytest.mark.parametrize("case", ["quad-dragon", "nh-clustered-delaunay400"])
+def test_exact_reference_agrees_with_both_restatements_on_every_decision(case):
+    """hit / no hit and the chosen box face, entry by entry, on every particle that is not fragile; on the planted particles (decided by
+    an exact equality) as well; the positions within f32 rounding"""
+    from collider_ref import EPS, collide_exact, decisions
+    from test_gpu_colliders import DT, GRAB_ID
+    p0, prev, t, live, cols, planted, pp = _oracle_state(case)
+    mask = live.copy()
+    mask[GRAB_ID] = False
+    ex = collide_exact(p0, prev, cols, DT, mask)
+    firm = (ex["margin"] >= EPS) & live
+    firm[[i for i, _, _ in planted.values()]] = True
+    assert firm.sum() > 0.95 * live.sum()
+    for f in (collide_f32, collide_f64):
+        hits, face, sign = decisions(p0, prev, cols, DT, f, mask)
+        assert np.array_equal(hits[firm], ex["hits"][firm])
+        assert np.array_equal(face[firm], ex["face"][firm]) and np.array_equal(sign[firm], ex["sign"][firm])
+        got = f(p0, prev, cols, DT, mask).astype(np.float64)
+        assert np.abs(got[firm] - ex["pos"][firm]).max() < 16 * 2.0 ** -24 * np.abs(p0[live]).max() * max(1.0, ex["cond"].max())
+        for what, (i, entry, push) in planted.items():
+            want = p0[i] if push is None else (p0[i] + push).astype(F32)
+            assert np.array_equal(got[i].astype(F32), want), (what, f.__name__)
+    # the restatement of a generic scene too: a random cloud round the colliders of tests/test_gpu_colliders.py
+    from test_gpu_colliders import scene
+    rng = np.random.default_rng(3)
+    cloud = rng.uniform(-0.6, 0.6, (20000, 3)).astype(F32) + F32([0.0, -0.15, 0.0])
+    q = (cloud + rng.normal(0, 0.002, cloud.shape)).astype(F32)
+    cs = scene(np.array([[-0.5, 0.0, -0.5], [0.5, 1.0, 0.5]], F32))
+    ex = collide_exact(cloud, q, cs, DT)
+    firm = ex["margin"] >= EPS
+    assert firm.mean() > 0.99 and (ex["hits"].sum(0) > 50).all()
+    for f in (collide_f32, collide_f64):
+        hits, face, sign = decisions(cloud, q, cs, DT, f)
+        assert np.array_equal(hits[firm], ex["hits"][firm]) and np.array_equal(face[firm], ex["face"][firm])

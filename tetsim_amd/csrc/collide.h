@@ -68,7 +68,13 @@ __device__ __forceinline__ void collide_f32(float& px, float& py, float& pz, con
                 const float abx = C.b[0] - C.a[0], aby = C.b[1] - C.a[1], abz = C.b[2] - C.a[2];
                 const float ab2 = dot<kFast>(abx, aby, abz, abx, aby, abz);
                 float t = 0.0f;
-                if (ab2 != 0.0f) t = div<kFast>(dot<kFast>(px - C.a[0], py - C.a[1], pz - C.a[2], abx, aby, abz), ab2, rcp<kFast>(ab2));
+                if (ab2 != 0.0f) {
+                    const float num = dot<kFast>(px - C.a[0], py - C.a[1], pz - C.a[2], abx, aby, abz);
+                    t = div<kFast>(num, ab2, rcp<kFast>(ab2));
+                    // FAST: num * rcp(ab2) can fall an ulp short of 1 where num >= ab2 -- a particle exactly on b then stood an ulp off the
+                    // nearest point, L > 0, and was thrown out by r along rounding noise.  t >= 1 iff num >= ab2: decide it there.
+                    if constexpr (kFast) { if (num >= ab2) t = 1.0f; }
+                }
                 t = fminf(fmaxf(t, 0.0f), 1.0f);
                 cx = mad<kFast>(abx, t, C.a[0]); cy = mad<kFast>(aby, t, C.a[1]); cz = mad<kFast>(abz, t, C.a[2]);
             }
