@@ -498,7 +498,8 @@ int tetsim_set_colliders(tetsim_handle h, const TetSimCollider *colliders, uint3
  * Cost, measured on an MI355X (tools/body_grabs_cost.py, profiles/body_grabs_cost.txt): never switched on, the benchmark
  * line is inside the parent's run-to-run spread; 64 Dragons in one batch with every body held against none held, one call of 20
  * substeps: polar FAST x1.20, Neo-Hookean FAST x0.99-1.02.
- * Out of scope: more than one grab per body; per-body parameters; partitioned bodies; gradients; a Node binding. */
+ * Out of scope: more than one grab per body (that is the pin table, tetsim_set_body_pins below); per-body parameters; partitioned
+ * bodies; gradients; a Node binding. */
 
 /* particles [num_bodies] int32: index INSIDE the body (0 = the body's first particle), -1 = this body is not held.
  * targets [num_bodies] rows of 3 f32.  particles == NULL: body grabs OFF (targets ignored). */
@@ -517,6 +518,68 @@ int tetsim_set_body_grabs_device(tetsim_handle h, const void *particles, const v
  * bodies.  The ids it writes are directly the `particles` argument of tetsim_set_body_grabs_device. */
 int tetsim_nearest_particles_device(tetsim_handle h, const void *points, uint64_t point_stride,
                                     void *ids, void *dist2, void *caller_stream);
+
+/* --- body pins: many held particles per body of a batch, settable from device memory ------------- */
+
+/* A body-grab row holds ONE particle of a body.  The pin table holds up to per_body particles of EVERY body, each at a target of its
+ * own: a fixed base, a body hung from several points, a face clamped between gripper pads, boundary particles driven along a
+ * trajectory.  An ADDITIVE extension of ABI version 5 (TETSIM_ABI_VERSION is unchanged; no existing struct changed): look the
+ * symbols up.
+ *
+ * The table has num_bodies * per_body rows, body-major: row b * per_body + k is (particles[row], target xyz) -- a particle index
+ * INSIDE body b, -1 = unused, and 3 f32.  While pins are ON, every particle a valid row names is treated in every substep, on every
+ * stepping path, exactly as the particle named by tetsim_set_grab is treated on that path: POLAR_JACOBI sets it to its target before
+ * the clamp, NEOHOOKEAN_GS after clamp and floor, the colliders skip it.  Nothing else about a substep changes.  THE CONTRACT: with
+ * per_body = 1 a body gives the bits it gives with its body-grab row, and so those it gives alone with tetsim_set_grab; a body whose
+ * every particle is pinned sits on its targets after every call, bit for bit.  A handle that never switches pins on executes what it
+ * always executed: pins are a second mode of the body grabs' one uniform branch per particle pass, tested only behind it.
+ *
+ * NORMALISATION, the same for both variants and for tetsim_prep_pin_slots, in this order: (1) a row whose index is outside
+ * [0, particles of body b) is "none"; (2) a row with a non-finite target component is "none"; (3) if two valid rows of one body
+ * name the same particle, the LOWEST row wins and the later ones are ignored.  The device kernels apply all three silently and
+ * disturb no other body.  The host variant refuses (1) -- other than -1 -- and (2) with TETSIM_EINVAL and leaves the previous
+ * table in force; duplicates it accepts and resolves by (3).
+ *
+ * The table lives in device memory owned by the handle: an int32 per particle (the row that holds it, -1 = free) and 16 bytes per
+ * row; it counts into device_bytes.  The first set call allocates it and may block.  A call with ANOTHER per_body than the table
+ * has makes the rows anew: it waits for the handle's stream, may block, and empties every body's rows first -- a body that its
+ * body_mask leaves out then holds nothing.  Every other set call only enqueues: on the handle's stream it clears the slots of the
+ * bodies it takes, scatters the rows' indices with an integer atomicMin (the lowest row wins: two calls give the same bits; no
+ * floating-point atomics) and writes the normalised rows; every substep enqueued afterwards sees them.  Switching OFF
+ * (particles == NULL) is host state; it also empties the table.  The table is not solver state: checkpoints and snapshots do not
+ * hold it, their sizes do not change, and a restore does not touch it.
+ *
+ * One kind of hold at a time: with pins ON, tetsim_set_grab(id >= 0), tetsim_start_grab, tetsim_start_grab_ray and switching body
+ * grabs on return TETSIM_ESTATE (tetsim_set_grab(-1) stays legal); switching pins ON while a handle grab or body grabs are set is
+ * TETSIM_ESTATE.  Also TETSIM_ESTATE: any partitioned body; a handle with TETSIM_FLAG_REF_GRAB_TEXEL.  TETSIM_EINVAL: a NULL
+ * handle; NULL targets with non-NULL particles; per_body == 0 or per_body * num_bodies >= 2^31; and, for the device variant, a
+ * stride that is neither 0 nor a multiple of 4 of at least 12; a pointer that is not 4-byte aligned, that hipPointerGetAttributes
+ * does not place on the handle's device, or whose rows do not fit its allocation.  Every error is found before anything is
+ * enqueued.
+ * Cost, measured on an MI355X (tools/body_pins_cost.py, profiles/body_pins_cost.txt): never switched on, the benchmark
+ * line is 34.04-34.15 G tet-solves/s against the parent's 33.88-34.12 in alternating runs -- no run below the parent's lowest, one
+ * above its highest.  64 Dragons in one batch with 1 / 16 / 256 pins per body against none held, one call of 20 substeps: polar FAST
+ * x1.20 / x1.22 / x1.16, Neo-Hookean FAST x0.99 / x1.01 / x1.01.  A body of the persistent 256-tet frame kernel (a single medium
+ * body; TetSimInfo::fused_particle_pass == 2) leaves that kernel while pins are on and steps through its fused kernels, with the same
+ * bits: a 28-cell lattice x1.68, whatever the number of pins.  The four-lane frame kernel of small bodies and the one-launch calls
+ * keep their kernels.
+ * Out of scope: pins on partitioned bodies; per-pin stiffness or springs (a pin is a hard hold); attachments between two bodies;
+ * gradients; a Node binding. */
+
+/* particles [num_bodies * per_body] int32, body-major: index INSIDE the body, -1 = unused row.  targets: a row of 3 f32 per row of
+ * particles, packed.  particles == NULL: pins OFF (targets and per_body ignored). */
+int tetsim_set_body_pins(tetsim_handle h, const int32_t *particles, const float *targets, uint32_t per_body);
+/* The same from DEVICE memory: particles packed int32, targets rows of xyz f32 at targets + row * target_stride (0 = packed 12;
+ * else a multiple of 4, >= 12); body_mask, the stream contract and the pointer checks are those of tetsim_set_body_grabs_device
+ * (a body the mask leaves out keeps all its rows). */
+int tetsim_set_body_pins_device(tetsim_handle h, const void *particles, const void *targets, uint64_t target_stride,
+                                uint32_t per_body, const void *body_mask, void *caller_stream);
+/* The normalisation above on the host, without a device: body_particles [num_bodies] particles of every body; slot_out
+ * [sum of body_particles], in body order: for every particle the row (b * per_body + k) that holds it, -1 = free.  What the
+ * device setter leaves in its slots, particle for particle.  TETSIM_EINVAL: a NULL argument, per_body == 0, per_body * num_bodies
+ * >= 2^31. */
+int tetsim_prep_pin_slots(const int32_t *particles, const float *targets, uint32_t num_bodies, uint32_t per_body,
+                          const uint32_t *body_particles /*[num_bodies]*/, int32_t *slot_out /*[sum body_particles], -1 = free*/);
 
 /* --- body colliders: up to eight colliders per body of a batch, settable from device memory ------ */
 

@@ -171,6 +171,7 @@ SYMBOLS = [
     "tetsim_closest_visual_device", "tetsim_closest_visual",
     "tetsim_tet_strain_device", "tetsim_read_tet_strain", "tetsim_body_strain_device", "tetsim_visual_strain_device", "tetsim_prep_strain_table",
     "tetsim_set_body_grabs", "tetsim_set_body_grabs_device", "tetsim_nearest_particles_device",
+    "tetsim_set_body_pins", "tetsim_set_body_pins_device", "tetsim_prep_pin_slots",
     "tetsim_set_body_colliders", "tetsim_set_body_colliders_device",
     "tetsim_set_body_params", "tetsim_set_body_params_device",
     "tetsim_place_bodies_device", "tetsim_place_bodies",
@@ -185,6 +186,7 @@ OPTIONAL_SYMBOLS = ("tetsim_set_colliders", "tetsim_raycast_visual", "tetsim_sta
                     "tetsim_raycast_visual_device", "tetsim_visual_bounding_spheres_device",
                     "tetsim_tet_strain_device", "tetsim_read_tet_strain", "tetsim_body_strain_device", "tetsim_visual_strain_device", "tetsim_prep_strain_table",
                     "tetsim_set_body_grabs", "tetsim_set_body_grabs_device", "tetsim_nearest_particles_device",
+                    "tetsim_set_body_pins", "tetsim_set_body_pins_device", "tetsim_prep_pin_slots",
                     "tetsim_set_body_colliders", "tetsim_set_body_colliders_device",
                     "tetsim_set_body_params", "tetsim_set_body_params_device",
                     "tetsim_place_bodies_device", "tetsim_place_bodies",
@@ -296,6 +298,10 @@ def lib():
         L.tetsim_set_body_grabs.argtypes = [H, ip, fp]
         L.tetsim_set_body_grabs_device.argtypes = [H, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.tetsim_nearest_particles_device.argtypes = [H, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(L, "tetsim_set_body_pins"):   # (additive to ABI 5; device arrays, the mask and the stream travel as plain addresses)
+        L.tetsim_set_body_pins.argtypes = [H, ip, fp, u32]
+        L.tetsim_set_body_pins_device.argtypes = [H, C.c_void_p, C.c_void_p, C.c_uint64, u32, C.c_void_p, C.c_void_p]
+        L.tetsim_prep_pin_slots.argtypes = [ip, fp, u32, u32, C.POINTER(u32), ip]
     if hasattr(L, "tetsim_set_body_colliders"):   # (additive to ABI 5; device rows, the mask and the stream travel as plain addresses)
         L.tetsim_set_body_colliders.argtypes = [H, fp, u32]
         L.tetsim_set_body_colliders_device.argtypes = [H, C.c_void_p, C.c_uint64, u32, C.c_void_p, C.c_void_p]

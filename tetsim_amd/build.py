@@ -47,6 +47,8 @@ UNITS = {
     "touch.hip": ["-ffp-contract=off"],
     # the nearest query's f64 squared distance is tetsim_nearest_particle's, compared bit for bit: every multiply and add rounded on its own
     "body_grabs.hip": ["-ffp-contract=off"],
+    # integer work only (slots, an unsigned minimum, rows copied by their bits); it includes body_rows.h, whose units are all built this way
+    "body_pins.hip": ["-ffp-contract=off"],
     # the set kernel normalises plane normals and box axes in f64 exactly as tetsim_set_colliders does on the host: every operation rounded on its own
     "body_colliders.hip": ["-ffp-contract=off"],
     # a row is validated and rounded to f32 by one routine compiled for both sides: nothing for the compiler to contract, and it stays that way

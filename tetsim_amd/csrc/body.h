@@ -262,6 +262,15 @@ struct tetsim_body {
     bool body_grabs_on = false;
     uint32_t* d_grab_body = nullptr;    // [particles]; made by whichever of body grabs and body colliders is set first (ensure_particle_bodies)
     int4* d_grab_rows = nullptr;        // [bodies]
+    // body pins (tetsim_set_body_pins / _device, body_pins.hip): any number of held particles per body.  Per particle in device order the
+    // row that holds it (-1 = free) and pin_per_body rows of the same 16 bytes per body; the slots are made by the first set call and keep
+    // their address, the rows are made anew when per_body changes.  ON / OFF is host state and travels as DevParams::body_grabs ==
+    // kHoldBodyPins, with the rows' address in DevParams::grab_rows.  Not solver state either.
+    bool body_pins_on = false;
+    int32_t* d_pin_slot = nullptr;      // [particles]
+    int4* d_pin_rows = nullptr;         // [bodies * pin_per_body]
+    size_t pin_rows_cap = 0;
+    uint32_t pin_per_body = 0;
     // body colliders (tetsim_set_body_colliders / _device, body_colliders.hip): per body a count and kMaxColliders compacted entries, in the
     // view this handle's arithmetic reads (f32: polar, FAST Neo-Hookean; f64: PRECISE Neo-Hookean -- the other pointer stays null).  Made by
     // the first set call, every body empty; ON / OFF is host state and travels as DevParams::body_colliders.  Not solver state either.
@@ -613,6 +622,7 @@ bool record_stride_ok(uint64_t stride, uint64_t row_bytes, uint32_t align);
 int check_device_records(tetsim_body* h, const void* ptr, uint64_t stride, uint32_t rows, uint64_t row_bytes, uint32_t align, const std::string& what);
 extern const char* const kPartitionedIo;           // the refusal of a partitioned body, one text for every device-side call
 extern const char* const kBodyGrabsOn;             // the refusal of the handle's grab while body grabs are on (body_grabs.hip)
+extern const char* const kBodyPinsOn;              // the refusal of the handle's grab and of body grabs while body pins are on (body_pins.hip)
 extern const char* const kBodyCollidersOn;         // the refusal of a non-empty handle list while body colliders are on (body_colliders.hip)
 // what the per-body tables start from (body_grabs.hip; the first call of each may block)
 uint32_t num_bodies(const tetsim_body* h);

@@ -142,6 +142,7 @@ int check_grab_state(tetsim_body* h) {
     if (h->partitioned || !h->group.empty()) return fail(h, TETSIM_ESTATE, "body grabs on a partitioned body are not supported (tetsim_set_grab on each partition)");
     if (h->opt.flags & TETSIM_FLAG_REF_GRAB_TEXEL) return fail(h, TETSIM_ESTATE, "body grabs on a TETSIM_FLAG_REF_GRAB_TEXEL handle are not supported (its quirk picks other particles, in host arithmetic)");
     if (h->grab_global >= 0) return fail(h, TETSIM_ESTATE, "a handle grab is set (tetsim_set_grab): one kind of grab at a time -- release it first (id -1)");
+    if (h->body_pins_on) return fail(h, TETSIM_ESTATE, kBodyPinsOn);
     return 0;
 }
 

@@ -37,7 +37,7 @@ static_assert(sizeof(BodyParamsF) == 48 && sizeof(BodyParamsD) == 80, "body para
 struct DevParams {
     // f32 view -- POLAR_JACOBI: the reference uploads these as f32 uniforms (SoftbodyGPU.js:614-637)
     float dt, gravity, friction;
-    uint32_t body_grabs;   // non-zero: the body-grab table below decides which particles are held, grab / grab_local are not looked at (tetsim_set_body_grabs)
+    uint32_t body_grabs;   // non-zero: a table below decides which particles are held, grab / grab_local are not looked at -- 1 (kHoldBodyGrabs): the body-grab table (tetsim_set_body_grabs), 2 (kHoldBodyPins): the pin table (tetsim_set_body_pins)
     float lo[3];
     uint32_t body_colliders;   // non-zero: a particle meets the rows of ITS body in the table below (tetsim_set_body_colliders); n_colliders is 0 then
     float hi[3];
@@ -67,6 +67,10 @@ struct DevParams {
     const BodyParamsF* bp_f;
     const BodyParamsD* bp_d;
     const uint32_t* tet_body;
+    // body pins (body_pins.hip): per particle in DEVICE particle order the row of the pin table that holds it, -1 = free.  While pins are
+    // on (body_grabs == kHoldBodyPins) grab_rows above is the pin table -- rows of the same 16 bytes, any number per body.  Null until the
+    // handle's first set call; its address never changes.  (Behind the older fields: they keep their offsets.)
+    const int32_t* pin_slot;
     // kinematic colliders (collide.h): entries [0, n_colliders) are meaningful, in both views.  Behind every field above, so that a
     // body without colliders reads what it always read at the offsets it always read it from.
     DevColliderF col[kMaxColliders];     // f32 view: polar solver, FAST Neo-Hookean
@@ -94,9 +98,26 @@ __device__ __forceinline__ void store_params(DevParams* dst, const DevParams& v)
 // selection: the particle passes that are inlined into several kernels and held to bit-equality get no arithmetic from here, and a handle
 // that never switches body grabs on executes what it always executed plus the branch.  v must be a particle of the body (the tile
 // kernels' idle lanes carry a valid id too).
+// Body pins (tetsim_set_body_pins) are the second mode of the same branch: the particle's own slot names its row of the pin table, and a
+// handle that never switches them on never reaches the test of the mode.
+constexpr uint32_t kHoldBodyGrabs = 1u, kHoldBodyPins = 2u;
+// the row that may hold particle v -- only behind the uniform test of DevParams::body_grabs; the particle is held if the row names it
+__device__ __forceinline__ int4 body_hold_row(uint32_t mode, const uint32_t* grab_body, const int4* grab_rows, const int32_t* pin_slot, uint32_t v) {
+    // (two paths, not one load through an index array chosen by the mode: with the one load nh_call_kernel and nh_sweep1_kernel held
+    // two registers more and lost a wave of occupancy)
+    if (mode == kHoldBodyPins) {   // (uniform)
+        const int32_t slot = pin_slot[v];
+        return slot >= 0 ? grab_rows[slot] : make_int4(-1, 0, 0, 0);
+    }
+    return grab_rows[grab_body[v]];
+}
+// kPins = false: compiled without the pin mode.  The polar frame kernels of pj_blocked.hip are: with it they held 170 registers for 168
+// and two waves per SIMD for three, so a body of theirs steps through the fused kernels while pins are on (tetsim_api.hip: frame_now),
+// which agree with them bit for bit.
+template <bool kPins = true>
 __device__ __forceinline__ void body_grab_pick(const DevParams& P, uint32_t v, bool& held, float& x, float& y, float& z) {
     if (P.body_grabs) {
-        const int4 row = P.grab_rows[P.grab_body[v]];
+        const int4 row = kPins ? body_hold_row(P.body_grabs, P.grab_body, P.grab_rows, P.pin_slot, v) : P.grab_rows[P.grab_body[v]];
         held = row.x == static_cast<int32_t>(v);
         if (held) { x = __int_as_float(row.y); y = __int_as_float(row.z); z = __int_as_float(row.w); }
     }

@@ -230,7 +230,7 @@ struct VParams {
     T dt, gravity, friction, lo[3], hi[3];
     int32_t grab_local;
     float grab[3];
-    uint32_t body_grabs;           // non-zero: the body's row decides (tetsim_set_body_grabs), grab_local / grab are not looked at
+    uint32_t body_grabs;           // non-zero: a table's row decides (tetsim_set_body_grabs, tetsim_set_body_pins: dev_common.h), grab_local / grab are not looked at
     const uint32_t* grab_body;     // the table's two addresses as values; post_vertex reads a particle's row before anything is stored
     const int4* grab_rows;
     const DevParams* all;   // the colliders (collide.h)
@@ -347,8 +347,12 @@ __device__ __forceinline__ void post_vertex(const VParams& P, uint32_t v, float4
     bool grabbed = static_cast<int32_t>(v) == P.grab_local;
     if (grabbed) { pos.x = P.grab[0]; pos.y = P.grab[1]; pos.z = P.grab[2]; }
     if (P.body_grabs) {   // body grabs (tetsim_set_body_grabs): behind one uniform branch the row of the particle's body decides -- the handle's
-                          // grab names nobody then; the row is read through the VALUES of its addresses, before this particle's stores
-        const int4 row = P.grab_rows[P.grab_body[v]];
+                          // grab names nobody then; the row is read through the VALUES of its addresses, before this particle's stores.
+                          // Body pins (tetsim_set_body_pins) are the branch's second mode.  Only that mode reads the slots' address, and through
+                          // P.all, not as a fourth value of VParams: as a value it cost nh_call_kernel and nh_sweep1_kernel two registers each
+                          // (169 and 170 for 167 and 168) and with them a wave per SIMD, for every handle.  So with pins ON the cluster kernels'
+                          // write-back loop re-reads that one scalar behind each write-through store, as any_colliders(*P.all) does below
+        const int4 row = body_hold_row(P.body_grabs, P.grab_body, P.grab_rows, P.all->pin_slot, v);
         grabbed = row.x == static_cast<int32_t>(v);
         if (grabbed) { pos.x = __int_as_float(row.y); pos.y = __int_as_float(row.z); pos.z = __int_as_float(row.w); }
     }

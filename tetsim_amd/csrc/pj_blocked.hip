@@ -75,14 +75,15 @@ struct VertexOut { f3 p, vel, pred; };
 // kUniformBody: every lane of the wave carries a particle of ONE body (a tile's own particles) -- a body's row of parameters
 // (tetsim_set_body_params) then arrives through scalar loads; the particle kernels' waves span bodies and load per lane.
 // kTable = false: compiled without the table (the caller has tested DevParams::body_params itself and found it off).
-template <bool kUniformBody, bool kTable = true>
+// kPins = false: compiled without body pins (dev_common.h: body_grab_pick) -- the frame kernels, whose bodies leave them while pins are on.
+template <bool kUniformBody, bool kTable = true, bool kPins = true>
 __device__ __forceinline__ VertexOut pjb_vertex_update(f3 acc, float wsum, f3 prev, const DevParams& P, uint32_t v) {
     const float rw = __builtin_amdgcn_rcpf(wsum);
     f3 p = F3(acc.x * rw, acc.y * rw, acc.z * rw);  // 0 * inf = NaN for a particle without tets, as in the reference
     // P6, SoftbodyGPU.js:340-355
     bool grabbed = static_cast<int32_t>(v) == P.grab_local || static_cast<int32_t>(v) == P.grab_local2;
     if (grabbed) p = F3(P.grab[0], P.grab[1], P.grab[2]);
-    body_grab_pick(P, v, grabbed, p.x, p.y, p.z);   // (body grabs, dev_common.h: a selection behind one uniform branch, no arithmetic)
+    body_grab_pick<kPins>(P, v, grabbed, p.x, p.y, p.z);   // (body grabs and pins, dev_common.h: a selection behind one uniform branch, no arithmetic)
     PolarBodyParams B = {P.gravity, P.friction, {P.lo[0], P.lo[1], P.lo[2]}, {P.hi[0], P.hi[1], P.hi[2]}};
     if constexpr (kTable) B = body_params_polar<kUniformBody>(P, v);   // (body parameters, dev_common.h: the call's values or the body's row)
     p.x = fminf(fmaxf(p.x, B.lo[0]), B.hi[0]);
@@ -617,7 +618,7 @@ __device__ __forceinline__ void pjb_frame_body(const PJBlk& d, const DevParams& 
                 acc.x += gj.x; acc.y += gj.y; acc.z += gj.z;
             }
         }
-        return pjb_vertex_update<true>(acc, wsum, prev, P, vid);
+        return pjb_vertex_update<true, true, false>(acc, wsum, prev, P, vid);
     };
 
     for (uint32_t s = 0; s < n; s++) {

@@ -150,7 +150,8 @@ __device__ __forceinline__ void pjq_solve(float cur[4], float rest[4], QRot& q, 
 // ---- P5's division + P6 + P7 (+ P1, P2 of the next substep) for one component of one particle ---------------------------------
 struct QParams { float dt, rdt, fr, g_dt, lo, hi, grab; int32_t grab0, grab1; uint32_t body_grabs; const DevParams* all; };   // all: the colliders
 // vid: the lane's particle, the same for the whole call -- with body grabs on (tetsim_set_body_grabs) its body's row is read here, once, and
-// `grab` says it all: the target's component if the particle is held (always finite: body_grabs.hip), NaN if it is not.  (No register
+// `grab` says it all: the target's component if the particle is held (always finite: body_grabs.hip), NaN if it is not.  Body pins
+// (tetsim_set_body_pins) likewise: the particle's slot and its row of the pin table, once, into the same value.  (No register
 // beyond those the handle's grab needs: the frame kernel has none to spare.)
 __device__ __forceinline__ QParams load_qparams(const DevParams& P, uint32_t c, uint32_t vid) {
     QParams o;
@@ -167,7 +168,7 @@ __device__ __forceinline__ QParams load_qparams(const DevParams& P, uint32_t c, 
     o.grab0 = P.grab_local; o.grab1 = P.grab_local2;
     o.body_grabs = P.body_grabs;
     if (P.body_grabs) {   // (uniform)
-        const int4 row = P.grab_rows[P.grab_body[vid]];
+        const int4 row = body_hold_row(P.body_grabs, P.grab_body, P.grab_rows, P.pin_slot, vid);
         o.grab = row.x == static_cast<int32_t>(vid) ? __int_as_float(c == 0u ? row.y : c == 1u ? row.z : row.w) : __uint_as_float(0x7fc00000u);
     }
     o.all = &P;

@@ -90,9 +90,13 @@ void fill_params(const tetsim_body* h, double dt, const TetSimParams& p, DevPara
     }
     // body grabs (body_grabs.hip): the switch is host state and goes through push_params' comparison like any parameter; the table's
     // addresses are null until the handle's first set call and constant from then on
-    o->body_grabs = h->body_grabs_on ? 1u : 0u;
+    o->body_grabs = h->body_grabs_on ? kHoldBodyGrabs : 0u;
     o->grab_body = h->d_grab_body;
     o->grab_rows = h->d_grab_rows;
+    // body pins (body_pins.hip): the same switch's second mode (the two are never on together); the pin table then stands where the
+    // body-grab table stood.  A table made anew for another per_body changes that address, and with it what push_params compares
+    if (h->body_pins_on) { o->body_grabs = kHoldBodyPins; o->grab_rows = h->d_pin_rows; }
+    o->pin_slot = h->d_pin_slot;
     // body colliders (body_colliders.hip): likewise -- the switch, and the table's addresses (grab_body is shared with the body grabs)
     o->body_colliders = h->body_colliders_on ? 1u : 0u;
     o->bcol_count = h->d_bcol_count;
@@ -703,7 +707,9 @@ int tetsim_get_info(tetsim_handle h, TetSimInfo* info) {
 // The persistent frame kernel serves this call -- not while a quad body has body colliders on: pjq_frame_kernel has no register for a second
 // kind of list (pj_quad.hip: pjq_vertex_update), the body then takes the two launches per substep that tetsim_profile and the fall-back
 // take, which agree with the frame kernel bit for bit.
-static bool frame_now(const tetsim_body* h) { return h->frame && !(h->quad && h->body_colliders_on); }
+// Nor while a body of the 256-tet tiles has body pins on: pjb_frame_kernel is compiled without them (with them it lost a wave of occupancy:
+// dev_common.h, body_grab_pick), the body then steps through the fused kernels, which agree with the frame kernel bit for bit.
+static bool frame_now(const tetsim_body* h) { return h->frame && !(h->quad && h->body_colliders_on) && !(!h->quad && h->body_pins_on); }
 // Likewise the Neo-Hookean calls that are one launch: nh_frame_kernel, nh_sweep1_kernel and nh_call_kernel keep the parent's particle pass
 // (with the second list they lose a wave of occupancy or gain a stack: nh_kernels.inc, post_vertex), so while body colliders are on the
 // body steps through the level / cluster kernels and the particle kernels, which take the table and agree with them bit for bit.

@@ -242,6 +242,28 @@ int tetsim_prep_ref_grab_texels(int32_t grab_id, uint32_t num_elems, uint32_t nu
     ref_grab_texels(grab_id, num_elems, num_particles, out);
     return 0;
 }
+// The pin table's normalisation (include/tetsim.h: tetsim_set_body_pins), the host's statement of what body_pins.hip's kernels do: rows in
+// ascending order, so the first valid row to name a particle keeps it -- the integer minimum the device takes.
+int tetsim_prep_pin_slots(const int32_t* particles, const float* targets, uint32_t num_bodies, uint32_t per_body, const uint32_t* body_particles, int32_t* slot_out) {
+    if (!particles || !targets || !body_particles || !slot_out || per_body == 0u) return TETSIM_EINVAL;
+    if (static_cast<uint64_t>(per_body) * num_bodies >= 0x80000000ull) return TETSIM_EINVAL;
+    size_t first = 0;
+    for (uint32_t b = 0; b < num_bodies; b++) {
+        const uint32_t n = body_particles[b];
+        int32_t* const slot = slot_out + first;
+        for (uint32_t i = 0; i < n; i++) slot[i] = -1;
+        for (uint32_t k = 0; k < per_body; k++) {
+            const size_t row = static_cast<size_t>(b) * per_body + k;
+            const int32_t p = particles[row];
+            const float* const t = targets + 3u * row;
+            if (p < 0 || static_cast<uint32_t>(p) >= n) continue;
+            if (!finite_value(t[0]) || !finite_value(t[1]) || !finite_value(t[2])) continue;
+            if (slot[p] < 0) slot[p] = static_cast<int32_t>(row);
+        }
+        first += n;
+    }
+    return 0;
+}
 int tetsim_prep_boundary_surface(const float* verts, const int32_t* tets, uint32_t nt, uint32_t nv, float* vis_verts, int32_t* tri_ids,
                                  uint32_t* nrows, uint32_t* ntri) {
     if ((nt && !tets) || !nrows || !ntri || (!vis_verts != !tri_ids)) return fail(nullptr, TETSIM_EINVAL, "tetsim_prep_boundary_surface: null argument");

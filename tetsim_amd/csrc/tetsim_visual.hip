@@ -242,6 +242,7 @@ int tetsim_set_grab(tetsim_handle h, int32_t id, const float xyz[3]) {
     if (!h) return TETSIM_EINVAL;
     if (id >= static_cast<int32_t>(h->info.num_particles)) return fail(h, TETSIM_EINVAL, "grab id out of range");
     if (id >= 0 && h->body_grabs_on) return fail(h, TETSIM_ESTATE, kBodyGrabsOn);   // (releasing the handle's grab, id < 0, stays legal)
+    if (id >= 0 && h->body_pins_on) return fail(h, TETSIM_ESTATE, kBodyPinsOn);
     h->grab_global = id < 0 ? -1 : id;
     ref_grab_texels(h->grab_global, h->info.num_elems, h->info.num_particles, h->grab_ref);
     if (xyz) std::memcpy(h->grab_pos, xyz, 3 * sizeof(float));
@@ -308,6 +309,7 @@ int nearest_owned(tetsim_body* h, const float xyz[3], int32_t* local, double* be
 int tetsim_start_grab(tetsim_handle h, const float xyz[3], int32_t* id_out) {
     if (!h || !xyz) return fail(h, TETSIM_EINVAL, "null argument");
     if (h->body_grabs_on) return fail(h, TETSIM_ESTATE, kBodyGrabsOn);
+    if (h->body_pins_on) return fail(h, TETSIM_ESTATE, kBodyPinsOn);
     if (h->partitioned) return fail(h, TETSIM_ESTATE, "start_grab on a partitioned body: combine tetsim_nearest_particle over the partitions on the host, then tetsim_set_grab on each");
     int32_t id = -1;
     double best = 0.0;
@@ -458,6 +460,7 @@ int tetsim_raycast_visual(tetsim_handle h, const TetSimRay* rays, uint32_t count
 int tetsim_start_grab_ray(tetsim_handle h, const TetSimRay* ray, TetSimRayHit* hit_out, int32_t* id_out) {
     if (!h || !ray) return fail(h, TETSIM_EINVAL, "null argument");
     if (h->body_grabs_on) return fail(h, TETSIM_ESTATE, kBodyGrabsOn);
+    if (h->body_pins_on) return fail(h, TETSIM_ESTATE, kBodyPinsOn);
     if (int rc = check_query_state(h, true)) return rc;
     TetSimRayHit hit;
     if (int rc = cast_rays(h, ray, 1, &hit)) return rc;

@@ -156,6 +156,21 @@ def place_rows(q, pivot=(0.0, 0.0, 0.0), offset=(0.0, 0.0, 0.0), linear=(0.0, 0.
     return rows
 
 
+def prep_pin_slots(particles, targets, body_particles):
+    """The pin table's normalisation on the host (include/tetsim.h: tetsim_prep_pin_slots): particles int [B, K] (index inside the body,
+    -1 = unused), targets float [B, K, 3], body_particles [B] particles of every body.  Returns int32 [sum(body_particles)]: for every
+    particle, in body order, the row b * K + k that holds it, -1 = free -- a row outside its body or with a non-finite target holds
+    nothing, the lowest row wins a particle that several name."""
+    p = np.ascontiguousarray(particles, dtype=np.int32)
+    t = _f32(targets)
+    n = np.ascontiguousarray(body_particles, dtype=np.uint32).reshape(-1)
+    if p.ndim != 2 or p.shape[0] != len(n) or p.shape[1] < 1 or t.shape != p.shape + (3,):
+        raise ValueError("particles must be [%d, per_body >= 1] and targets [%d, per_body, 3]" % (len(n), len(n)))
+    out = np.empty(int(n.sum(dtype=np.uint64)), dtype=np.int32)
+    capi.check(capi.lib().tetsim_prep_pin_slots(_ip(p.reshape(-1)), _fp(t.reshape(-1)), len(n), p.shape[1], n.ctypes.data_as(C.POINTER(C.c_uint32)), _ip(out)))
+    return out
+
+
 def boundary_surface(tets, nv, verts=None):
     """(visVerts [rows, 4], visTriIds [triangles, 3]) of the tet mesh's boundary, oriented outward, in the reference's visual-mesh
     format -- for bodies without an artist's mesh (include/tetsim.h: tetsim_prep_boundary_surface).  Host only, no GPU needed.
@@ -973,6 +988,47 @@ class SoftBodyHIP:
                 raise ValueError("particles must be a contiguous int32 tensor on %s of shape (%d,)" % (dev, n))
             _check_rows(torch, targets, dev, n, 3, "targets")
             return self._L.tetsim_set_body_grabs_device(self._h, particles.data_ptr(), targets.data_ptr(), 4 * targets.stride(0) if n > 1 else 0, mask, s)
+        self._masked_call(bodies, stream, call)
+
+    # -- body pins (include/tetsim.h: tetsim_set_body_pins / _device) -------------------------------------------------------
+    def setBodyPins(self, particles, targets):
+        """Hold up to K particles of every body: particles int32 [num_bodies, K], indices INSIDE the body (-1 = unused row), targets
+        float32 [num_bodies, K, 3].  Every particle a row names is held at its target exactly as setGrab holds its particle; if two
+        rows of a body name one particle the lowest row wins.  None, None switches pins off.  Raises TetSimError(EINVAL) for an index
+        outside its body or a non-finite target (the previous table stays in force), TetSimError(ESTATE) while a handle grab or body
+        grabs are set.  A call with another K than the last one makes the table anew and may block."""
+        if particles is None:
+            capi.check(self._L.tetsim_set_body_pins(self._h, None, None, 0), self._h)
+            return
+        n = self.info.num_bodies
+        p = np.ascontiguousarray(particles, dtype=np.int32)
+        t = _f32(targets)
+        if p.ndim != 2 or p.shape[0] != n or t.shape != p.shape + (3,):
+            raise ValueError("particles must be [%d, per_body] and targets [%d, per_body, 3]" % (n, n))
+        capi.check(self._L.tetsim_set_body_pins(self._h, _ip(p.reshape(-1)), _fp(t.reshape(-1)), p.shape[1]), self._h)
+
+    def setBodyPinsDevice(self, particles, targets, bodies=None, stream=None):
+        """setBodyPins from device tensors, with no host copy and no synchronisation (a call with another K than the last one makes the
+        table anew and may block): particles torch.int32 [num_bodies, K] (contiguous), targets torch.float32 [num_bodies, K, 3] -- or the
+        [..., :3] view of a [num_bodies, K, 4] tensor: rows evenly spaced, the stride is passed through -- both on the handle's device
+        and produced on `stream` (as in exportTensors; reusable on it right after the call).  bodies: a mask as in restore -- a body it
+        leaves out keeps all its rows.  A row the table cannot hold (an index outside its body, a non-finite target) holds nothing and
+        disturbs no other row."""
+        n = self.info.num_bodies
+
+        def call(torch, dev, mask, s):
+            if (not isinstance(particles, torch.Tensor) or particles.dtype != torch.int32 or particles.device != dev or particles.dim() != 2
+                    or particles.shape[0] != n or particles.shape[1] < 1 or not particles.is_contiguous()):
+                raise ValueError("particles must be a contiguous int32 tensor on %s of shape (%d, per_body >= 1)" % (dev, n))
+            k = int(particles.shape[1])
+            ok = (isinstance(targets, torch.Tensor) and targets.dtype == torch.float32 and targets.device == dev and tuple(targets.shape) == (n, k, 3)
+                  and targets.stride(2) == 1)
+            if ok:
+                step = targets.stride(1) if k > 1 else (targets.stride(0) if n > 1 else 3)
+                ok = step >= 3 and (n == 1 or k == 1 or targets.stride(0) == k * step)
+            if not ok:
+                raise ValueError("targets must be a float32 tensor on %s of shape (%d, %d, 3) with a contiguous last dimension and evenly spaced rows" % (dev, n, k))
+            return self._L.tetsim_set_body_pins_device(self._h, particles.data_ptr(), targets.data_ptr(), 4 * step if n * k > 1 else 0, k, mask, s)
         self._masked_call(bodies, stream, call)
 
     # -- body colliders (include/tetsim.h: tetsim_set_body_colliders / _device) ---------------------------------------------
