@@ -227,6 +227,31 @@ def test_the_blocks_of_sequence_numbers_wrap():
         b.close()
 
 
+@pytest.mark.parametrize("which", ["lattice3-quad", "dragon-256"])
+def test_a_call_of_more_than_32768_substeps_is_cut_into_launches(which):
+    """A persistent frame launch numbers its substeps inside one block of 65,536 stamps, so tetsim_step_n cuts a longer call into launches
+    of 32,768 substeps (tetsim_api.hip: most_substeps_per_launch).  One call of 32,768 + 5 substeps equals a twin stepped by calls of
+    32,768 and 5, and a second twin stepped by 20,000 and 12,773 -- launches on either side of the cut -- bit for bit in positions,
+    velocities and quaternions, and no wait gives up.  A 3-cell lattice on the four-lane frame kernel (pjq_frame_kernel) and the Dragon on
+    the 256-tet one (pjb_frame_kernel), both resting on the floor for most of the call."""
+    if which == "lattice3-quad":
+        (v, t), kw, path = make_lattice(3, y0=0.02), dict(), 3
+    else:
+        (v, t), kw, path = load_mesh("dragon"), dict(constant_rest_shape=True), 2
+        v = v - np.float32([0.0, v[:, 1].min() - 0.01, 0.0])
+    a, b, c = (SoftBodyHIP(v, t, None, dict(PP), solver="polar", precision="fast", **kw) for _ in range(3))
+    assert [x.info.fused_particle_pass for x in (a, b, c)] == [path] * 3
+    for body, calls in ((a, (32768 + 5,)), (b, (32768, 5)), (c, (20000, 12773))):
+        for n in calls:
+            body.simulateSubsteps(n, DT, PP)
+    for body in (a, b, c):
+        body.sync()                              # (raises if a tile waited in vain)
+    for other in (b, c):
+        assert _same(a.pos, other.pos) and _same(a.vel, other.vel) and _same(a.quats, other.quats), which
+    assert np.isfinite(a.pos).all() and a.pos[:, 1].min() < 0.01     # on the floor: contact and friction were exercised
+    assert all(x.info.fused_particle_pass == path for x in (a, b, c))
+
+
 def _wheel(spokes):
     """`spokes` tets around a common axis (particles 0 and 1): both axis particles have valence `spokes`."""
     ang = np.linspace(0.0, 2.0 * np.pi, spokes, endpoint=False)

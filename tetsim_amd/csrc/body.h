@@ -1,6 +1,7 @@
 // body.h -- the handle behind tetsim_handle and the helpers the translation units of the C ABI share.
 //
-//   tetsim_api.hip     lifecycle, stepping (streams / graphs)
+//   tetsim_api.hip     lifecycle, stepping (streams / graphs); behind the handle below: which one-launch path serves a call (frame_now,
+//                      nh_frame_now, nh_one_now) and the launchers of the handle's arithmetic mode (pj_launchers, nh_launchers)
 //   tetsim_state.hip   the state's host entry points: reads (copying: on the host; pinned: through the gather), tetsim_write_state,
 //                      checkpoint and resume, plan getters; state_sections(), the table of self-describing sections that IS the complete state
 //   tetsim_visual.hip  embedded visual mesh (its set-up and its host reads), grab (pin, nearest-particle query), picking
@@ -318,7 +319,7 @@ struct tetsim_body {
     float4 *rest0_a = nullptr, *rest0_b = nullptr, *rest0_c = nullptr;
     bool quat_stale = false;          // substeps have been enqueued since pj.quat was last recovered
     // persistent frame kernel (pjb_frame_kernel): tetsim_step_n runs ONE launch per call; fused bodies of few enough tiles
-    bool frame = false;
+    bool frame = false;               // (whether it serves the call at hand: frame_now, behind this struct)
     uint32_t frame_epoch = 1;         // sequence number of the next call's first substep (DevParams::epoch), advanced by 65536 per parameter push
     uint32_t fold_wave_limit = 0, fold_tile_limit = 0;   // waves / workgroups that may wait in-kernel on this device (pjb_wait_capacity, at creation)
     bool quad = false;                // SMALL body: 64-tet tiles, one tet / one particle on four lanes (pj_quad.hip) -- tetsim_step runs pjq_tet + pjq_vertex,
@@ -439,14 +440,14 @@ struct tetsim_body {
     uint32_t nh_untouched = 0;
     // clustered FAST bodies: the sweep as ONE launch per substep, particles handed on with their stamp (dev_common.h: NHSweep);
     // TETSIM_NH_ONE_LAUNCH=0 at creation keeps one launch per colour (A/B); tetsim_profile always does (it times the colour kernels)
-    bool nh_one_launch = false;
+    bool nh_one_launch = false;       // (whether it serves the call at hand: nh_one_now, behind this struct)
     bool nh_call = false;             // ... and tetsim_step_n runs the sweeps of ALL its substeps as one launch (nh_call_kernel: every particle touched by some cluster, <= 127 colours)
     NHSweep nh_sweep1;
     uint32_t nh_sub_index = 0;        // substep inside the run being enqueued (enqueue_substep: first -> 0)
     uint32_t nh_epoch_arg = 0;        // tetsim_step: a block of stamps of its own as a kernel argument; 0 = DevParams::epoch (tetsim_step_n)
     std::vector<uint32_t> level_off;
     // small bodies (all particles fit one CU's LDS, level schedules): tetsim_step_n runs a call as ONE single-workgroup launch
-    bool nh_frame = false;
+    bool nh_frame = false;            // (whether it serves the call at hand: nh_frame_now, behind this struct)
     NHFrameLaunch nh_frame_launch;
     std::vector<uint32_t> nh_seg;      // host copy of nh_frame_launch.seg ([levels][bodies][2]): the stepwise FAST twin makes the frame kernel's choice per piece
     std::vector<int32_t> order;
@@ -454,6 +455,23 @@ struct tetsim_body {
 };
 
 namespace tetsim {
+
+// ---- whether a one-launch flag of the handle (frame, nh_frame, nh_one_launch above) serves the call at hand: the flag says what the body
+// was built for, a per-body switch may take it off that path for as long as it is on.  Every stepping decision asks these, never the pair.
+// The persistent frame kernel serves this call -- not while a quad body has body colliders on: pjq_frame_kernel has no register for a second
+// kind of list (pj_quad.hip: pjq_vertex_update), the body then takes the two launches per substep that tetsim_profile and the fall-back
+// take, which agree with the frame kernel bit for bit.
+// Nor while a body of the 256-tet tiles has body pins on: pjb_frame_kernel is compiled without them (with them it lost a wave of occupancy:
+// dev_common.h, body_grab_pick), the body then steps through the fused kernels, which agree with the frame kernel bit for bit.
+inline bool frame_now(const tetsim_body* h) { return h->frame && !(h->quad && h->body_colliders_on) && !(!h->quad && h->body_pins_on); }
+// Likewise the Neo-Hookean calls that are one launch: nh_frame_kernel, nh_sweep1_kernel and nh_call_kernel keep the parent's particle pass
+// (with the second list they lose a wave of occupancy or gain a stack: nh_kernels.inc, post_vertex), so while body colliders are on the
+// body steps through the level / cluster kernels and the particle kernels, which take the table and agree with them bit for bit.
+inline bool nh_frame_now(const tetsim_body* h) { return h->nh_frame && !h->body_colliders_on; }
+inline bool nh_one_now(const tetsim_body* h) { return h->nh_one_launch && !h->body_colliders_on; }
+// ---- the launchers of the handle's arithmetic mode (dev_common.h: one table per solver, an instance per mode)
+inline const PJLaunchers& pj_launchers(const tetsim_body* h) { return h->fast ? pj_launchers_fast : pj_launchers_precise; }
+inline const NHLaunchers& nh_launchers(const tetsim_body* h) { return h->fast ? nh_launchers_fast : nh_launchers_precise; }
 
 // ---- the bodies of a handle (here alone: batch_first_* are empty for a single body).  is_batch: made by tetsim_create_batch, of however many bodies
 inline bool is_batch(const tetsim_body* h) { return !h->batch_first_vert.empty(); }

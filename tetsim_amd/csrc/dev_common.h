@@ -112,7 +112,7 @@ __device__ __forceinline__ int4 body_hold_row(uint32_t mode, const uint32_t* gra
     return grab_rows[grab_body[v]];
 }
 // kPins = false: compiled without the pin mode.  The polar frame kernels of pj_blocked.hip are: with it they held 170 registers for 168
-// and two waves per SIMD for three, so a body of theirs steps through the fused kernels while pins are on (tetsim_api.hip: frame_now),
+// and two waves per SIMD for three, so a body of theirs steps through the fused kernels while pins are on (body.h: frame_now),
 // which agree with them bit for bit.
 template <bool kPins = true>
 __device__ __forceinline__ void body_grab_pick(const DevParams& P, uint32_t v, bool& held, float& x, float& y, float& z) {
@@ -315,22 +315,18 @@ void nh_launch_sweep1_fast(hipStream_t s, const NHDev& d, const NHSweep& w, bool
 // the prediction kernel, behind it the kernel that ends the call; stamps start at DevParams::epoch
 void nh_launch_call_fast(hipStream_t s, const NHDev& d, const NHSweep& w, uint32_t n);
 
-// launchers (one set per arithmetic mode; defined in pj_precise.hip / pj_fast.hip / nh_*.hip)
-// e0/e1 (optional): HIP events that timestamp the kernel's own begin and end (hipExtLaunchKernelGGL), for
-// tetsim_profile; normal launches pass none.
-void pj_launch_tet_precise(hipStream_t s, const PJDev& d, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
-void pj_launch_tet_fast(hipStream_t s, const PJDev& d, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
-void pj_launch_vertex_precise(hipStream_t s, const PJDev& d, uint32_t first, uint32_t count, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
-void pj_launch_vertex_fast(hipStream_t s, const PJDev& d, uint32_t first, uint32_t count, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
-void pj_launch_repredict_precise(hipStream_t s, const PJDev& d);
-void pj_launch_repredict_fast(hipStream_t s, const PJDev& d);
+// The launchers that exist in both arithmetic modes: per solver one table of them, and an instance per mode at the end of pj_kernels.inc /
+// nh_kernels.inc (pj_precise.hip / pj_fast.hip / nh_precise.hip / nh_fast.hip).  body.h picks the instance by tetsim_body::fast: pj_launchers(h),
+// nh_launchers(h).  Launchers that exist in FAST only (nh_launch_sweep1_fast, nh_launch_call_fast, pjb_*, pjq_*) are free functions.
+struct PJLaunchers {
+    // e0/e1 (may be null): HIP events that timestamp the kernel's own begin and end (hipExtLaunchKernelGGL), for
+    // tetsim_profile; normal launches pass none.
+    void (*tet)(hipStream_t s, const PJDev& d, hipEvent_t e0, hipEvent_t e1);
+    void (*vertex)(hipStream_t s, const PJDev& d, uint32_t first, uint32_t count, hipEvent_t e0, hipEvent_t e1);
+    void (*repredict)(hipStream_t s, const PJDev& d);
+};
+extern const PJLaunchers pj_launchers_precise, pj_launchers_fast;
 
-void nh_launch_post_predict_precise(hipStream_t s, const NHDev& d);
-void nh_launch_post_predict_fast(hipStream_t s, const NHDev& d);
-// fold: this sweep's first touchers do the particle pass between the previous substep and this one (L.first_mask)
-void nh_launch_cluster_precise(hipStream_t s, const NHDev& d, const NHClusterLaunch& L, bool fold = false);
-void nh_launch_cluster_fast(hipStream_t s, const NHDev& d, const NHClusterLaunch& L, bool fold = false);
-// the same pass for the particles no cluster touches (list of particle ids), when the sweeps fold the rest
 // small bodies: a whole call as ONE workgroup per body with every particle of the body in LDS (nh_kernels.inc: nh_frame_kernel)
 struct NHFrameLaunch {
     const uint32_t* seg = nullptr;         // [levels][bodies][2]: per level and body, first and end solve position of the body's tets (8-byte aligned pairs)
@@ -338,17 +334,25 @@ struct NHFrameLaunch {
     uint32_t levels = 0, bodies = 0, block = 512;   // threads per workgroup, <= 512
     uint32_t max_body_particles = 0;       // x 40 bytes of LDS per workgroup
 };
-void nh_launch_frame_precise(hipStream_t s, const NHDev& d, const NHFrameLaunch& f, uint32_t n, const DevParams& params, DevParams* params_dev);   // (parameters by value: pjb_launch_frame)
-void nh_launch_frame_fast(hipStream_t s, const NHDev& d, const NHFrameLaunch& f, uint32_t n, const DevParams& params, DevParams* params_dev);
 // levels of at most this many tets are solved on four lanes per tet by the single-workgroup launch of small bodies (and, FAST, by its
 // stepwise twin): 128 quads = two waves per SIMD in f32; f64 (PRECISE) runs at half rate, one wave per SIMD
 constexpr uint32_t kNHQuadLevelFast = 128, kNHQuadLevelPrecise = 64;
-void nh_launch_level4_fast(hipStream_t s, const NHDev& d, uint32_t first, uint32_t count);   // one tet per quad: FAST stepwise twin of the frame kernel's sweep; small levels
-void nh_launch_level4_precise(hipStream_t s, const NHDev& d, uint32_t first, uint32_t count);
-uint32_t nh_frame_lds_limit_precise();
-uint32_t nh_frame_lds_limit_fast();
-void nh_launch_post_predict_list_precise(hipStream_t s, const NHDev& d, const uint32_t* list, uint32_t n);
-void nh_launch_post_predict_list_fast(hipStream_t s, const NHDev& d, const uint32_t* list, uint32_t n);
+struct NHLaunchers {
+    void (*predict)(hipStream_t s, const NHDev& d);
+    void (*predict_value)(hipStream_t s, const NHDev& d, const DevParams& params, DevParams* params_dev);   // (the prediction that brings a call's parameters along)
+    void (*level)(hipStream_t s, const NHDev& d, uint32_t first, uint32_t count);
+    void (*level4)(hipStream_t s, const NHDev& d, uint32_t first, uint32_t count);   // one tet per quad: FAST stepwise twin of the frame kernel's sweep; small levels
+    // fold: this sweep's first touchers do the particle pass between the previous substep and this one (L.first_mask)
+    void (*cluster)(hipStream_t s, const NHDev& d, const NHClusterLaunch& L, bool fold);
+    void (*post)(hipStream_t s, const NHDev& d);
+    void (*post_predict)(hipStream_t s, const NHDev& d);
+    // the same pass for the particles no cluster touches (list of particle ids), when the sweeps fold the rest
+    void (*post_predict_list)(hipStream_t s, const NHDev& d, const uint32_t* list, uint32_t n);
+    void (*frame)(hipStream_t s, const NHDev& d, const NHFrameLaunch& f, uint32_t n, const DevParams& params, DevParams* params_dev);   // (parameters by value: pjb_launch_frame)
+    uint32_t (*frame_lds_limit)();
+};
+extern const NHLaunchers nh_launchers_precise, nh_launchers_fast;
+
 // raise_word != nullptr: the kernel sets that hand-over word (PJSync::flag) as it STARTS, i.e. "everything in front of this kernel
 // in its queue is done" -- a signal kernel folded into its successor
 // clear_word != nullptr: ... and puts that word back to 0 first (a word whose waiters were the waves of the kernel in front: pjb_launch_vertex_await)
@@ -431,15 +435,6 @@ void pjb_launch_tet_alt(hipStream_t s, const PJBlk& d, uint32_t tile_first, uint
 void pjb_launch_signal(hipStream_t s, const PJSync& y, uint32_t* clear_word = nullptr);   // one wave: [clear another word,] set
 // the particle kernel whose every wave awaits y.flag itself, without clearing it (the queue's next kernel does: clear_word above)
 void pjb_launch_vertex_await(hipStream_t s, const PJBlk& d, uint32_t first, uint32_t count, const PJSync& y, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
-
-void nh_launch_predict_precise(hipStream_t s, const NHDev& d);
-void nh_launch_predict_fast(hipStream_t s, const NHDev& d);
-void nh_launch_predict_value_precise(hipStream_t s, const NHDev& d, const DevParams& params, DevParams* params_dev);   // (the prediction that brings a call's parameters along)
-void nh_launch_predict_value_fast(hipStream_t s, const NHDev& d, const DevParams& params, DevParams* params_dev);
-void nh_launch_level_precise(hipStream_t s, const NHDev& d, uint32_t first, uint32_t count);
-void nh_launch_level_fast(hipStream_t s, const NHDev& d, uint32_t first, uint32_t count);
-void nh_launch_post_precise(hipStream_t s, const NHDev& d);
-void nh_launch_post_fast(hipStream_t s, const NHDev& d);
 
 // embedded visual mesh skinning (skin_kernels.hip)
 struct SkinDev {

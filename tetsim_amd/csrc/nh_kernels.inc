@@ -327,7 +327,7 @@ __device__ __forceinline__ T js_min(T a, T b) {
 // bounds / floor friction / grab / velocity, Softbody.js:213-239: (pos, prev) in, (pos, vel) out
 // kBodyColliders: the pass also serves body colliders (tetsim_set_body_colliders).  The stepwise kernels do; the one-launch kernels
 // (nh_frame_kernel, nh_sweep1_kernel, nh_call_kernel) do not -- with the second list they lose a wave of occupancy or gain a stack -- so
-// a body steps through the stepwise kernels while body colliders are on (tetsim_api.hip: nh_frame_now, nh_one_now); they agree bit for bit.
+// a body steps through the stepwise kernels while body colliders are on (body.h: nh_frame_now, nh_one_now); they agree bit for bit.
 template <bool kBodyColliders = true>
 __device__ __forceinline__ void post_vertex(const VParams& P, uint32_t v, float4& pos, const float4& prev, float4& vel) {
     const T dt = P.dt, friction = P.friction;
@@ -1242,5 +1242,11 @@ void TETSIM_SFX(nh_launch_post_predict_)(hipStream_t s, const NHDev& d) {
     if (d.nv == 0) return;
     hipLaunchKernelGGL(TETSIM_SFX(nh_post_predict_kernel_), dim3((d.nv + 255u) / 256u), dim3(256), 0, s, d);
 }
+// this mode's instance of the launcher table (dev_common.h); host pass only: a const object would be emitted for the device too, where no launcher exists
+#if !defined(__HIP_DEVICE_COMPILE__)
+const NHLaunchers TETSIM_SFX(nh_launchers_) = {
+    TETSIM_SFX(nh_launch_predict_), TETSIM_SFX(nh_launch_predict_value_), TETSIM_SFX(nh_launch_level_), TETSIM_SFX(nh_launch_level4_), TETSIM_SFX(nh_launch_cluster_),
+    TETSIM_SFX(nh_launch_post_), TETSIM_SFX(nh_launch_post_predict_), TETSIM_SFX(nh_launch_post_predict_list_), TETSIM_SFX(nh_launch_frame_), TETSIM_SFX(nh_frame_lds_limit_)};
+#endif
 
 }  // namespace tetsim

@@ -160,5 +160,9 @@ void TETSIM_SFX(pj_launch_repredict_)(hipStream_t s, const PJDev& d) {
     if (d.nv_owned == 0) return;
     hipLaunchKernelGGL(TETSIM_SFX(pj_repredict_kernel_), dim3((d.nv_owned + 255u) / 256u), dim3(256), 0, s, d);
 }
+// this mode's instance of the launcher table (dev_common.h); host pass only: a const object would be emitted for the device too, where no launcher exists
+#if !defined(__HIP_DEVICE_COMPILE__)
+const PJLaunchers TETSIM_SFX(pj_launchers_) = {TETSIM_SFX(pj_launch_tet_), TETSIM_SFX(pj_launch_vertex_), TETSIM_SFX(pj_launch_repredict_)};
+#endif
 
 }  // namespace tetsim

@@ -177,7 +177,7 @@ __device__ __forceinline__ QParams load_qparams(const DevParams& P, uint32_t c, 
 struct QVertex { float p, vel, pred; };
 // kBodyColliders: the pass also serves body colliders (tetsim_set_body_colliders).  The two-launch substep does; the persistent frame kernel
 // does not -- its 128 registers hold the parent's code and not one value more (with the second list it spilled) -- so a quad body steps
-// through the two launches while body colliders are on (tetsim_api.hip: frame_now); the three agree bit for bit, as ever.
+// through the two launches while body colliders are on (body.h: frame_now); the three agree bit for bit, as ever.
 template <bool kBodyColliders>
 __device__ __forceinline__ QVertex pjq_vertex_update(float acc, float wsum, float prev, const QParams& P, uint32_t vid, uint32_t c) {
     float p = acc * __builtin_amdgcn_rcpf(wsum);   // 0 * inf = NaN for a particle without tets, as in the reference

@@ -1,6 +1,10 @@
 // tetsim_api.hip -- C ABI of libtetsim_hip.so, part 1 (include/tetsim.h): handle lifecycle and stepping (stream / graph
 // orchestration of the gfx950 kernels).  State read-back: tetsim_state.hip; visual mesh and grab: tetsim_visual.hip;
 // measurement: tetsim_measure.hip.  See body.h for all translation units.
+// Every stepping call: open_call (checks, device, what a step makes stale) and take_params (a block of stamps, the host's record) behind
+// push_params / stage_params; the path by frame_now / nh_frame_now / nh_one_now (body.h), top to bottom in tetsim_step and tetsim_step_n;
+// long calls cut by most_substeps_per_launch; kernel-by-kernel stepping through enqueue_substeps; the mode's kernels through pj_launchers /
+// nh_launchers (body.h).  tetsim_sync: wait_gave_up for the three one-launch error words, drop_graphs behind it and behind tetsim_destroy.
 #include <mutex>
 
 #include "body_rows.h"
@@ -135,6 +139,7 @@ void fill_params(const tetsim_body* h, double dt, const TetSimParams& p, DevPara
 //     which can have any stamp's bits: none of them runs between the call's prediction and its sweep.
 // Stamps restart at every body's creation, so none may travel in a checkpoint: tetsim_save_state and tetsim_load_state write 0 in
 // the sections that state_sections() marks `stamped` (tetsim_state.hip) -- pos_pred.w, pos_final.w and Neo-Hookean prev.w; a snapshot likewise.
+constexpr uint32_t kStampBlock = 65536u;
 int next_epoch_block(tetsim_body* h) {
     if (h->frame_epoch >= 0xfffe0000u) {
         if (h->partial_b && h->partial_slots) {
@@ -144,19 +149,37 @@ int next_epoch_block(tetsim_body* h) {
         if (h->nh_one_launch) HIPCHK(h, hipMemsetAsync(h->nh_sweep1.exchange, 0, static_cast<size_t>(h->nh.nv) * sizeof(float4), h->stream));
         h->frame_epoch = 1u;
     }
-    h->frame_epoch += 65536u;
+    h->frame_epoch += kStampBlock;
     return 0;
 }
 
 constexpr uint32_t kDirectLaunchTets = 150000u;   // from here on a body's substeps are launched kernel by kernel instead of replayed from a graph (tetsim_step_n)
 
-// The parameters of this call into DevParams, in stream order.
-int push_params(tetsim_body* h, double dt, const TetSimParams* params, bool reuse_ok) {
+// What a stepping call opens with, however its parameters travel (push_params, stage_params): the checks, the handle's device, and what
+// a step makes stale.
+int open_call(tetsim_body* h, double dt, const TetSimParams* params) {
     if (!params) return fail(h, TETSIM_EINVAL, "params is null");
     if (!(dt > 0.0) || !std::isfinite(dt)) return fail(h, TETSIM_EINVAL, "dt must be a positive finite number");
     HIPCHK(h, hipSetDevice(h->opt.device));  // group stepping walks over handles that may live on different devices
     h->final_ghosts_fresh = false;           // (every stepping path comes through here: the ghosts' end-of-substep positions fetched for the visual mesh are stale)
     h->quat_stale = true;                    // (... and a lean-state body's quaternion array: ensure_quats)
+    return 0;
+}
+// ... and what it takes for its launches: a fresh block of sequence numbers and the host's record of what the device holds once the upload
+// (push_params) or the launch that brings the parameters along (stage_params) has run.
+// block_fresh: the caller's own launch may use this block instead of taking another (epoch_block_fresh)
+int take_params(tetsim_body* h, double dt, const TetSimParams* params, bool block_fresh) {
+    if (int rc = next_epoch_block(h)) return rc;
+    h->epoch_block_fresh = block_fresh;
+    fill_params(h, dt, *params, &h->params_on_device);
+    h->params_known = true;
+    h->fork_needed = true;  // whatever the caller did on the main stream since the last call must be visible to the boundary stream
+    return 0;
+}
+
+// The parameters of this call into DevParams, in stream order.
+int push_params(tetsim_body* h, double dt, const TetSimParams* params, bool reuse_ok) {
+    if (int rc = open_call(h, dt, params)) return rc;
     if (reuse_ok && h->params_known && !h->comm_stream && !h->partitioned) {   // (a halo queue keeps a copy of its own: always refreshed)
         // A host that keeps the reference's loop (main.js:79-84: simulate(dt, physicsParams) per substep) sends the same numbers again
         // and again: the copy and its event were most of what such a call cost (22.5 -> 7.8 us per tetsim_step on the Dragon,
@@ -166,11 +189,9 @@ int push_params(tetsim_body* h, double dt, const TetSimParams* params, bool reus
         now.epoch = h->params_on_device.epoch;
         if (std::memcmp(&now, &h->params_on_device, sizeof now) == 0) { h->fork_needed = true; return 0; }
     }
-    if (int rc = next_epoch_block(h)) return rc;
-    h->epoch_block_fresh = reuse_ok;   // (only tetsim_step passes reuse_ok: its frame launch may use this block instead of taking another;
-                                       //  every other caller's launches consume the block the upload names)
-    fill_params(h, dt, *params, &h->params_on_device);
-    h->params_known = true;
+    // (only tetsim_step passes reuse_ok: its launch may use this block instead of taking another; every other caller's launches consume
+    //  the block the upload names)
+    if (int rc = take_params(h, dt, params, reuse_ok)) return rc;
     // (a one-lane kernel whose arguments are the parameters: in stream order like the copy it replaces, without the copy engine)
     util_launch_set_params(h->stream, h->d_params, h->params_on_device);
     // the halo queue runs the boundary particles itself (enqueue_phase_a) and is ordered against the main queue only through
@@ -178,7 +199,6 @@ int push_params(tetsim_body* h, double dt, const TetSimParams* params, bool reus
     if (h->comm_stream && h->d_params_halo) util_launch_set_params(h->comm_stream, h->d_params_halo, h->params_on_device);
     const hipError_t le = hipGetLastError();
     if (le != hipSuccess) return fail(h, TETSIM_EHIP, std::string("kernel launch: ") + hipGetErrorString(le));
-    h->fork_needed = true;  // whatever the caller did on the main stream since the last call must be visible to the boundary stream
     return 0;
 }
 
@@ -186,17 +206,8 @@ int push_params(tetsim_body* h, double dt, const TetSimParams* params, bool reus
 // kernels behind it): the same checks, a fresh block of sequence numbers, the host's record of what the device holds once the launch has
 // run -- and no copy, no event, no pinned slot.  (A launch that is not enqueued takes that record back: launched_with_params.)
 int stage_params(tetsim_body* h, double dt, const TetSimParams* params) {
-    if (!params) return fail(h, TETSIM_EINVAL, "params is null");
-    if (!(dt > 0.0) || !std::isfinite(dt)) return fail(h, TETSIM_EINVAL, "dt must be a positive finite number");
-    HIPCHK(h, hipSetDevice(h->opt.device));
-    h->final_ghosts_fresh = false;
-    h->quat_stale = true;
-    if (int rc = next_epoch_block(h)) return rc;
-    h->epoch_block_fresh = false;
-    fill_params(h, dt, *params, &h->params_on_device);
-    h->params_known = true;
-    h->fork_needed = true;
-    return 0;
+    if (int rc = open_call(h, dt, params)) return rc;
+    return take_params(h, dt, params, false);
 }
 
 // ... for such a call: staged, unless its dt differs from the one the predictions on the device were made with -- the re-prediction kernel
@@ -211,12 +222,12 @@ int params_for_launch(tetsim_body* h, double dt, const TetSimParams* params) {
 void pj_tet(tetsim_body* h, hipEvent_t e0, hipEvent_t e1) {
     if (h->quad) pjq_launch_tet(h->stream, h->blk, e0, e1);
     else if (h->blocked) pjb_launch_tet(h->stream, h->blk, 0, h->blk.nb, e0, e1);
-    else h->fast ? pj_launch_tet_fast(h->stream, h->pj, e0, e1) : pj_launch_tet_precise(h->stream, h->pj, e0, e1);
+    else pj_launchers(h).tet(h->stream, h->pj, e0, e1);
 }
 void pj_vertex(tetsim_body* h, uint32_t first, uint32_t count, hipEvent_t e0, hipEvent_t e1) {
     if (h->quad) pjq_launch_vertex(h->stream, h->blk, e0, e1);   // (all owned particles: quad bodies are unpartitioned)
     else if (h->blocked) pjb_launch_vertex(h->stream, h->blk, first, count, e0, e1);
-    else h->fast ? pj_launch_vertex_fast(h->stream, h->pj, first, count, e0, e1) : pj_launch_vertex_precise(h->stream, h->pj, first, count, e0, e1);
+    else pj_launchers(h).vertex(h->stream, h->pj, first, count, e0, e1);
 }
 // One substep of a fused body inside a run of substeps with one dt (HISTORY.md 5.4):
 //   first substep:  plain tet kernel (predictions of the previous call's particle kernel)          -> partial sums A
@@ -247,7 +258,7 @@ void pj_fused_substep(tetsim_body* h, bool first, bool last, hipEvent_t* e) {
 }
 void pj_repredict(tetsim_body* h) {
     if (h->blocked) pjb_launch_repredict(h->stream, h->blk);
-    else h->fast ? pj_launch_repredict_fast(h->stream, h->pj) : pj_launch_repredict_precise(h->stream, h->pj);
+    else pj_launchers(h).repredict(h->stream, h->pj);
 }
 
 // The halo stream carries the transfers AND the boundary tiles that consume them; high priority so that its few
@@ -258,12 +269,13 @@ void pj_repredict(tetsim_body* h) {
 void nh_sweep(tetsim_body* h, bool fold, bool last, bool one_launch) {
     NHDev nh = h->nh;
     if (!last) nh.vol_err = nullptr;
-    if (one_launch && h->nh_one_launch && !h->body_colliders_on) {   // (not while body colliders are on: tetsim_step, nh_one_now)   clustered FAST: every colour in ONE launch, particles handed on with their stamp (nh_kernels.inc: nh_sweep1_kernel)
+    const NHLaunchers& K = nh_launchers(h);
+    if (one_launch && nh_one_now(h)) {   // clustered FAST: every colour in ONE launch, particles handed on with their stamp (nh_kernels.inc: nh_sweep1_kernel)
         nh_launch_sweep1_fast(h->stream, nh, h->nh_sweep1, fold, h->nh_sub_index, h->nh_epoch_arg);
         return;
     }
     if (!h->cluster_launch.empty()) {
-        for (const NHClusterLaunch& L : h->cluster_launch) h->fast ? nh_launch_cluster_fast(h->stream, nh, L, fold) : nh_launch_cluster_precise(h->stream, nh, L, fold);
+        for (const NHClusterLaunch& L : h->cluster_launch) K.cluster(h->stream, nh, L, fold);
         return;
     }
     if (h->nh_frame && h->fast) {
@@ -273,8 +285,8 @@ void nh_sweep(tetsim_body* h, bool fold, bool last, bool one_launch) {
         for (size_t l = 0; l + 1 < h->level_off.size(); l++)
             for (uint32_t b = 0; b < bodies; b++) {
                 const uint32_t first = h->nh_seg[2u * (l * bodies + b)], count = h->nh_seg[2u * (l * bodies + b) + 1u] - first;
-                if (count <= kNHQuadLevelFast) nh_launch_level4_fast(h->stream, nh, first, count);
-                else nh_launch_level_fast(h->stream, nh, first, count);
+                if (count <= kNHQuadLevelFast) K.level4(h->stream, nh, first, count);
+                else K.level(h->stream, nh, first, count);
             }
         return;
     }
@@ -285,8 +297,8 @@ void nh_sweep(tetsim_body* h, bool fold, bool last, bool one_launch) {
     constexpr uint32_t level4_max = 8192u;
     for (size_t l = 0; l + 1 < h->level_off.size(); l++) {
         const uint32_t first = h->level_off[l], count = h->level_off[l + 1] - first;
-        if (count <= level4_max) h->fast ? nh_launch_level4_fast(h->stream, nh, first, count) : nh_launch_level4_precise(h->stream, nh, first, count);
-        else h->fast ? nh_launch_level_fast(h->stream, nh, first, count) : nh_launch_level_precise(h->stream, nh, first, count);
+        if (count <= level4_max) K.level4(h->stream, nh, first, count);
+        else K.level(h->stream, nh, first, count);
     }
 }
 
@@ -357,8 +369,7 @@ int launch_frame_kernel(tetsim_body* h, uint32_t n, uint32_t epoch) {
 }
 // the single-workgroup frame kernel of a small Neo-Hookean body for n substeps, the call's parameters among its arguments
 int launch_nh_frame_kernel(tetsim_body* h, uint32_t n) {
-    h->fast ? nh_launch_frame_fast(h->stream, h->nh, h->nh_frame_launch, n, h->params_on_device, h->d_params)
-            : nh_launch_frame_precise(h->stream, h->nh, h->nh_frame_launch, n, h->params_on_device, h->d_params);
+    nh_launchers(h).frame(h->stream, h->nh, h->nh_frame_launch, n, h->params_on_device, h->d_params);
     return launched_with_params(h);
 }
 
@@ -391,17 +402,25 @@ int enqueue_substep(tetsim_body* h, bool first, bool last) {
         // clustered schedules fold the particle pass BETWEEN two substeps of a run into the next sweep: the lane of the first cluster
         // to touch a particle finishes the previous substep and predicts the next for it while loading it (nh_kernels.inc:
         // fold_particle) -- one kernel and one launch boundary less per substep, the same operations per particle
-        if (first) h->fast ? nh_launch_predict_fast(h->stream, h->nh) : nh_launch_predict_precise(h->stream, h->nh);
+        const NHLaunchers& K = nh_launchers(h);
+        if (first) K.predict(h->stream, h->nh);
         h->nh_sub_index = first ? 0u : h->nh_sub_index + 1u;
         nh_sweep(h, !first && h->nh_fold, last, true);
-        if (last) h->fast ? nh_launch_post_fast(h->stream, h->nh) : nh_launch_post_precise(h->stream, h->nh);
-        else if (h->nh_fold) h->fast ? nh_launch_post_predict_list_fast(h->stream, h->nh, h->d_nh_untouched, h->nh_untouched)
-                                     : nh_launch_post_predict_list_precise(h->stream, h->nh, h->d_nh_untouched, h->nh_untouched);
-        else h->fast ? nh_launch_post_predict_fast(h->stream, h->nh) : nh_launch_post_predict_precise(h->stream, h->nh);
+        if (last) K.post(h->stream, h->nh);
+        else if (h->nh_fold) K.post_predict_list(h->stream, h->nh, h->d_nh_untouched, h->nh_untouched);
+        else K.post_predict(h->stream, h->nh);
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(h, TETSIM_EHIP, std::string("kernel launch: ") + hipGetErrorString(e));
     return 0;
+}
+// the n substeps of a call, launch by launch (into the stream, or into its capture: build_graph); flush: with the flag path's last V hand-over
+// behind them (flush_v: nothing for a body without a halo queue)
+int enqueue_substeps(tetsim_body* h, uint32_t n, bool flush) {
+    int rc = 0;
+    for (uint32_t i = 0; i < n && !rc; i++) rc = enqueue_substep(h, i == 0, i + 1 == n);
+    if (!rc && flush) rc = flush_v(h);
+    return rc;
 }
 
 // POLAR_JACOBI keeps x* = x + v*dt precomputed by the previous vertex kernel; redo it if dt changed.
@@ -455,13 +474,12 @@ int ensure_prediction(tetsim_body* h, double dt) {
 int build_graph(tetsim_body* h, uint32_t n, hipGraphExec_t* out) {
     hipGraph_t graph = nullptr;
     HIPCHK(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-    int rc = 0;
     const bool halo = has_transport(h);
     if (halo) {  // the graph is self-contained: it forks the halo stream from the main stream and joins it before it ends
         h->halo_pending = false;
         h->fork_needed = true;
     }
-    for (uint32_t i = 0; i < n && !rc; i++) rc = enqueue_substep(h, i == 0, i + 1 == n);
+    int rc = enqueue_substeps(h, n, false);
     if (halo && !rc) {
         hipError_t je = hipStreamWaitEvent(h->stream, h->ev_sent2[h->halo_parity ^ 1u], 0);  // join: the last transfer
         if (je != hipSuccess) rc = fail(h, TETSIM_EHIP, std::string("join: ") + hipGetErrorString(je));
@@ -474,6 +492,12 @@ int build_graph(tetsim_body* h, uint32_t n, hipGraphExec_t* out) {
     (void)hipGraphDestroy(graph);
     if (e != hipSuccess) return fail(h, TETSIM_EHIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
     return 0;
+}
+// every captured graph of the body: they hold the kernels of the way it stepped when they were captured (tetsim_sync: a body that leaves a
+// path for good; tetsim_destroy)
+void drop_graphs(tetsim_body* h) {
+    for (auto& kv : h->graphs) (void)hipGraphExecDestroy(kv.second);
+    h->graphs.clear();
 }
 
 }  // namespace tetsim
@@ -681,8 +705,7 @@ void tetsim_destroy(tetsim_handle h) {
 #endif
     frame_turn_leave(h);
     // graphs first: a captured halo graph holds RCCL work, and ncclCommDestroy waits for (hangs on) captured work that still exists
-    for (auto& kv : h->graphs) (void)hipGraphExecDestroy(kv.second);
-    h->graphs.clear();
+    drop_graphs(h);
     drop_flag_graphs(h);
     for (PeerLink& l : h->links) for (void* m : l.ipc) if (m) (void)hipIpcCloseMemHandle(m);
     if (h->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(h->comm);
@@ -704,19 +727,34 @@ int tetsim_get_info(tetsim_handle h, TetSimInfo* info) {
     return 0;
 }
 
-// The persistent frame kernel serves this call -- not while a quad body has body colliders on: pjq_frame_kernel has no register for a second
-// kind of list (pj_quad.hip: pjq_vertex_update), the body then takes the two launches per substep that tetsim_profile and the fall-back
-// take, which agree with the frame kernel bit for bit.
-// Nor while a body of the 256-tet tiles has body pins on: pjb_frame_kernel is compiled without them (with them it lost a wave of occupancy:
-// dev_common.h, body_grab_pick), the body then steps through the fused kernels, which agree with the frame kernel bit for bit.
-static bool frame_now(const tetsim_body* h) { return h->frame && !(h->quad && h->body_colliders_on) && !(!h->quad && h->body_pins_on); }
-// Likewise the Neo-Hookean calls that are one launch: nh_frame_kernel, nh_sweep1_kernel and nh_call_kernel keep the parent's particle pass
-// (with the second list they lose a wave of occupancy or gain a stack: nh_kernels.inc, post_vertex), so while body colliders are on the
-// body steps through the level / cluster kernels and the particle kernels, which take the table and agree with them bit for bit.
-static bool nh_frame_now(const tetsim_body* h) { return h->nh_frame && !h->body_colliders_on; }
-static bool nh_one_now(const tetsim_body* h) { return h->nh_one_launch && !h->body_colliders_on; }
+// (Which one-launch path serves a call while a per-body switch is on: frame_now, nh_frame_now, nh_one_now -- body.h.)
 // a captured graph holds the kernels of the way the body stepped when it was captured: one set of graphs per way
-static uint32_t graph_key(const tetsim_body* h, uint32_t n) { return h->nh_one_launch && h->body_colliders_on ? n | 0x80000000u : n; }
+static uint32_t graph_key(const tetsim_body* h, uint32_t n) { return h->nh_one_launch && !nh_one_now(h) ? n | 0x80000000u : n; }
+// A halo graph that cannot be captured or built (an RCCL build that refuses capture): the body stays eager for good, loudly; the message
+// names what refused (h->err).
+static void halo_graph_failed(tetsim_body* h) {
+    fprintf(stderr, "[tetsim] halo graph capture failed (%s); falling back to eager halo stepping\n", h->err.c_str());
+    h->halo_graph_broken = true;
+    (void)hipGetLastError();
+}
+
+// The most substeps ONE launch of this body may hold; tetsim_step_n cuts a longer call into calls of that many.  At most one of the three
+// flags is set on a handle, so the bounds never meet: `frame` is given only inside create_polar's `if (h->fused || h->quad)`
+// (tetsim_create.hip), `pj_one_launch` a few lines above it only with `!h->fused && !h->quad`, and `nh_one_launch` by create_neohookean
+// alone -- a handle is built by one of the two (create_common).  tetsim_sync only ever clears them.
+constexpr uint32_t kFrameCallMost = 32768u;   // a persistent frame launch stamps substep s of its call with epoch + s, inside one block
+static_assert(kFrameCallMost <= kStampBlock, "the substeps of one frame launch are numbered inside one block of stamps");
+static uint32_t most_substeps_per_launch(const tetsim_body* h) {
+    if (h->frame) return kFrameCallMost;
+    // the one-launch call of large polar bodies: n periods of its dispatch table and the table's tail in one grid of at most 2^32 - 1
+    // work-items, stamps inside one block; every chunk drains
+    if (h->pj_one_launch) return pjb_call_chunk(h->call_sched.period, h->call_sched.tail, kBlockTile, 8192u);
+    if (h->nh_one_launch) {   // the one-launch sweep stamps substep x colour inside one block too; the call kernel's grid is n x its blocks
+        const uint32_t stamps = 65000u / h->nh_sweep1.ncolours;
+        return h->nh_call ? call_chunk(nh_call_blocks_per_sub(h->nh_sweep1.blocks), 256u, stamps) : stamps;
+    }
+    return 0xffffffffu;   // kernel by kernel, or a graph of them: any n
+}
 
 int tetsim_step(tetsim_handle h, double dt, const TetSimParams* params) {
     if (!h) return TETSIM_EINVAL;
@@ -753,24 +791,10 @@ int tetsim_step_n(tetsim_handle h, uint32_t n, double dt, const TetSimParams* pa
     if (!h) return TETSIM_EINVAL;
     if (!h->group.empty()) return fail(h, TETSIM_ESTATE, "this body belongs to an in-process group: step it with tetsim_group_step_n");
     if (n == 0) return 0;
-    while (h->frame && n > 32768u) {   // (a persistent launch numbers its substeps inside one block of 65,536 sequence numbers)
-        if (int rc = tetsim_step_n(h, 32768u, dt, params)) return rc;
-        n -= 32768u;
-    }
-    if (h->pj_one_launch) {   // (the one-launch call of large polar bodies: n periods of its dispatch table and the table's tail in one grid of at most 2^32 - 1 work-items, stamps inside one block; every chunk drains)
-        const uint32_t most = pjb_call_chunk(h->call_sched.period, h->call_sched.tail, kBlockTile, 8192u);
-        while (n > most) {
-            if (int rc = tetsim_step_n(h, most, dt, params)) return rc;
-            n -= most;
-        }
-    }
-    if (h->nh_one_launch) {            // (the one-launch sweep stamps substep x colour inside one block too; the call kernel's grid is n x its blocks)
-        const uint32_t stamps = 65000u / h->nh_sweep1.ncolours;
-        const uint32_t most = h->nh_call ? call_chunk(nh_call_blocks_per_sub(h->nh_sweep1.blocks), 256u, stamps) : stamps;
-        while (n > most) {
-            if (int rc = tetsim_step_n(h, most, dt, params)) return rc;
-            n -= most;
-        }
+    const uint32_t most = most_substeps_per_launch(h);
+    while (n > most) {   // a long call: calls of `most` substeps, then the rest below
+        if (int rc = tetsim_step_n(h, most, dt, params)) return rc;
+        n -= most;
     }
     HIPCHK(h, hipSetDevice(h->opt.device));
     if (h->nh_call && nh_one_now(h) && !has_transport(h)) {
@@ -778,9 +802,9 @@ int tetsim_step_n(tetsim_handle h, uint32_t n, double dt, const TetSimParams* pa
         // that ends the call -- three direct launches, the first of which brings the call's parameters along
         if (int rc = params_for_launch(h, dt, params)) return rc;
         return launch_in_turn(h, [&]() -> int {
-            nh_launch_predict_value_fast(h->stream, h->nh, h->params_on_device, h->d_params);
+            nh_launchers_fast.predict_value(h->stream, h->nh, h->params_on_device, h->d_params);
             nh_launch_call_fast(h->stream, h->nh, h->nh_sweep1, n);
-            nh_launch_post_fast(h->stream, h->nh);
+            nh_launchers_fast.post(h->stream, h->nh);
             return launched_with_params(h);
         });
     }
@@ -791,9 +815,8 @@ int tetsim_step_n(tetsim_handle h, uint32_t n, double dt, const TetSimParams* pa
     if (h->nh_frame && !nh_frame_now(h)) {
         // ... and with body colliders on its level kernels, launched one by one: the stepwise twin launches a kernel per level and BODY, and a
         // batch's call is tens of thousands of them (64 Dragons x 34 levels x 20 substeps) -- too long a chain to capture as one graph
-        int rc = push_params(h, dt, params);
-        for (uint32_t i = 0; i < n && !rc; i++) rc = enqueue_substep(h, i == 0, i + 1 == n);
-        return rc;
+        if (int rc = push_params(h, dt, params)) return rc;
+        return enqueue_substeps(h, n, false);
     }
     if ((frame_now(h) || h->pj_one_launch) && !has_transport(h)) {
         // Calls that are ONE kernel -- small polar bodies: the persistent frame kernel, every tile's workgroup resident for the n substeps
@@ -822,17 +845,12 @@ int tetsim_step_n(tetsim_handle h, uint32_t n, double dt, const TetSimParams* pa
             // by independent hardware queues (probed once) and the chains can be captured (else: eager for good, loudly)
             if ((rc = probe_queue_independence(h))) return rc;
             if (h->queues_independent) {
-                rc = step_n_flag_graphs(h, n);
-                if (!rc) return 0;
-                fprintf(stderr, "[tetsim] halo graph capture failed (%s); falling back to eager halo stepping\n", h->err.c_str());
-                h->halo_graph_broken = true;
-                (void)hipGetLastError();
-                rc = 0;
+                if (!step_n_flag_graphs(h, n)) return 0;
+                halo_graph_failed(h);   // (... and the eager substeps below)
             }
         }
         if (!own_rank || !h->comm || !use_graph || !h->halo_warm || h->halo_graph_broken || uses_flag_sync(h)) {
-            for (uint32_t i = 0; i < n && !rc; i++) rc = enqueue_substep(h, i == 0, i + 1 == n);
-            if (!rc) rc = flush_v(h);
+            rc = enqueue_substeps(h, n, true);
             h->halo_warm = true;
             return rc;
         }
@@ -846,22 +864,15 @@ int tetsim_step_n(tetsim_handle h, uint32_t n, double dt, const TetSimParams* pa
         // One queue and kernels of tens of microseconds each: the substeps' kernels go into the stream one by one.  A graph's replay ends
         // with a completion signal that the next call's first kernel waits ~9 us for; kernel follows kernel without a gap, and the host
         // (2-3 us per launch) stays ahead.  Small bodies keep their graphs: their kernels are shorter than a launch call.
-        for (uint32_t i = 0; i < n && !rc; i++) rc = enqueue_substep(h, i == 0, i + 1 == n);
-        return rc;
+        return enqueue_substeps(h, n, false);
     }
     auto it = h->graphs.find(graph_key(h, n));
     if (it == h->graphs.end()) {
         hipGraphExec_t exec = nullptr;
         if ((rc = build_graph(h, n, &exec))) {
             if (!has_transport(h)) return rc;
-            // a halo graph that cannot be built (an RCCL build that refuses capture): stay eager for good, loudly
-            fprintf(stderr, "[tetsim] halo graph capture failed (%s); falling back to eager halo stepping\n", h->err.c_str());
-            h->halo_graph_broken = true;
-            (void)hipGetLastError();
-            rc = 0;
-            for (uint32_t i = 0; i < n && !rc; i++) rc = enqueue_substep(h, i == 0, i + 1 == n);
-            if (!rc) rc = flush_v(h);
-            return rc;
+            halo_graph_failed(h);
+            return enqueue_substeps(h, n, true);
         }
         it = h->graphs.emplace(graph_key(h, n), exec).first;
     }
@@ -875,46 +886,35 @@ int tetsim_step_n(tetsim_handle h, uint32_t n, double dt, const TetSimParams* pa
     return 0;
 }
 
+// The error word of a one-launch kernel whose bounded wait gave up: read, and if it is raised, cleared; the body leaves that path for good
+// (*flag; leave_turn: and its device's turn-taking of persistent launches), no captured graph survives, and the call fails with `msg`.
+static int wait_gave_up(tetsim_body* h, uint32_t* word, bool* flag, bool leave_turn, const char* msg) {
+    uint32_t err = 0;
+    HIPCHK(h, hipMemcpy(&err, word, sizeof err, hipMemcpyDeviceToHost));
+    if (!err) return 0;
+    HIPCHK(h, hipMemset(word, 0, sizeof err));
+    *flag = false;
+    if (leave_turn) frame_turn_leave(h);
+    drop_graphs(h);
+    return fail(h, TETSIM_EHIP, msg);
+}
+
 int tetsim_sync(tetsim_handle h) {
     if (!h) return TETSIM_EINVAL;
     if (int rc = drain(h)) return rc;
-    if (h->d_frame_err) {   // persistent frame kernel: a tile's wait for its neighbours' partial sums gave up (never in a correct run)
-        uint32_t err = 0;
-        HIPCHK(h, hipMemcpy(&err, h->d_frame_err, sizeof err, hipMemcpyDeviceToHost));
-        if (err) {
-            HIPCHK(h, hipMemset(h->d_frame_err, 0, sizeof err));
-            h->frame = false;   // step with one kernel per substep from now on
-            frame_turn_leave(h);   // ... and no longer makes the device's persistent launches take turns
-            for (auto& kv : h->graphs) (void)hipGraphExecDestroy(kv.second);
-            h->graphs.clear();
-            return fail(h, TETSIM_EHIP, "persistent frame kernel: a tile waited in vain for a neighbour tile's partial sums (workgroups not co-resident?); "
-                                        "the state since then is invalid; this body falls back to one kernel per substep");
-        }
-    }
-    if (h->pj_one_launch) {   // one-launch substep: a particle wave waited in vain for a tile's partial sums (never in a correct run)
-        uint32_t err = 0;
-        HIPCHK(h, hipMemcpy(&err, h->d_substep_err, sizeof err, hipMemcpyDeviceToHost));
-        if (err) {
-            HIPCHK(h, hipMemset(h->d_substep_err, 0, sizeof err));
-            h->pj_one_launch = false;   // two kernels per substep from now on
-            for (auto& kv : h->graphs) (void)hipGraphExecDestroy(kv.second);
-            h->graphs.clear();
-            return fail(h, TETSIM_EHIP, "one-launch substep: a particle wave waited in vain for a tile's partial sums (workgroups not dispatched in grid order?); "
-                                        "the state since then is invalid; this body falls back to two kernels per substep");
-        }
-    }
-    if (h->nh_one_launch) {   // one-launch Gauss-Seidel sweep: a cluster waited in vain for a particle of an earlier colour (never in a correct run)
-        uint32_t err = 0;
-        HIPCHK(h, hipMemcpy(&err, h->nh_sweep1.error, sizeof err, hipMemcpyDeviceToHost));
-        if (err) {
-            HIPCHK(h, hipMemset(h->nh_sweep1.error, 0, sizeof err));
-            h->nh_one_launch = false;   // one launch per colour from now on
-            for (auto& kv : h->graphs) (void)hipGraphExecDestroy(kv.second);
-            h->graphs.clear();
-            return fail(h, TETSIM_EHIP, "one-launch Gauss-Seidel sweep: a cluster waited in vain for a particle of an earlier colour (workgroups not dispatched in grid order?); "
-                                        "the state since then is invalid; this body falls back to one launch per colour");
-        }
-    }
+    // the three one-launch kernels' bounded waits (never in a correct run): each body falls back to its stepwise kernels
+    if (h->d_frame_err)   // persistent frame kernel: a tile's wait for its neighbours' partial sums gave up -- one kernel per substep from now on, and no longer in its device's turn-taking
+        if (int rc = wait_gave_up(h, h->d_frame_err, &h->frame, true,
+                                  "persistent frame kernel: a tile waited in vain for a neighbour tile's partial sums (workgroups not co-resident?); "
+                                  "the state since then is invalid; this body falls back to one kernel per substep")) return rc;
+    if (h->pj_one_launch)   // one-launch substep: a particle wave waited in vain for a tile's partial sums -- two kernels per substep from now on
+        if (int rc = wait_gave_up(h, h->d_substep_err, &h->pj_one_launch, false,
+                                  "one-launch substep: a particle wave waited in vain for a tile's partial sums (workgroups not dispatched in grid order?); "
+                                  "the state since then is invalid; this body falls back to two kernels per substep")) return rc;
+    if (h->nh_one_launch)   // one-launch Gauss-Seidel sweep: a cluster waited in vain for a particle of an earlier colour -- one launch per colour from now on
+        if (int rc = wait_gave_up(h, h->nh_sweep1.error, &h->nh_one_launch, false,
+                                  "one-launch Gauss-Seidel sweep: a cluster waited in vain for a particle of an earlier colour (workgroups not dispatched in grid order?); "
+                                  "the state since then is invalid; this body falls back to one launch per colour")) return rc;
     if (h->d_sync) {  // a bounded device-side wait that gave up (util_kernels.hip): the results since then are not to be trusted
         uint32_t err = 0;
         HIPCHK(h, hipMemcpy(&err, h->d_sync + 4, sizeof err, hipMemcpyDeviceToHost));

@@ -742,7 +742,7 @@ int create_neohookean(tetsim_body* h, const float* verts, uint32_t nv, const int
         const uint32_t bodies = static_cast<uint32_t>(first_vert.size() - 1);
         uint32_t most_v = 0, most_t = 0;
         for (uint32_t b = 0; b < bodies; b++) { most_v = std::max(most_v, first_vert[b + 1] - first_vert[b]); most_t = std::max(most_t, first_tet[b + 1] - first_tet[b]); }
-        const uint32_t lds_limit = h->fast ? nh_frame_lds_limit_fast() : nh_frame_lds_limit_precise();
+        const uint32_t lds_limit = nh_launchers(h).frame_lds_limit();
         if (most_v > 0 && static_cast<uint64_t>(most_v) * 40u <= lds_limit && (h->fast || most_t <= 12288u) && bodies <= 65535u) {
             // per level, where every body's tets begin (solve positions; the tets of a level lie body by body)
             std::vector<uint32_t> seg(2ull * nl * bodies);   // (first, end) pairs

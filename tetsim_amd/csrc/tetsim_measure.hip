@@ -44,11 +44,11 @@ int tetsim_profile(tetsim_handle h, uint32_t n, double dt, const TetSimParams* p
             pj_vertex(h, 0, h->pj.nv_owned, ev[4 * i + 2], ev[4 * i + 3]);
         } else {
             HIPCHK(h, hipEventRecord(ev[4 * i], h->stream));
-            h->fast ? nh_launch_predict_fast(h->stream, h->nh) : nh_launch_predict_precise(h->stream, h->nh);
+            nh_launchers(h).predict(h->stream, h->nh);
             HIPCHK(h, hipEventRecord(ev[4 * i + 1], h->stream));
             nh_sweep(h);
             HIPCHK(h, hipEventRecord(ev[4 * i + 2], h->stream));
-            h->fast ? nh_launch_post_fast(h->stream, h->nh) : nh_launch_post_precise(h->stream, h->nh);
+            nh_launchers(h).post(h->stream, h->nh);
             HIPCHK(h, hipEventRecord(ev[4 * i + 3], h->stream));
         }
     }
@@ -100,8 +100,8 @@ int tetsim_time_kernels(tetsim_handle h, uint32_t reps, double dt, const TetSimP
     };
     auto vert_once = [&]() {
         if (pjs) { pj_vertex(h, 0, h->pj.nv_owned); return 1u; }
-        h->fast ? nh_launch_predict_fast(h->stream, h->nh) : nh_launch_predict_precise(h->stream, h->nh);
-        h->fast ? nh_launch_post_fast(h->stream, h->nh) : nh_launch_post_precise(h->stream, h->nh);
+        nh_launchers(h).predict(h->stream, h->nh);
+        nh_launchers(h).post(h->stream, h->nh);
         return 2u;
     };
     float ms = 0.0f;
