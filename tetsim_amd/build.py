@@ -34,6 +34,8 @@ UNITS = {
     "tetsim_api.hip": ["-ffp-contract=off"],
     "tetsim_state.hip": ["-ffp-contract=off"],
     "tetsim_visual.hip": ["-ffp-contract=off"],
+    # host code only; it decodes the sphere keys with query_rays.h's arithmetic, whose units are all built this way
+    "tetsim_query.hip": ["-ffp-contract=off"],
     "tetsim_measure.hip": ["-ffp-contract=off"],
     "device_io.hip": ["-ffp-contract=off"],
     "snapshot.hip": ["-ffp-contract=off"],
@@ -85,7 +87,7 @@ UNITS = {
     "query_closest.hip": ["-ffp-contract=off"],
     "build_info.cpp": ["-x", "hip"],
 }
-HEADERS = ["body.h", "body_reduce.h", "body_rows.h", "dev_common.h", "dev_store.h", "host_prep.h", "mesh_file.h", "pj_kernels.inc", "pj_math.inc", "pj_lab.h", "pj_blocked_lab.inc", "nh_kernels.inc", "collide.h", "query_device.h", "query_rays.h", os.path.join("..", "..", "include", "tetsim.h")]
+HEADERS = ["body.h", "body_reduce.h", "body_rows.h", "dev_common.h", "dev_store.h", "host_prep.h", "mesh_file.h", "pj_kernels.inc", "pj_math.inc", "pj_lab.h", "pj_blocked_lab.inc", "nh_kernels.inc", "collide.h", "query_device.h", "query_rays.h", "query_tree.h", os.path.join("..", "..", "include", "tetsim.h")]
 # what determines the polar tet kernel (pjb_tet_kernel), its tiling and therefore its HBM traffic: profiles/pmc_traffic.json
 # is keyed by the hash of these (+ their flags), so a stale counter figure is never attached to a different kernel
 KERNEL_FILES = ["pj_blocked.hip", "pj_math.inc", "pj_lab.h", "collide.h", "dev_common.h", "dev_store.h", "host_prep.cpp", "host_prep.h"]

@@ -4,7 +4,7 @@
 //                      nh_frame_now, nh_one_now) and the launchers of the handle's arithmetic mode (pj_launchers, nh_launchers)
 //   tetsim_state.hip   the state's host entry points: reads (copying: on the host; pinned: through the gather), tetsim_write_state,
 //                      checkpoint and resume, plan getters; state_sections(), the table of self-describing sections that IS the complete state
-//   tetsim_visual.hip  embedded visual mesh (its set-up and its host reads), grab (pin, nearest-particle query), picking
+//   tetsim_visual.hip  embedded visual mesh (its set-up and its host reads), grab (pin, nearest-particle query), the handle's colliders; tetsim_query.hip: picking, range sensors, closest points
 //   device_io.hip      how rows leave and enter the device arrays, for all of the above: the table of TETSIM_FIELD_* (source, rows, width,
 //                      index map, what must run first, which requests are errors), the one gather kernel and the staging buffer of the
 //                      host reads that use it; export / import in device memory; every device-side call's guard and ordering against a caller's stream

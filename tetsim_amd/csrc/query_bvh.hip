@@ -1,18 +1,19 @@
 // query_bvh.hip -- range sensors through a refitted bounding-volume hierarchy (include/tetsim.h: tetsim_raycast_visual_bvh_device;
-// query_device.h: the layout).  The answer is DEFINED without the tree (tests/raycast_bvh_ref.py is the definition in numpy: brute force
-// with two extra predicates per triangle), and every test the traversal skips on is monotone in the box, so that tree shape and visit
-// order cannot change a bit of it:
-//   * the padded slab test of a node's f32 box uses the formulas and the padding e of a triangle's own box; a box that contains a
-//     triangle's box has tn <= the triangle's tn, tf >= its tf, and passes every axis test the triangle's passes;
-//   * a node is skipped only if it holds no triangle, its own test fails, tn > far, tf < near, or a best hit exists and tn > its distance
-//     (tn == best is entered: a lower triangle index may tie);
-//   * at a leaf every triangle is tested against the box of its OWN corners, then by tri_test (query_rays.h, the brute-force call's).
+// query_device.h: the layout; query_tree.h: the walk, and why tree shape and visit order cannot change a bit of the answer).  The answer is
+// DEFINED without the tree (tests/raycast_bvh_ref.py is the definition in numpy: brute force with two extra predicates per triangle).
+// This walk's predicate:
+//   * the padded slab test: a box that contains a triangle's box has tn <= the triangle's tn, tf >= its tf, and passes every axis test
+//     the triangle's passes;
+//   * a node is refused only if its own test fails, tn > far, tf < near, or a best hit exists and tn > its distance (tn == best is
+//     entered: a lower triangle index may tie);
+//   * a triangle is tested against the box of its OWN corners, then by tri_test (query_rays.h, the brute-force call's).
 // f64, every operation rounded separately: build with -ffp-contract=off.
 //   Topology: once per handle on the host (bvh_build_topology, plain C++).  Refit: every call, two launches whatever the batch.
 //   Traversal: one lane per ray, stackless -- a complete tree in heap order needs one word of "the sibling is still to do" bits.
 #include "dev_common.h"
 #include "query_device.h"
 #include "query_rays.h"
+#include "query_tree.h"
 
 #include <algorithm>
 #include <cmath>
@@ -95,110 +96,47 @@ __device__ inline bool slab_test(const RayPrep& r, const SlabRay& y, const float
     return tn <= tf;
 }
 
-// A lane = one ray.  It walks the tree of its body (the trees of all bodies, lowest first, without ray_body) near child first and keeps
-// its best by the lexicographic rule.  No stack: going down from a node of level l with both children to visit sets bit l of `pending`;
-// going up, the deepest set bit above the node names the ancestor whose other child is next.  Lanes of a wave diverge as their rays do;
-// which bodies they name costs no more than that.
+// A lane = one ray.  It walks the tree of its body (the trees of all bodies, lowest first, without a body array) near child first
+// (query_tree.h: tree_walk) and keeps its best by the lexicographic rule.
 template <bool kStats>
 __global__ __launch_bounds__(256) void bvh_cast_kernel(QueryDev q, QueryBodiesDev t, BvhDev v, CastIo io, uint32_t first) {
     const uint32_t i = first + blockIdx.x * 256u + threadIdx.x;
     if (!(i < io.count && i >= first)) return;   // (i >= first: the last chunk's index may wrap)
     const CastRay c = cast_load(q, t, io, i);
     double bd = 0.0, bp[3] = {0.0, 0.0, 0.0};
-    uint32_t bt = kRayNone, boxes = 0u, tris = 0u;
+    uint32_t bt = kRayNone;
+    TreeCounts count;
     RayPrep r;
     r.culled = 1u;
     if (!c.bad) r = ray_prepare(c.r, c.words);
     if (!r.culled) {
         SlabRay y;
-        {
-            double cen[3], w[3];
-            sphere_centre(c.words, cen);
-            const double radius = sqrt(__longlong_as_double(static_cast<long long>(*reinterpret_cast<const unsigned long long*>(c.words + 6))));
-            for (int k = 0; k < 3; k++) w[k] = r.o[k] - cen[k];
-            y.e = 0x1p-20 * (radius + sqrt(dot3(w, w)));
-            y.flat = 0u;
-            for (int k = 0; k < 3; k++) {
-                y.inv[k] = 1.0 / r.d[k];
-                if (r.d[k] == 0.0 || y.inv[k] - y.inv[k] != 0.0) y.flat |= 1u << k;   // (x - x: NaN for an infinity)
-            }
+        y.e = tree_padding(c.words, r.o);
+        y.flat = 0u;
+        for (int k = 0; k < 3; k++) {
+            y.inv[k] = 1.0 / r.d[k];
+            if (r.d[k] == 0.0 || y.inv[k] - y.inv[k] != 0.0) y.flat |= 1u << k;   // (x - x: NaN for an infinity)
         }
-        // may this node be entered?  (every reason to skip one: query_bvh.hip's head)
-        auto open = [&](const float lo[3], const float hi[3], double& tn) {
-            if (lo[0] > hi[0]) return false;   // the empty box: no triangle below
-            if (kStats) boxes++;
-            double tf;
-            if (!slab_test(r, y, lo, hi, tn, tf)) return false;
-            if (tn > r.far || tf < r.near) return false;
-            return !(bt != kRayNone && tn > bd);
-        };
-        const uint32_t b0 = io.ray_body ? c.body : 0u, b1 = io.ray_body ? c.body + 1u : t.bodies;
-        for (uint32_t b = b0; b < b1; b++) {
-            const uint32_t tfirst = t.tri_first[b], ntri = t.tri_first[b + 1u] - tfirst;
-            if (ntri == 0u) continue;
-            const uint32_t depth = v.depth[b];
-            const BvhBox* const box = v.box + v.node_first[b];
-            uint32_t node = 1u, pending = 0u;
-            bool walking;
-            {
-                const BvhBox root = box[1];
-                double tn;
-                walking = open(root.lo, root.hi, tn);
-            }
-            // this subtree is done: up to the deepest ancestor whose other child waits; false: the tree is done
-            auto ascend = [&]() {
-                const uint32_t level = bvh_level(node), above = pending & ((1u << level) - 1u);
-                if (above == 0u) return false;
-                const uint32_t l = bvh_level(above);
-                pending &= ~(1u << l);
-                node = (node >> (level - (l + 1u))) ^ 1u;
-                return true;
-            };
-            while (walking) {
-                // Inner nodes first, down to a leaf: a wave leaves this loop when every lane has a leaf or is done, so that the lanes
-                // gather and test their leaves' triangles together and not one lane's leaf in every round of the others' descent.
-                while (walking && bvh_level(node) < depth) {
-                    // both children at once: 48 contiguous bytes, 16-byte aligned (node_first is even)
-                    const float4* const p = reinterpret_cast<const float4*>(box + 2u * node);
-                    const float4 x = p[0], m = p[1], z = p[2];
-                    const float lo0[3] = {x.x, x.y, x.z}, hi0[3] = {x.w, m.x, m.y}, lo1[3] = {m.z, m.w, z.x}, hi1[3] = {z.y, z.z, z.w};
-                    double tn0, tn1;
-                    const bool go0 = open(lo0, hi0, tn0), go1 = open(lo1, hi1, tn1);
-                    if (go0 && go1) { pending |= 1u << bvh_level(node); node = 2u * node + (tn1 < tn0 ? 1u : 0u); }
-                    else if (go0 || go1) node = 2u * node + (go1 ? 1u : 0u);
-                    else walking = ascend();
+        count = tree_walk<kStats>(
+            q, t, v, io.body ? c.body : 0u, io.body ? c.body + 1u : t.bodies,
+            // may this node be entered?  (every reason to skip one: this file's head)
+            [&](const float lo[3], const float hi[3], double& tn) {
+                double tf;
+                if (!slab_test(r, y, lo, hi, tn, tf)) return false;
+                if (tn > r.far || tf < r.near) return false;
+                return !(bt != kRayNone && tn > bd);
+            },
+            [&](uint32_t id, const float4 A, const float4 B, const float4 C, const float tlo[3], const float thi[3]) {
+                double tn, tf, d, pt[3];
+                if (!slab_test(r, y, tlo, thi, tn, tf)) return;           // not a candidate
+                if (tri_hit(r, A, B, C, d, pt) && tn <= d && d <= tf && better(d, id, bd, bt)) {
+                    bd = d; bt = id;
+                    bp[0] = pt[0]; bp[1] = pt[1]; bp[2] = pt[2];
                 }
-                if (!walking) break;
-                // the leaf's triangles: ids, corners' rows and corners each in one round of loads (an entered leaf holds a triangle: lo < ntri)
-                const uint32_t lo = (node - (1u << depth)) * kBvhLeaf, n = ntri - lo < kBvhLeaf ? ntri - lo : kBvhLeaf;
-                uint32_t id[kBvhLeaf];
-                int4 at[kBvhLeaf];
-                float4 A[kBvhLeaf], B[kBvhLeaf], C[kBvhLeaf];
-#pragma unroll
-                for (uint32_t j = 0; j < kBvhLeaf; j++) id[j] = v.order[tfirst + lo + (j < n ? j : 0u)];   // (behind the end: the first again, not tested)
-#pragma unroll
-                for (uint32_t j = 0; j < kBvhLeaf; j++) at[j] = q.tri[id[j]];
-#pragma unroll
-                for (uint32_t j = 0; j < kBvhLeaf; j++) { A[j] = q.pos[at[j].x]; B[j] = q.pos[at[j].y]; C[j] = q.pos[at[j].z]; }
-#pragma unroll
-                for (uint32_t j = 0; j < kBvhLeaf; j++) {
-                    if (j >= n) continue;
-                    float tlo[3] = {INFINITY, INFINITY, INFINITY}, thi[3] = {-INFINITY, -INFINITY, -INFINITY};
-                    box_add(tlo, thi, A[j]); box_add(tlo, thi, B[j]); box_add(tlo, thi, C[j]);
-                    if (kStats) tris++;
-                    double tn, tf, d, pt[3];
-                    if (!slab_test(r, y, tlo, thi, tn, tf)) continue;           // not a candidate
-                    if (tri_hit(r, A[j], B[j], C[j], d, pt) && tn <= d && d <= tf && better(d, id[j], bd, bt)) {
-                        bd = d; bt = id[j];
-                        bp[0] = pt[0]; bp[1] = pt[1]; bp[2] = pt[2];
-                    }
-                }
-                walking = ascend();
-            }
-        }
+            });
     }
     cast_store_result(t, io, i, c, bt, bd, bp);
-    if (kStats) { v.stats[2u * static_cast<size_t>(i)] = boxes; v.stats[2u * static_cast<size_t>(i) + 1u] = tris; }
+    if (kStats) tree_store_counts(v, i, count);
 }
 
 // 10 bits per axis, interleaved
@@ -268,16 +206,7 @@ void query_launch_bvh_refit(hipStream_t s, const QueryDev& q, const QueryBodiesD
 }
 
 void query_launch_cast_bvh(hipStream_t s, const QueryDev& q, const QueryBodiesDev& b, const BvhDev& v, const CastIo& io) {
-    // a dispatch holds at most 2^32 - 1 work-items (max_grid_blocks)
-    const uint64_t chunk = static_cast<uint64_t>(max_grid_blocks(256u)) * 256u;
-    for (uint64_t first = 0; first < io.count; first += chunk) {
-        const uint64_t n = std::min<uint64_t>(chunk, io.count - first);
-        const dim3 grid(static_cast<uint32_t>((n + 255u) / 256u));
-#ifdef TETSIM_BVH_STATS
-        if (v.stats) { hipLaunchKernelGGL(bvh_cast_kernel<true>, grid, dim3(256), 0, s, q, b, v, io, static_cast<uint32_t>(first)); continue; }
-#endif
-        hipLaunchKernelGGL(bvh_cast_kernel<false>, grid, dim3(256), 0, s, q, b, v, io, static_cast<uint32_t>(first));
-    }
+    launch_per_lane(s, bvh_cast_kernel<false>, bvh_cast_kernel<kTreeCounts>, q, b, v, io);
 }
 
 }  // namespace tetsim

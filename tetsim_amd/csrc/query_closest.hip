@@ -1,16 +1,16 @@
 // query_closest.hip -- closest-point queries through the refitted tree of query_bvh.hip (include/tetsim.h: tetsim_closest_visual_device;
-// query_device.h: the layout, and the refit this kernel runs behind).  The answer is DEFINED without the tree (tests/closest_ref.py is the
-// definition in numpy: brute force, three.js r160's Triangle.closestPointToPoint per triangle, one box predicate), and the one test the
-// traversal skips on is monotone in the box, so that tree shape and visit order cannot change a bit of it:
-//   * the bound lb of a node's f32 box uses the formulas and the padding e of a triangle's own box; a box that contains a triangle's box
-//     has lb <= the triangle's lb;
-//   * a node is skipped only if it holds no triangle, lb > max_distance^2, or a best exists and lb > its d2 (lb == best is entered: a
-//     lower triangle index may tie);
-//   * at a leaf every triangle is tested against the box of its OWN corners, then by tri_closest.
-// f64, every operation rounded separately: build with -ffp-contract=off.  One lane per query, stackless, as bvh_cast_kernel.
+// query_device.h: the layout, and the refit this kernel runs behind; query_tree.h: the walk, and why tree shape and visit order cannot
+// change a bit of the answer).  The answer is DEFINED without the tree (tests/closest_ref.py is the definition in numpy: brute force,
+// three.js r160's Triangle.closestPointToPoint per triangle, one box predicate).  This walk's predicate:
+//   * the bound lb of a box: a box that contains a triangle's box has lb <= the triangle's lb;
+//   * a node is refused only if lb > max_distance^2, or a best exists and lb > its d2 (lb == best is entered: a lower triangle index
+//     may tie);
+//   * a triangle is tested against the box of its OWN corners, then by tri_closest.
+// f64, every operation rounded separately: build with -ffp-contract=off.  One lane per query.
 #include "dev_common.h"
 #include "query_device.h"
 #include "query_rays.h"
+#include "query_tree.h"
 
 #include <algorithm>
 #include <cmath>
@@ -76,7 +76,7 @@ __device__ inline int tri_closest(const double p[3], const float4 A, const float
 }
 
 // the 64 bytes of a record as eight 8-byte stores (the record is 8-byte aligned, no more)
-__device__ inline void closest_store(const ClosestIo& io, uint32_t i, int32_t found, int32_t body, int32_t triangle, int32_t region, double distance,
+__device__ inline void closest_store(const CastIo& io, uint32_t i, int32_t found, int32_t body, int32_t triangle, int32_t region, double distance,
                                      const double pt[3], double v, double w) {
     unsigned long long* const o = reinterpret_cast<unsigned long long*>(io.out + static_cast<uint64_t>(i) * io.out_stride);
     o[0] = static_cast<unsigned long long>(static_cast<uint32_t>(found)) | (static_cast<unsigned long long>(static_cast<uint32_t>(body)) << 32);
@@ -87,137 +87,62 @@ __device__ inline void closest_store(const ClosestIo& io, uint32_t i, int32_t fo
     o[7] = static_cast<unsigned long long>(__double_as_longlong(w));
 }
 
-// A lane = one query.  It walks the tree of its body (the trees of all bodies, lowest first, without query_body), the child with the smaller
-// bound first, and keeps its best by the lexicographic rule.  The descent, the `pending` word and the leaf's gather are bvh_cast_kernel's.
+// A lane = one query.  It walks the tree of its body (the trees of all bodies, lowest first, without a body array), the child with the
+// smaller bound first (query_tree.h: tree_walk), and keeps its best by the lexicographic rule.
 template <bool kStats>
-__global__ __launch_bounds__(256) void bvh_closest_kernel(QueryDev q, QueryBodiesDev t, BvhDev v, ClosestIo io, uint32_t first) {
+__global__ __launch_bounds__(256) void bvh_closest_kernel(QueryDev q, QueryBodiesDev t, BvhDev v, CastIo io, uint32_t first) {
     const uint32_t i = first + blockIdx.x * 256u + threadIdx.x;
     if (!(i < io.count && i >= first)) return;   // (i >= first: the last chunk's index may wrap)
     double p[3], max2;
     bool bad;
-    uint32_t body = 0u;
-    const uint32_t* words = q.sphere;
+    uint32_t body;
+    const uint32_t* words;
     {
-        const double* const src = reinterpret_cast<const double*>(io.queries + static_cast<uint64_t>(i) * io.query_stride);
+        const double* const src = reinterpret_cast<const double*>(io.in + static_cast<uint64_t>(i) * io.in_stride);
         for (int k = 0; k < 3; k++) p[k] = src[k];
         const double limit = src[3];
         bad = point_query_defect(p, limit) != kPointGood;
         max2 = limit * limit;
-        if (io.query_body) {
-            const int32_t b = io.query_body[i];
-            if (b < 0 || static_cast<uint32_t>(b) >= t.bodies) bad = true;
-            else { body = static_cast<uint32_t>(b); words = t.spheres + static_cast<size_t>(b) * kSphereWords; }
-        }
+        if (record_body(q, t, io.body, i, &body, &words)) bad = true;
     }
     double bd2 = 0.0, bq[3] = {0.0, 0.0, 0.0}, bv = 0.0, bw = 0.0;
-    uint32_t bt = kRayNone, boxes = 0u, tris = 0u;
+    uint32_t bt = kRayNone;
+    TreeCounts count;
     int bregion = -1;
     if (!bad) {
-        double e;
-        {
-            double cen[3], d[3];
-            sphere_centre(words, cen);
-            const double radius = sqrt(__longlong_as_double(static_cast<long long>(*reinterpret_cast<const unsigned long long*>(words + 6))));
-            for (int k = 0; k < 3; k++) d[k] = p[k] - cen[k];
-            e = 0x1p-20 * (radius + sqrt(dot3(d, d)));
-        }
-        // may this node be entered?  (every reason to skip one: this file's head)
-        auto open = [&](const float lo[3], const float hi[3], double& lb) {
-            if (lo[0] > hi[0]) return false;   // the empty box: no triangle below
-            if (kStats) boxes++;
-            lb = box_bound(p, e, lo, hi);
-            if (lb > max2) return false;
-            return !(bt != kRayNone && lb > bd2);
-        };
-        const uint32_t b0 = io.query_body ? body : 0u, b1 = io.query_body ? body + 1u : t.bodies;
-        for (uint32_t b = b0; b < b1; b++) {
-            const uint32_t tfirst = t.tri_first[b], ntri = t.tri_first[b + 1u] - tfirst;
-            if (ntri == 0u) continue;
-            const uint32_t depth = v.depth[b];
-            const BvhBox* const box = v.box + v.node_first[b];
-            uint32_t node = 1u, pending = 0u;
-            bool walking;
-            {
-                const BvhBox root = box[1];
-                double lb;
-                walking = open(root.lo, root.hi, lb);
-            }
-            // this subtree is done: up to the deepest ancestor whose other child waits; false: the tree is done
-            auto ascend = [&]() {
-                const uint32_t level = bvh_level(node), above = pending & ((1u << level) - 1u);
-                if (above == 0u) return false;
-                const uint32_t l = bvh_level(above);
-                pending &= ~(1u << l);
-                node = (node >> (level - (l + 1u))) ^ 1u;
-                return true;
-            };
-            while (walking) {
-                // inner nodes first, down to a leaf: the lanes of a wave gather and test their leaves' triangles together
-                while (walking && bvh_level(node) < depth) {
-                    // both children at once: 48 contiguous bytes, 16-byte aligned (node_first is even)
-                    const float4* const c2 = reinterpret_cast<const float4*>(box + 2u * node);
-                    const float4 x = c2[0], m = c2[1], z = c2[2];
-                    const float lo0[3] = {x.x, x.y, x.z}, hi0[3] = {x.w, m.x, m.y}, lo1[3] = {m.z, m.w, z.x}, hi1[3] = {z.y, z.z, z.w};
-                    double lb0, lb1;
-                    const bool go0 = open(lo0, hi0, lb0), go1 = open(lo1, hi1, lb1);
-                    if (go0 && go1) { pending |= 1u << bvh_level(node); node = 2u * node + (lb1 < lb0 ? 1u : 0u); }
-                    else if (go0 || go1) node = 2u * node + (go1 ? 1u : 0u);
-                    else walking = ascend();
+        const double e = tree_padding(words, p);
+        count = tree_walk<kStats>(
+            q, t, v, io.body ? body : 0u, io.body ? body + 1u : t.bodies,
+            // may this node be entered?  (every reason to skip one: this file's head)
+            [&](const float lo[3], const float hi[3], double& lb) {
+                lb = box_bound(p, e, lo, hi);
+                if (lb > max2) return false;
+                return !(bt != kRayNone && lb > bd2);
+            },
+            [&](uint32_t id, const float4 A, const float4 B, const float4 C, const float tlo[3], const float thi[3]) {
+                const double lb = box_bound(p, e, tlo, thi);
+                if (lb > max2 || (bt != kRayNone && lb > bd2)) return;   // counts only with lb <= d2: it cannot beat the best
+                double pt[3], cv, cw;
+                const int region = tri_closest(p, A, B, C, pt, cv, cw);
+                const double w3[3] = {p[0] - pt[0], p[1] - pt[1], p[2] - pt[2]};
+                const double d2 = dot3(w3, w3);
+                if (lb <= d2 && d2 <= max2 && better(d2, id, bd2, bt)) {
+                    bd2 = d2; bt = id; bregion = region; bv = cv; bw = cw;
+                    bq[0] = pt[0]; bq[1] = pt[1]; bq[2] = pt[2];
                 }
-                if (!walking) break;
-                // (a sibling that waited was opened against an older best: its triangles' own bounds meet the current one below)
-                // the leaf's triangles: ids, corners' rows and corners each in one round of loads (an entered leaf holds a triangle: lo < ntri)
-                const uint32_t lo = (node - (1u << depth)) * kBvhLeaf, n = ntri - lo < kBvhLeaf ? ntri - lo : kBvhLeaf;
-                uint32_t id[kBvhLeaf];
-                int4 at[kBvhLeaf];
-                float4 A[kBvhLeaf], B[kBvhLeaf], C[kBvhLeaf];
-#pragma unroll
-                for (uint32_t j = 0; j < kBvhLeaf; j++) id[j] = v.order[tfirst + lo + (j < n ? j : 0u)];   // (behind the end: the first again, not tested)
-#pragma unroll
-                for (uint32_t j = 0; j < kBvhLeaf; j++) at[j] = q.tri[id[j]];
-#pragma unroll
-                for (uint32_t j = 0; j < kBvhLeaf; j++) { A[j] = q.pos[at[j].x]; B[j] = q.pos[at[j].y]; C[j] = q.pos[at[j].z]; }
-#pragma unroll
-                for (uint32_t j = 0; j < kBvhLeaf; j++) {
-                    if (j >= n) continue;
-                    float tlo[3] = {INFINITY, INFINITY, INFINITY}, thi[3] = {-INFINITY, -INFINITY, -INFINITY};
-                    box_add(tlo, thi, A[j]); box_add(tlo, thi, B[j]); box_add(tlo, thi, C[j]);
-                    if (kStats) tris++;
-                    const double lb = box_bound(p, e, tlo, thi);
-                    if (lb > max2 || (bt != kRayNone && lb > bd2)) continue;   // counts only with lb <= d2: it cannot beat the best
-                    double pt[3], cv, cw;
-                    const int region = tri_closest(p, A[j], B[j], C[j], pt, cv, cw);
-                    const double w3[3] = {p[0] - pt[0], p[1] - pt[1], p[2] - pt[2]};
-                    const double d2 = dot3(w3, w3);
-                    if (lb <= d2 && d2 <= max2 && better(d2, id[j], bd2, bt)) {
-                        bd2 = d2; bt = id[j]; bregion = region; bv = cv; bw = cw;
-                        bq[0] = pt[0]; bq[1] = pt[1]; bq[2] = pt[2];
-                    }
-                }
-                walking = ascend();
-            }
-        }
+            });
     }
     const double zero[3] = {0.0, 0.0, 0.0};
     if (bad) closest_store(io, i, -1, -1, -1, -1, 0.0, zero, 0.0, 0.0);                 // TETSIM_CLOSEST_INVALID
     else if (bt == kRayNone) closest_store(io, i, 0, -1, -1, -1, 0.0, zero, 0.0, 0.0);
-    else closest_store(io, i, 1, io.query_body ? static_cast<int32_t>(body) : t.tri_body ? t.tri_body[bt] : 0, static_cast<int32_t>(bt), bregion, sqrt(bd2), bq, bv, bw);
-    if (kStats) { v.stats[2u * static_cast<size_t>(i)] = boxes; v.stats[2u * static_cast<size_t>(i) + 1u] = tris; }
+    else closest_store(io, i, 1, io.body ? static_cast<int32_t>(body) : t.tri_body ? t.tri_body[bt] : 0, static_cast<int32_t>(bt), bregion, sqrt(bd2), bq, bv, bw);
+    if (kStats) tree_store_counts(v, i, count);
 }
 
 }  // namespace
 
-void query_launch_closest_bvh(hipStream_t s, const QueryDev& q, const QueryBodiesDev& b, const BvhDev& v, const ClosestIo& io) {
-    // a dispatch holds at most 2^32 - 1 work-items (max_grid_blocks)
-    const uint64_t chunk = static_cast<uint64_t>(max_grid_blocks(256u)) * 256u;
-    for (uint64_t first = 0; first < io.count; first += chunk) {
-        const uint64_t n = std::min<uint64_t>(chunk, io.count - first);
-        const dim3 grid(static_cast<uint32_t>((n + 255u) / 256u));
-#ifdef TETSIM_BVH_STATS
-        if (v.stats) { hipLaunchKernelGGL(bvh_closest_kernel<true>, grid, dim3(256), 0, s, q, b, v, io, static_cast<uint32_t>(first)); continue; }
-#endif
-        hipLaunchKernelGGL(bvh_closest_kernel<false>, grid, dim3(256), 0, s, q, b, v, io, static_cast<uint32_t>(first));
-    }
+void query_launch_closest_bvh(hipStream_t s, const QueryDev& q, const QueryBodiesDev& b, const BvhDev& v, const CastIo& io) {
+    launch_per_lane(s, bvh_closest_kernel<false>, bvh_closest_kernel<kTreeCounts>, q, b, v, io);
 }
 
 }  // namespace tetsim

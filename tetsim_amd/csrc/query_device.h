@@ -1,5 +1,5 @@
 // query_device.h -- range sensors on the device (include/tetsim.h: tetsim_raycast_visual_device / tetsim_raycast_visual_bvh_device /
-// tetsim_visual_bounding_spheres_device): what tetsim_visual.hip and query_kernels.hip share beyond dev_common.h -- the one definition of
+// tetsim_visual_bounding_spheres_device): what tetsim_query.hip and the query kernels' units share beyond dev_common.h -- the one definition of
 // an invalid ray, the per-body tables of a handle's visual mesh and the launches over them.
 #pragma once
 #include "dev_common.h"
@@ -23,7 +23,7 @@ __host__ __device__ inline int ray_defect(const double o[3], const double d[3], 
     return kRayGood;
 }
 
-// The bodies of a handle's visual mesh, built once on the host (tetsim_visual.hip: ensure_row_tables / ensure_triangle_tables).
+// The bodies of a handle's visual mesh, built once on the host (tetsim_query.hip: ensure_row_tables / ensure_triangle_tables).
 struct QueryBodiesDev {
     uint32_t bodies = 0;
     const uint32_t* row_body = nullptr;     // [nvis] the body whose tets carry the row
@@ -37,11 +37,12 @@ struct QueryBodiesDev {
 constexpr uint32_t kCastTile = 256;         // triangles staged in LDS at a time = rays of a workgroup
 constexpr uint32_t kCastCandCap = 1u << 17; // candidates of the split launches (few rays): 2 MiB, whatever the count
 
-// the caller's records: ray i at rays + i * ray_stride, its body at ray_body[i] (null: the whole mesh), its hit at hits + i * hit_stride
+// The caller's records, of a cast or of a closest-point call (the struct keeps its first user's name): ray or query i at in + i * in_stride,
+// its body at body[i] (null: the whole mesh), its hit or answer at out + i * out_stride.
 struct CastIo {
-    const char* rays; uint64_t ray_stride;
-    const int32_t* ray_body;
-    char* hits; uint64_t hit_stride;
+    const char* in; uint64_t in_stride;
+    const int32_t* body;
+    char* out; uint64_t out_stride;
     uint32_t count;
 };
 
@@ -49,7 +50,7 @@ struct CastIo {
 void query_launch_body_spheres(hipStream_t s, const QueryDev& q, const QueryBodiesDev& b);
 // row k of dst = (centre xyz, radius) of body k, 4 doubles; a body without rows: zeros
 void query_launch_spheres_out(hipStream_t s, const QueryBodiesDev& b, char* dst, uint64_t stride);
-// The cast: q.sphere (io.ray_body null) or b.spheres (else) must be current.  cand: kCastCandCap entries.
+// The cast: q.sphere (io.body null) or b.spheres (else) must be current.  cand: kCastCandCap entries.
 void query_launch_cast_device(hipStream_t s, const QueryDev& q, const QueryBodiesDev& b, const CastIo& io, RayCand* cand);
 // into how many parts the triangle range is split over gridDim.y (few rays must not run on few compute units)
 uint32_t query_cast_splits(uint32_t tiles, uint32_t count);
@@ -90,7 +91,7 @@ std::string bvh_build_topology(const float* pos, uint32_t pos_stride, const int3
                                const uint32_t* tri_first, uint32_t bodies, BvhTopology* out);
 // the refit, in stream order behind the skinning: two launches whatever the number of bodies (the second only if some body has tops)
 void query_launch_bvh_refit(hipStream_t s, const QueryDev& q, const QueryBodiesDev& b, const BvhDev& v);
-// The cast: q.sphere (io.ray_body null) or b.spheres (else) and the boxes must be current.
+// The cast: q.sphere (io.body null) or b.spheres (else) and the boxes must be current.
 void query_launch_cast_bvh(hipStream_t s, const QueryDev& q, const QueryBodiesDev& b, const BvhDev& v, const CastIo& io);
 
 // ---- closest-point queries through the same tree (include/tetsim.h: tetsim_closest_visual_device; query_closest.hip) ----------------
@@ -106,14 +107,7 @@ __host__ __device__ inline int point_query_defect(const double p[3], double max_
     if (max_distance < 0.0) return kPointNegativeLimit;
     return kPointGood;
 }
-// the caller's records: query i at queries + i * query_stride, its body at query_body[i] (null: the whole mesh), its record at out + i * out_stride
-struct ClosestIo {
-    const char* queries; uint64_t query_stride;
-    const int32_t* query_body;
-    char* out; uint64_t out_stride;
-    uint32_t count;
-};
-// The queries: q.sphere (io.query_body null) or b.spheres (else) and the boxes must be current.
-void query_launch_closest_bvh(hipStream_t s, const QueryDev& q, const QueryBodiesDev& b, const BvhDev& v, const ClosestIo& io);
+// The queries (io: CastIo above): q.sphere (io.body null) or b.spheres (else) and the boxes must be current.
+void query_launch_closest_bvh(hipStream_t s, const QueryDev& q, const QueryBodiesDev& b, const BvhDev& v, const CastIo& io);
 
 }  // namespace tetsim

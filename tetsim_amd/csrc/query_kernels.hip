@@ -193,7 +193,7 @@ __global__ __launch_bounds__(256) void body_spheres_out_kernel(const uint32_t* _
     double c[3];
     sphere_centre(w, c);
     o[0] = c[0]; o[1] = c[1]; o[2] = c[2];
-    o[3] = sqrt(__longlong_as_double(static_cast<long long>(*reinterpret_cast<const unsigned long long*>(w + 6))));
+    o[3] = sphere_radius(w);
 }
 
 // A lane = one ray, a workgroup = kCastTile rays; grid = (workgroups of rays, parts of the triangle range).  The workgroup goes through
@@ -226,12 +226,12 @@ __global__ __launch_bounds__(256) void cast_device_kernel(QueryDev q, QueryBodie
         const uint32_t cur = s_next;      // the same for the whole workgroup: every barrier below is reached by all of it
         if (cur == kRayNone) break;
         const bool mine = todo && c.body == cur;
-        const uint64_t lo = io.ray_body ? t.tri_first[cur] : 0u, hi = io.ray_body ? t.tri_first[cur + 1u] : q.ntri;
+        const uint64_t lo = io.body ? t.tri_first[cur] : 0u, hi = io.body ? t.tri_first[cur + 1u] : q.ntri;
         for (uint64_t base = lo + static_cast<uint64_t>(blockIdx.y) * kCastTile; base < hi; base += static_cast<uint64_t>(gridDim.y) * kCastTile) {
             __syncthreads();              // (the tile before this one has been read)
             const uint64_t k = base + threadIdx.x;
             if (k < hi) {
-                const uint32_t id = io.ray_body ? t.tri_sorted[k] : static_cast<uint32_t>(k);
+                const uint32_t id = io.body ? t.tri_sorted[k] : static_cast<uint32_t>(k);
                 const int4 v = q.tri[id];
                 tri_prepare(q.pos[v.x], q.pos[v.y], q.pos[v.z], s_tri[threadIdx.x]);
                 s_id[threadIdx.x] = id;
@@ -284,9 +284,7 @@ __global__ __launch_bounds__(256) void cast_finish_kernel(QueryDev q, QueryBodie
 
 void query_decode_sphere(const uint32_t words[kSphereWords], double centre[3], double* radius) {
     sphere_centre(words, centre);
-    double r2;
-    std::memcpy(&r2, words + 6, 8);
-    *radius = std::sqrt(r2);
+    *radius = sphere_radius(words);
 }
 
 void query_launch_sphere(hipStream_t s, const QueryDev& q) {
@@ -335,7 +333,7 @@ uint32_t query_cast_splits(uint32_t tiles, uint32_t count) {
 }
 
 void query_launch_cast_device(hipStream_t s, const QueryDev& q, const QueryBodiesDev& b, const CastIo& io, RayCand* cand) {
-    const uint32_t tiles = io.ray_body ? b.max_tiles : (q.ntri + kCastTile - 1u) / kCastTile;
+    const uint32_t tiles = io.body ? b.max_tiles : (q.ntri + kCastTile - 1u) / kCastTile;
     const uint32_t parts = query_cast_splits(tiles, io.count);
     if (parts > 1u) {   // (parts * count <= kCastCandCap: one launch holds every ray)
         hipLaunchKernelGGL(cast_device_kernel<true>, dim3((io.count + kCastTile - 1u) / kCastTile, parts), dim3(256), 0, s, q, b, io, 0u, cand);

@@ -1,7 +1,8 @@
-// query_rays.h -- the device functions the ray kernels share (query_kernels.hip: brute force; query_bvh.hip: the refitted tree): the
-// sphere keys, three.js r160's ray preparation and triangle test, the lexicographic winner, and a caller's ray and hit records in device
-// memory.  One text for both units, so that "the existing device function unchanged" (include/tetsim.h) holds by construction; both are
-// built with -ffp-contract=off.  f64 arithmetic on the f32 positions, every operation rounded separately, sums left to right.
+// query_rays.h -- the device functions the query kernels share (query_kernels.hip: brute force; query_bvh.hip and query_closest.hip: the
+// refitted tree): the sphere keys, three.js r160's ray preparation and triangle test, the lexicographic winner, a record's body, and a
+// caller's ray and hit records in device memory.  One text for all three units, so that "the existing device function unchanged"
+// (include/tetsim.h) holds by construction; all three are built with -ffp-contract=off.  f64 arithmetic on the f32 positions, every
+// operation rounded separately, sums left to right.
 #pragma once
 #include "dev_common.h"
 #include "query_device.h"
@@ -28,6 +29,17 @@ __host__ __device__ inline void sphere_centre(const uint32_t* w, double c[3]) {
     }
 }
 
+// the radius from the keys' last two words: the square root of the largest squared distance to the centre (Sphere.radius = sqrt(maxRadiusSq))
+__host__ __device__ inline double sphere_radius(const uint32_t* w) {
+    double r2;
+#if defined(__HIP_DEVICE_COMPILE__)
+    r2 = __longlong_as_double(static_cast<long long>(*reinterpret_cast<const unsigned long long*>(w + 6)));
+#else
+    std::memcpy(&r2, w + 6, 8);
+#endif
+    return sqrt(r2);
+}
+
 // a box grown by a point: the exact f32 min / max (the refit's leaves, a triangle's own box in both traversals)
 __device__ inline void box_add(float lo[3], float hi[3], const float4 p) {
     const float v[3] = {p.x, p.y, p.z};
@@ -41,7 +53,7 @@ __device__ inline double dot3(const double* u, const double* v) { return u[0] * 
 __device__ inline RayPrep ray_prepare(const RayIn& r, const uint32_t* __restrict__ words) {
     double c[3];
     sphere_centre(words, c);
-    const double radius = sqrt(__longlong_as_double(static_cast<long long>(*reinterpret_cast<const unsigned long long*>(words + 6))));
+    const double radius = sphere_radius(words);
     const double radius2 = radius * radius;
     double o2[3], v[3];
     for (int k = 0; k < 3; k++) o2[k] = r.o[k] + r.d[k] * r.near;          // Ray.recast(near) = at(near)
@@ -112,26 +124,32 @@ __device__ inline bool tri_hit(const RayPrep& r, const float4 A, const float4 B,
 
 __device__ inline bool better(double d, uint32_t t, double bd, uint32_t bt) { return t != kRayNone && (bt == kRayNone || d < bd || (d == bd && t < bt)); }
 
+// The body of record i and that body's sphere keys; without a body array, body 0 and the whole mesh's keys.  true: the body is outside the handle.
+__device__ inline bool record_body(const QueryDev& q, const QueryBodiesDev& t, const int32_t* body_of, uint32_t i, uint32_t* body, const uint32_t** words) {
+    *body = 0u;
+    *words = q.sphere;
+    if (!body_of) return false;
+    const int32_t b = body_of[i];
+    if (b < 0 || static_cast<uint32_t>(b) >= t.bodies) return true;
+    *body = static_cast<uint32_t>(b);
+    *words = t.spheres + static_cast<size_t>(b) * kSphereWords;
+    return false;
+}
+
 // A caller's ray: its record, what is wrong with it (ray_defect; a body outside the handle), its body and that body's sphere keys.
 struct CastRay { RayIn r; uint32_t body; bool bad; const uint32_t* words; };
 __device__ inline CastRay cast_load(const QueryDev& q, const QueryBodiesDev& t, const CastIo& io, uint32_t i) {
     CastRay c;
-    const double* const src = reinterpret_cast<const double*>(io.rays + static_cast<uint64_t>(i) * io.ray_stride);
+    const double* const src = reinterpret_cast<const double*>(io.in + static_cast<uint64_t>(i) * io.in_stride);
     for (int k = 0; k < 3; k++) { c.r.o[k] = src[k]; c.r.d[k] = src[3 + k]; }
     c.r.near = src[6]; c.r.far = src[7];
     c.bad = ray_defect(c.r.o, c.r.d, c.r.near, c.r.far) != kRayGood;
-    c.body = 0u;
-    c.words = q.sphere;
-    if (io.ray_body) {
-        const int32_t b = io.ray_body[i];
-        if (b < 0 || static_cast<uint32_t>(b) >= t.bodies) c.bad = true;
-        else { c.body = static_cast<uint32_t>(b); c.words = t.spheres + static_cast<size_t>(b) * kSphereWords; }
-    }
+    if (record_body(q, t, io.body, i, &c.body, &c.words)) c.bad = true;
     return c;
 }
 // the 48 bytes of a hit record as six 8-byte stores (the record is 8-byte aligned, no more)
 __device__ inline void cast_store(const CastIo& io, uint32_t i, int32_t hit, int32_t body, int32_t triangle, double distance, const double pt[3]) {
-    unsigned long long* const o = reinterpret_cast<unsigned long long*>(io.hits + static_cast<uint64_t>(i) * io.hit_stride);
+    unsigned long long* const o = reinterpret_cast<unsigned long long*>(io.out + static_cast<uint64_t>(i) * io.out_stride);
     o[0] = static_cast<unsigned long long>(static_cast<uint32_t>(hit)) | (static_cast<unsigned long long>(static_cast<uint32_t>(body)) << 32);
     o[1] = static_cast<unsigned long long>(static_cast<uint32_t>(triangle));
     o[2] = static_cast<unsigned long long>(__double_as_longlong(distance));
@@ -141,7 +159,7 @@ __device__ inline void cast_store_result(const QueryBodiesDev& t, const CastIo& 
     const double zero[3] = {0.0, 0.0, 0.0};
     if (c.bad) cast_store(io, i, -1, -1, -1, 0.0, zero);                  // TETSIM_RAY_INVALID
     else if (bt == kRayNone) cast_store(io, i, 0, -1, -1, 0.0, zero);
-    else cast_store(io, i, 1, io.ray_body ? static_cast<int32_t>(c.body) : t.tri_body ? t.tri_body[bt] : 0, static_cast<int32_t>(bt), bd, bp);
+    else cast_store(io, i, 1, io.body ? static_cast<int32_t>(c.body) : t.tri_body ? t.tri_body[bt] : 0, static_cast<int32_t>(bt), bd, bp);
 }
 
 }  // namespace tetsim

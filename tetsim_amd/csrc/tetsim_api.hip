@@ -1,5 +1,5 @@
 // tetsim_api.hip -- C ABI of libtetsim_hip.so, part 1 (include/tetsim.h): handle lifecycle and stepping (stream / graph
-// orchestration of the gfx950 kernels).  State read-back: tetsim_state.hip; visual mesh and grab: tetsim_visual.hip;
+// orchestration of the gfx950 kernels).  State read-back: tetsim_state.hip; visual mesh and grab: tetsim_visual.hip; its queries: tetsim_query.hip;
 // measurement: tetsim_measure.hip.  See body.h for all translation units.
 // Every stepping call: open_call (checks, device, what a step makes stale) and take_params (a block of stamps, the host's record) behind
 // push_params / stage_params; the path by frame_now / nh_frame_now / nh_one_now (body.h), top to bottom in tetsim_step and tetsim_step_n;

@@ -866,19 +866,27 @@ class SoftBodyHIP:
 
     def _raycastDevice(self, call, rays, bodies, out, stream):
         import torch
+        out = self._recordsDevice(call, "rays", rays, 8, bodies, "rayHits", 48, out, stream)
+        i32, f64 = out.view(torch.int32), out.view(torch.float64)   # (rows of 12 / 6 of them; a strided `out` keeps its row stride)
+        return {"hit": i32[:, 0], "body": i32[:, 1], "triangle": i32[:, 2], "distance": f64[:, 2], "point": f64[:, 3:6], "raw": out}
+
+    def _recordsDevice(self, call, name, records, width, bodies, key, out_bytes, out, stream):
+        """What the device calls on records share: `records` is checked (float64 [count, width], `name` in the refusal), `bodies` too, the
+        uint8 [count, out_bytes] answer is `out` or the cached tensor `key`, and `call` gets pointers and strides by the ABI's rules (no
+        pointer for no rows, stride 0 for at most one).  Returns the answer's tensor."""
+        import torch
         dev, s = self._torch_stream(torch, stream)
-        if (not isinstance(rays, torch.Tensor) or rays.dtype != torch.float64 or rays.device != dev or rays.dim() != 2 or rays.shape[1] != 8
-                or (rays.shape[0] and rays.stride(1) != 1) or (rays.shape[0] > 1 and rays.stride(0) < 8)):
-            raise ValueError("rays must be a float64 tensor on %s of shape (count, 8) with contiguous, non-overlapping rows" % (dev,))
-        n = int(rays.shape[0])
+        if (not isinstance(records, torch.Tensor) or records.dtype != torch.float64 or records.device != dev or records.dim() != 2 or records.shape[1] != width
+                or (records.shape[0] and records.stride(1) != 1) or (records.shape[0] > 1 and records.stride(0) < width)):
+            raise ValueError("%s must be a float64 tensor on %s of shape (count, %d) with contiguous, non-overlapping rows" % (name, dev, width))
+        n = int(records.shape[0])
         if bodies is not None and (not isinstance(bodies, torch.Tensor) or bodies.dtype != torch.int32 or bodies.device != dev
                                    or tuple(bodies.shape) != (n,) or not bodies.is_contiguous()):
             raise ValueError("bodies must be a contiguous int32 tensor on %s of shape (%d,)" % (dev, n))
-        out = self._out_rows(torch, dev, "rayHits", out, (n, 48), torch.uint8, align=8)
-        capi.check(call(self._h, rays.data_ptr() if n else None, 8 * rays.stride(0) if n > 1 else 0, bodies.data_ptr() if bodies is not None and n else None, n,
+        out = self._out_rows(torch, dev, key, out, (n, out_bytes), torch.uint8, align=8)
+        capi.check(call(self._h, records.data_ptr() if n else None, 8 * records.stride(0) if n > 1 else 0, bodies.data_ptr() if bodies is not None and n else None, n,
                         out.data_ptr() if n else None, out.stride(0) if n > 1 else 0, s), self._h)
-        i32, f64 = out.view(torch.int32), out.view(torch.float64)   # (rows of 12 / 6 of them; a strided `out` keeps its row stride)
-        return {"hit": i32[:, 0], "body": i32[:, 1], "triangle": i32[:, 2], "distance": f64[:, 2], "point": f64[:, 3:6], "raw": out}
+        return out
 
     # -- closest points (include/tetsim.h: tetsim_closest_visual_device / tetsim_closest_visual) --------------------
     def closestPointsDevice(self, queries, bodies=None, out=None, stream=None):
@@ -891,18 +899,7 @@ class SoftBodyHIP:
         query or body gets found = _capi.CLOSEST_INVALID instead of an exception.  The handle's first tree call builds the topology on the
         host and may block.  Valid for work enqueued on `stream` (as in exportTensors) after this returns."""
         import torch
-        dev, s = self._torch_stream(torch, stream)
-        if (not isinstance(queries, torch.Tensor) or queries.dtype != torch.float64 or queries.device != dev or queries.dim() != 2 or queries.shape[1] != 4
-                or (queries.shape[0] and queries.stride(1) != 1) or (queries.shape[0] > 1 and queries.stride(0) < 4)):
-            raise ValueError("queries must be a float64 tensor on %s of shape (count, 4) with contiguous, non-overlapping rows" % (dev,))
-        n = int(queries.shape[0])
-        if bodies is not None and (not isinstance(bodies, torch.Tensor) or bodies.dtype != torch.int32 or bodies.device != dev
-                                   or tuple(bodies.shape) != (n,) or not bodies.is_contiguous()):
-            raise ValueError("bodies must be a contiguous int32 tensor on %s of shape (%d,)" % (dev, n))
-        out = self._out_rows(torch, dev, "closestPoints", out, (n, 64), torch.uint8, align=8)
-        capi.check(self._L.tetsim_closest_visual_device(self._h, queries.data_ptr() if n else None, 8 * queries.stride(0) if n > 1 else 0,
-                                                        bodies.data_ptr() if bodies is not None and n else None, n,
-                                                        out.data_ptr() if n else None, out.stride(0) if n > 1 else 0, s), self._h)
+        out = self._recordsDevice(self._L.tetsim_closest_visual_device, "queries", queries, 4, bodies, "closestPoints", 64, out, stream)
         i32, f64 = out.view(torch.int32), out.view(torch.float64)   # (rows of 16 / 8 of them; a strided `out` keeps its row stride)
         return {"found": i32[:, 0], "body": i32[:, 1], "triangle": i32[:, 2], "region": i32[:, 3], "distance": f64[:, 2], "point": f64[:, 3:6],
                 "v": f64[:, 6], "w": f64[:, 7], "raw": out}
